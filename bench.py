@@ -6,11 +6,17 @@ level-5 core chain) followed by kz_decode_blocks of the produced block streams, 
 resident in HBM.  Blocks are independent (K/io/CompressedOutputStream.java:792,907): with N GPUs
 block g goes to rank g mod N, no collective on the data path.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 With N > 1 and no WORLD_SIZE in the environment the script re-executes itself under
 torch.distributed.run (one rank per GPU); launched by torch.distributed.run it uses the ranks it is given.
-Rank 0 prints ONE JSON line:
+A plain run sets up the bulk batch, runs W warm-up and K timed steps of it, writes the last timed step's outputs
+with --dump-outputs, and rank 0 prints ONE JSON line with the headline (metric, value, unit, ms_per_step, config's
+encode / decode rates).  --full adds everything else below, as before, to that line.
   value              the bulk batch (--blocks 4 MiB blocks per GPU per step, weak scaling), timed without instrumentation
+  ms_per_step        wall time of one timed step of the bulk batch (its encode and its decode)
+  --dump-outputs DIR what the last timed step handed its caller, as .npy (float64 per-block results, float32 samples of
+                     the encoded and decoded bytes at fixed seeded positions; 64 MB at most in all): see dump_outputs
+  (--full)
   roofline, kernels  from one extra instrumented step (HIP events around every launch, on the stream it is launched on):
                      roofline.kernel = the kernel with the largest SUMMED GPU time of the step (rocprofv3's top row);
                      achieved = the algorithmic bytes of that kernel's pipeline stage / the summed time of the
@@ -230,6 +236,13 @@ def compact(out):
     return o
 
 
+def headline(out):
+    """the printed line of a plain run: the contract's keys and the headline batch's rates (no --full sections)"""
+    o = {k: _r(v) for k, v in out.items() if k not in ("config", "roofline", "kernels", "cpu_baseline") and not k.startswith("_")}
+    o["config"] = {k: _r(v) for k, v in out["config"].items() if k not in ("chains", "shapes")}
+    return o
+
+
 def load_traffic(path, B, chain, entropy):
     if not os.path.exists(path):                                       # this round's PMC passes not collected (yet): the newest earlier round's,
         import glob                                                    # named as such in roofline.traffic_source
@@ -248,6 +261,45 @@ def load_traffic(path, B, chain, entropy):
     # KZ_GIT_SHA into the file; the kernel TIMES next to it are this run's own)
     tj["_path"] = "%s @ %s" % (os.path.relpath(path, ROOT), tj.get("git_sha") or "unstamped")
     return tj
+
+
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: payload of all the .npy files together (64 MB)
+DUMP_SEED = 20240601           # the sample positions: the same for every run and every build
+
+
+def dump_outputs(path, enc_res, dec_res, d_enc, d_dec, budget=DUMP_BYTES, prefix=""):
+    """Write what one step of the hot path returned to its caller as DIR/<prefix><name>.npy:
+      encode_bits, encode_length, encode_skip_flags, encode_mode, decode_length   float64 [blocks]: the BlockResult fields
+      encoded_sample  float32 [blocks, k]: byte j of block b's encoded stream at j = floor(u[b, i] * bytes_b), u a fixed
+                      seeded uniform sample and bytes_b = (bits_b + 7) // 8 (the stream ends there; positions move only if the
+                      bit lengths differ, which encode_bits shows)
+      decoded_sample  float32 [blocks, k2]: the same over the decoded blocks (decode_length bytes each)
+    d_enc / d_dec are the [blocks, stride] uint8 tensors the step wrote (device or host).  Three quarters of what the per-block
+    arrays leave of `budget` go to encoded_sample, the rest to decoded_sample.  Returns {name: bytes written}."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    nb = len(enc_res)
+    per_block = {"encode_bits": [r.bits for r in enc_res], "encode_length": [r.length for r in enc_res],
+                 "encode_skip_flags": [r.skipFlags for r in enc_res], "encode_mode": [r.mode for r in enc_res],
+                 "decode_length": [r.length for r in dec_res]}
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in per_block.items()}
+    left = budget - 8 * nb * len(arrays) - 4096                        # (4096: the files' headers)
+    rng = np.random.default_rng(DUMP_SEED)
+    for name, buf, nbytes, share in (("encoded_sample", d_enc, (arrays["encode_bits"].astype(np.int64) + 7) // 8, 0.75),
+                                     ("decoded_sample", d_dec, arrays["decode_length"].astype(np.int64), 0.25)):
+        k = max(1, min(int(left * share) // (4 * max(nb, 1)), buf.shape[1]))
+        u = rng.random((nb, k))
+        n = np.clip(nbytes, 1, buf.shape[1])[:, None]                 # every index stays inside its row of the buffer
+        pos = np.minimum((u * n).astype(np.int64), n - 1)
+        flat = (np.arange(nb, dtype=np.int64)[:, None] * buf.shape[1] + pos).reshape(-1)
+        vals = buf.reshape(-1)[torch.from_numpy(flat).to(buf.device)].to(torch.float32).cpu().numpy().reshape(nb, k)
+        vals[nbytes <= 0] = -1.0                                       # a block without bytes has nothing to sample
+        arrays[name] = vals
+    sizes = {}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, prefix + name + ".npy"), a)
+        sizes[name] = int(a.nbytes)
+    return sizes
 
 
 def free_port():
@@ -334,7 +386,15 @@ def main():
     ap.add_argument("--profiles-tag", default="r06", help="profiles/<tag>_pmc_traffic*.json: per-kernel HBM bytes from separate rocprofv3 --pmc passes (tools/pmc_traffic.py)")
     ap.add_argument("--traffic-json", default="", help="override the PMC traffic file of the headline chain")
     ap.add_argument("--cpu-sample-blocks", type=int, default=0, help="0 = auto (about 10-30 s of CPU work)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the instrumented step (roofline, kernels), the two-stream row, "
+                    "config.chains, config.shapes, the cpu_baseline with its oracle comparisons and the --detail-json record (the --no-* "
+                    "options trim this part); a plain run does only the headline's warm-up and timed steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the outputs of the headline's last timed step to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if not args.full:                                                  # a plain run: every section below the headline is skipped
+        args.no_two_streams = args.no_chains = args.no_shapes = args.no_cpu_baseline = True
 
     # ---- N > 1 without a launcher: start one rank per GPU ourselves (the driver's `python bench.py --gpus N`) ----
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -437,6 +497,7 @@ def main():
             for k, r in enumerate(res2):
                 if r.status or r.length != self.lengths[k]:
                     raise RuntimeError("decode status %d len %d" % (r.status, r.length))
+            self.res_dec = res2
             return t1 - t0, t2 - t1, res
 
         def round_trip_ok(self):
@@ -446,9 +507,10 @@ def main():
             tl = int(self.lengths[-1])
             return ok and bool(torch.equal(self.d_in[-1, :tl], self.d_dec[-1, :tl]))
 
-    def timed_pass(src, nb, chain, entropy, steps, warmup, traffic_path, copy_rate=False, keep=False):
-        """warmup + `steps` timed steps (barrier and device sync on both sides, max over ranks), then ONE instrumented step
-        (HIP events around every kernel launch; stage timers for the host TEXT / UTF stages) -> dict"""
+    def timed_pass(src, nb, chain, entropy, steps, warmup, traffic_path, copy_rate=False, keep=False, instrument=True, on_timed=None):
+        """warmup + `steps` timed steps (barrier and device sync on both sides, max over ranks), on_timed(batch, encode results)
+        with the last timed step's outputs, then (instrument) ONE instrumented step (HIP events around every kernel launch; stage
+        timers for the host TEXT / UTF stages) -> dict"""
         bt = Batch(src, nb, chain, entropy)
         for _ in range(warmup):
             bt.step()
@@ -465,10 +527,18 @@ def main():
         elapsed, te, td = max_over_ranks([T1 - T0, te, td])
         if not bt.round_trip_ok():
             raise SystemExit("round trip mismatch (%s & %s): decoded blocks differ from the input" % (chain, entropy))
+        if on_timed is not None:
+            on_timed(bt, res)
         step_bytes = float(bt.nbytes)
         comp_bytes = float(sum((r.bits + 7) // 8 for r in res))
         post_bytes = float(sum(r.length for r in res))
         z, c = post_bytes / step_bytes, comp_bytes / step_bytes
+        rates = {"chain": chain, "entropy": entropy, "blocks_per_gpu_per_step": nb, "steps": steps, "warmup": warmup,
+                 "elapsed": elapsed, "t_enc": te, "t_dec": td, "step_bytes": step_bytes, "z": z, "c": c,
+                 "enc_dec_MBps": step_bytes * world * steps / elapsed / 1e6, "encode_MBps": step_bytes * world * steps / te / 1e6,
+                 "decode_MBps": step_bytes * world * steps / td / 1e6, "ms_per_step": elapsed / steps * 1e3}
+        if not instrument:
+            return dict(rates, roofline=None, kernels=[], host_stage_ms_per_step=None)
         ctx.set_kernel_timing(True)
         ctx.reset_kernel_timing()
         bt.step()
@@ -509,11 +579,7 @@ def main():
                 if t and k["ms_per_step"] > 0:
                     k["hbm_traffic_GBs"] = t["hbm_bytes_per_launch"] * k["launches_per_step"] / (k["ms_per_step"] * 1e-3) / 1e9
         roof = roofline_of(kernels, per_stage_alg, alg_enc, alg_dec, step_bytes, te, td, steps, traffic, copy_gbs)
-        out = {"chain": chain, "entropy": entropy, "blocks_per_gpu_per_step": nb, "steps": steps, "warmup": warmup,
-               "elapsed": elapsed, "t_enc": te, "t_dec": td, "step_bytes": step_bytes, "z": z, "c": c,
-               "enc_dec_MBps": step_bytes * world * steps / elapsed / 1e6, "encode_MBps": step_bytes * world * steps / te / 1e6,
-               "decode_MBps": step_bytes * world * steps / td / 1e6, "ms_per_step": elapsed / steps * 1e3,
-               "roofline": roof, "kernels": kernels, "host_stage_ms_per_step": host_ms}
+        out = dict(rates, roofline=roof, kernels=kernels, host_stage_ms_per_step=host_ms)
         if keep:                                                       # a sample of the HIP block streams for the oracle comparison in the cpu_baseline leg
             nsm = min(nb, src.shape[0], 16)                            # (rows 0 .. d-1 of the batch are the d distinct blocks)
             out["_sample"] = [(int(res[k].bits), int(res[k].skipFlags), int(res[k].length), bt.d_enc[k, :(int(res[k].bits) + 7) // 8].cpu().numpy().tobytes(),
@@ -525,7 +591,13 @@ def main():
     prof = lambda name: os.path.join(ROOT, "profiles", "%s_%s" % (tag, name))
 
     # ================= headline: the bulk batch, weak scaling, no instrumentation inside the timed region =================
-    head = timed_pass(d_host, B, args.chain, args.entropy, args.steps, args.warmup, args.traffic_json or prof("pmc_traffic.json"), copy_rate=True)
+    def dump(bt, res):
+        sizes = dump_outputs(args.dump_outputs, res, bt.res_dec, bt.d_enc[:bt.nb], bt.d_dec[:bt.nb], DUMP_BYTES // world,
+                             "rank%d_" % rank if world > 1 else "")
+        print("outputs of the last timed step: %s (%d B)" % (args.dump_outputs, sum(sizes.values())), file=sys.stderr)
+
+    head = timed_pass(d_host, B, args.chain, args.entropy, args.steps, args.warmup, args.traffic_json or prof("pmc_traffic.json"), copy_rate=args.full,
+                      instrument=args.full, on_timed=dump if args.dump_outputs else None)
     step_bytes, z, c = head["step_bytes"], head["z"], head["c"]
     value = head["enc_dec_MBps"]
     nk = int(os.environ.get("KZ_BENCH_KERNELS", "12"))
@@ -882,7 +954,9 @@ def main():
         except Exception:
             pass
         barrier()
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(json.dumps(headline(out), separators=(",", ":")))
+    elif rank == 0:
         # the full record goes to a file (tools/profile_round.sh copies it to profiles/<tag>_bench_kernels.json); the printed line is
         # the compact form: every BASELINE config and shape with its rates and its roofline, no per-kernel tables
         try:

@@ -136,20 +136,27 @@ def test_jni_shim_compiles_against_the_stub_header():
 
 
 def test_reference_patch_applies():
-    """integration/kanzi-hip.patch is a diff against the reference's Java tree (factories, DecodingTask, processBlock)."""
-    import shutil
-    import subprocess
-    import tempfile
-    ref = "/root/reference/java"
-    if not os.path.isdir(ref):
-        pytest.skip("the reference tree only exists in the build container")
-    with tempfile.TemporaryDirectory() as tmp:
-        for rel in ("transform/TransformFactory.java", "entropy/EntropyCodecFactory.java", "io/CompressedOutputStream.java", "io/CompressedInputStream.java"):
-            dst = os.path.join(tmp, "java/src/main/java/io/github/flanglet/kanzi", rel)
-            os.makedirs(os.path.dirname(dst), exist_ok=True)
-            shutil.copy(os.path.join(ref, "src/main/java/io/github/flanglet/kanzi", rel), dst)
-        r = subprocess.run(["patch", "-p1", "--dry-run", "-i", os.path.join(ROOT, "integration", "kanzi-hip.patch")], cwd=tmp, capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
+    """integration/kanzi-hip.patch is a diff against the reference's Java tree (factories, DecodingTask, processBlock).  The tree is
+    not part of this repository: tests/golden/reference_patch_preimage.json holds the sha256 of the reference lines every hunk
+    replaces (tools/patch_preimage.py), and each hunk's old side must be exactly those lines at that place, so the patch applies
+    to the reference with neither offset nor fuzz."""
+    import json
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import patch_preimage as P
+    patch = open(os.path.join(ROOT, "integration", "kanzi-hip.patch")).read()
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_patch_preimage.json")))["hunks"]
+    got = P.hunks(patch)
+    assert {h[0] for h in got} == {"java/src/main/java/io/github/flanglet/kanzi/" + rel for rel in (
+        "transform/TransformFactory.java", "entropy/EntropyCodecFactory.java", "io/CompressedOutputStream.java", "io/CompressedInputStream.java")}
+    assert len(got) == len(want)
+    for (path, start, count, old), w in zip(got, want):
+        assert (path, start, count) == (w["file"], w["old_start"], w["old_count"]), (path, start)
+        assert len(old) == count and start - 1 + count <= w["file_lines"], (path, start)
+        assert P.digest(old) == w["sha256"], "hunk @@ -%d of %s does not match the reference's lines" % (start, path)
+    # every hunk is well formed: its header's new-side count is the number of context and added lines that follow it
+    for m in re.finditer(r"^@@ -\d+(?:,\d+)? \+\d+,(\d+) @@\n((?:[ +\-].*\n|\n)*)", patch, flags=re.M):
+        body = m.group(2).splitlines()
+        assert sum(1 for l in body if not l.startswith("-")) == int(m.group(1)), m.group(0)[:60]
 
 
 def test_patch_hooks_exist_in_the_java_adapters():
