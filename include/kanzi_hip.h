@@ -13,7 +13,8 @@
  *       "false" is a normal outcome (Sequence.java:95-105) -> return 0.
  *   kz_entropy_encode / kz_entropy_decode
  *       K/EntropyEncoder.java:34 (int encode(byte[],int,int)) + dispose(), K/EntropyDecoder.java:33
- *       for K/entropy/ANSRangeEncoder.java:263-305, K/entropy/ANSRangeDecoder.java:189-236,
+ *       for K/entropy/ANSRangeEncoder.java:263-305, K/entropy/ANSRangeDecoder.java:189-236 (order 0 = ANS0 and
+ *       order 1 = ANS1, K/entropy/EntropyCodecFactory.java:124-128,175-179),
  *       K/entropy/HuffmanEncoder.java:380-416, K/entropy/HuffmanDecoder.java:353-390,
  *       K/entropy/FPAQEncoder.java:128-238, K/entropy/FPAQDecoder.java:161-335,
  *       K/entropy/NullEntropyEncoder.java:66-81.  The codec's output is a bit string (MSB first,
@@ -51,8 +52,10 @@ enum { KZ_T_NONE = 0, KZ_T_BWT = 1, KZ_T_LZ = 3, KZ_T_ZRLT = 6, KZ_T_MTFT = 7, K
    reaches the stream, and a binding maps by NAME (integration/java/HipByteTransform.java). */
 enum { KZ_DT_UNDEFINED = 0, KZ_DT_DNA = 1, KZ_DT_SMALL_ALPHABET = 2, KZ_DT_TEXT = 3, KZ_DT_MULTIMEDIA = 4, KZ_DT_EXE = 5,
        KZ_DT_NUMERIC = 6, KZ_DT_BASE64 = 7, KZ_DT_BIN = 8, KZ_DT_UTF8 = 9 };
-/* entropy ids: K/entropy/EntropyCodecFactory.java */
-enum { KZ_E_NONE = 0, KZ_E_HUFFMAN = 1, KZ_E_FPAQ = 2, KZ_E_ANS0 = 5 };
+/* entropy ids: K/entropy/EntropyCodecFactory.java (ANS1_TYPE = 8: order-1 ANS, 4 MiB chunks).  An ANS1 stream carries up to 256
+   context headers per chunk: kz_entropy_encode may need more than kz_max_block_stream_bytes(n) for it (n + n/8 + 1024 + 102400
+   per started 4 MiB is always enough); the batched calls store such a block as a raw copy, as the reference does (:926-973). */
+enum { KZ_E_NONE = 0, KZ_E_HUFFMAN = 1, KZ_E_FPAQ = 2, KZ_E_ANS0 = 5, KZ_E_ANS1 = 8 };
 /* error codes: K/Error.java:24-43 (returned negated); KZ_ERR_DEVICE is the one code the reference has no equivalent for */
 enum { KZ_ERR_MISSING_PARAM = 1, KZ_ERR_BLOCK_SIZE = 2, KZ_ERR_INVALID_CODEC = 3, KZ_ERR_READ_FILE = 11,
        KZ_ERR_WRITE_FILE = 12, KZ_ERR_PROCESS_BLOCK = 13, KZ_ERR_INVALID_FILE = 15, KZ_ERR_STREAM_VERSION = 16,

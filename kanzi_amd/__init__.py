@@ -28,12 +28,12 @@ LIB_PATH = os.path.join(_HERE, "libkanzi_hip.so")
 
 # transform ids (K/transform/TransformFactory.java:36-60) and entropy ids (K/entropy/EntropyCodecFactory.java)
 NONE_TYPE, BWT_TYPE, LZ_TYPE, ZRLT_TYPE, MTFT_TYPE, RANK_TYPE, SRT_TYPE, MM_TYPE, LZX_TYPE, PACK_TYPE, DNA_TYPE = 0, 1, 3, 6, 7, 8, 13, 15, 16, 18, 19
-E_NONE, E_HUFFMAN, E_FPAQ, E_ANS0 = 0, 1, 2, 5
+E_NONE, E_HUFFMAN, E_FPAQ, E_ANS0, E_ANS1 = 0, 1, 2, 5, 8
 TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "LZ": 3, "ZRLT": 6, "MTFT": 7, "RANK": 8, "TEXT": 10, "SRT": 13, "MM": 15, "LZX": 16, "UTF": 17, "PACK": 18, "DNA": 19}
 TEXT_TYPE, UTF_TYPE = 10, 17
 # Global.DataType (K/Global.java:40-80), numbered as KZ_DT_* in include/kanzi_hip.h
 DATA_TYPES = {"UNDEFINED": 0, "DNA": 1, "SMALL_ALPHABET": 2, "TEXT": 3, "MULTIMEDIA": 4, "EXE": 5, "NUMERIC": 6, "BASE64": 7, "BIN": 8, "UTF8": 9}
-ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "ANS0": 5}
+ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "ANS0": 5, "ANS1": 8}
 MEM_HOST, MEM_DEVICE = 0, 1
 
 STAGE_NAMES = ["bwt_fwd", "sbrt_fwd", "zrlt_fwd", "entropy_enc", "frame_enc",
@@ -429,6 +429,8 @@ class _EntropyEncoder:
         """EntropyEncoder.encode: returns count on success. Output bit string appended to self.bits."""
         s = np.ascontiguousarray(block[blkptr:blkptr + count], dtype=np.uint8) if count else np.zeros(1, dtype=np.uint8)
         cap = int(self.ctx.lib.kz_max_block_stream_bytes(count))
+        if self.TYPE == E_ANS1:
+            cap += 102400 * (count // (1 << 22) + 1)            # up to 256 context headers per 4 MiB chunk (include/kanzi_hip.h)
         out = np.zeros(cap, dtype=np.uint8)
         nbits = self.ctx.lib.kz_entropy_encode(self.ctx.h, self.TYPE, s.ctypes.data, count, out.ctypes.data, cap)
         self.ctx.check(nbits)
@@ -460,11 +462,25 @@ class _EntropyDecoder:
 
 
 class ANSRangeEncoder(_EntropyEncoder):
-    TYPE = E_ANS0              # K/entropy/ANSRangeEncoder.java (order 0)
+    """K/entropy/ANSRangeEncoder.java as EntropyCodecFactory builds it: order 0 is ANS0, order 1 is ANS1 (:175-179)."""
+    TYPE = E_ANS0
+
+    def __init__(self, ctx, order=0):
+        if order not in (0, 1):
+            raise ValueError("ANS Codec: The order must be 0 or 1")
+        super().__init__(ctx)
+        self.TYPE = E_ANS1 if order == 1 else E_ANS0
 
 
 class ANSRangeDecoder(_EntropyDecoder):
+    """K/entropy/ANSRangeDecoder.java: order 0 is ANS0, order 1 is ANS1 (EntropyCodecFactory.java:124-128)."""
     TYPE = E_ANS0
+
+    def __init__(self, ctx, data, nbits, order=0):
+        if order not in (0, 1):
+            raise ValueError("ANS Codec: The order must be 0 or 1")
+        super().__init__(ctx, data, nbits)
+        self.TYPE = E_ANS1 if order == 1 else E_ANS0
 
 
 class HuffmanEncoder(_EntropyEncoder):

@@ -296,7 +296,7 @@ __global__ __launch_bounds__(64) void k_ans_enc_chunk(const u8* __restrict__ src
 __global__ __launch_bounds__(64) void k_ans_enc_scan(const int32_t* __restrict__ d_len, AnsEnc E, int64_t* __restrict__ d_bits, int rawLimit) {
   const int b = blockIdx.x;
   const int count = d_len[b];
-  const int chunks = (count <= rawLimit) ? (count > 0 ? 1 : 0) : (count + ANS_CHUNK - 1) / ANS_CHUNK;
+  const int chunks = (count <= rawLimit) ? (count > 0 ? 1 : 0) : (count + E.chunk - 1) / E.chunk;
   const int lane = kz_lane();
   u64 carry = 0;
   for (int base = 0; base < chunks; base += 64) {
@@ -336,18 +336,19 @@ __global__ __launch_bounds__(KZ_WG) void k_ans_enc_concat(const int32_t* __restr
                                                            int64_t outStride, const int32_t* __restrict__ d_hdrBytes, int rawLimit) {
   const int b = blockIdx.y, ck = blockIdx.x;
   const int count = d_len[b];
-  const int chunks = (count <= rawLimit) ? (count > 0 ? 1 : 0) : (count + ANS_CHUNK - 1) / ANS_CHUNK;
+  const int chunks = (count <= rawLimit) ? (count > 0 ? 1 : 0) : (count + E.chunk - 1) / E.chunk;
   if (ck >= chunks) return;
   const int64_t ci = (int64_t)b * E.C + ck;
-  const u8* hdr = E.hdr + ci * ANS_HDR_BYTES;
+  const u8* hdr = E.hdr + ci * E.hdrStride;
   const int64_t hb = E.hdrBits[ci];
   const int64_t tb = (int64_t)E.tailBits[ci];
-  const u8* tail = E.scr + ci * ANS_SCRATCH + E.tailOff[ci];
+  const u8* tail = E.scr + ci * E.scrStride + E.tailOff[ci];
   const int64_t len = hb + tb;
   if (len == 0) return;
   const int64_t base = 8LL * d_hdrBytes[b] + (int64_t)E.bitOff[ci];
   u32* o = (u32*)(out + (int64_t)b * outStride);
-  const int64_t w0 = base >> 5, w1 = (base + len - 1) >> 5;
+  const int64_t wEnd = (base + len - 1) >> 5, wCap = (E.outCap >> 2) - 1;     // ANS1's headers may exceed a slot: the block then goes raw
+  const int64_t w0 = base >> 5, w1 = wEnd < wCap ? wEnd : wCap;
   for (int64_t w = w0 + threadIdx.x; w <= w1; w += KZ_WG) {
     const int64_t r = w * 32 - base;                       // chunk-relative bit of this word's first bit
     u32 v = kz_fetch32(hdr, hb, r) | kz_fetch32(tail, tb, r - hb);

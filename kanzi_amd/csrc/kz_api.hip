@@ -297,7 +297,10 @@ static int split_types(uint64_t tt, int* types) {                    // Transfor
   return k;
 }
 static bool transform_supported(int t) { return t == KZ_T_NONE || t == KZ_T_TEXT || t == KZ_T_UTF || t == KZ_T_BWT || t == KZ_T_RANK || t == KZ_T_MTFT || t == KZ_T_ZRLT || t == KZ_T_SRT || t == KZ_T_LZ || t == KZ_T_LZX || t == KZ_T_MM || t == KZ_T_PACK || t == KZ_T_DNA; }
-static bool entropy_supported(int e) { return e == KZ_E_NONE || e == KZ_E_ANS0 || e == KZ_E_HUFFMAN || e == KZ_E_FPAQ; }
+static bool entropy_supported(int e) { return e == KZ_E_NONE || e == KZ_E_ANS0 || e == KZ_E_ANS1 || e == KZ_E_HUFFMAN || e == KZ_E_FPAQ; }
+// TEXT is TextCodec2 under NONE / ANS0 / HUFFMAN / RANGE and TextCodec1 under every other coder (TransformFactory.java:275-286)
+static bool text_codec1(int e) { return !(e == KZ_E_NONE || e == KZ_E_ANS0 || e == KZ_E_HUFFMAN || e == 4 /* RANGE */); }
+int64_t kz_ans1_max_stream_bytes(int n) { return (int64_t)kz_align((size_t)n + (size_t)(n >> 3) + 1024 + 102400 * ((size_t)n / (1 << 22) + 1), 256); }
 static int seq_max_len(const int* types, int nb, int n) {             // Sequence.java:215-226
   int req = n;
   for (int i = 0; i < nb; i++) req = std::max(req, kz_transform_max_encoded_len((uint32_t)types[i], req));
@@ -521,6 +524,8 @@ static size_t pipeline_scratch(int B, int maxLen, bool decode, const ChainSpec& 
   }
   if (C.entropy == KZ_E_ANS0 || C.entropy == KZ_E_HUFFMAN)
     s += decode ? (size_t)B * ((size_t)(maxLen / 16384 + 4) * 8 + 64) + 65536 : kz_ans_scratch(B, maxLen);
+  else if (C.entropy == KZ_E_ANS1)
+    s += kz_ans1_scratch(B, maxLen, decode);
   else if (C.entropy == KZ_E_FPAQ)
     s += decode ? 4096 : kz_fpaq_scratch(B, maxLen);
   return s;
@@ -831,12 +836,12 @@ __global__ void k_gather_group(const int32_t* __restrict__ in, const int32_t* __
 // form is one serial walk per block: 1.07 s for 1 536 text blocks of 4 MiB side by side -- and as long for 384 of them -- where 16
 // host CPUs need 0.87 s under the GPU's next chunk; it pays only where the host has next to no CPUs for the process.
 // TEXT inverse on the device (kz_text_gpu.hip).  KZ_TEXT_GPU: unset = the row form (three waves per block) for streams whose entropy
-// coder selects TextCodec2 (every coder but FPAQ / the CM family, TextCodec.java:73-88) in batches of KZ_TEXT_GPU_MIN blocks or more
+// coder selects TextCodec2 (NONE / ANS0 / HUFFMAN / RANGE, TransformFactory.java:275-286) in batches of KZ_TEXT_GPU_MIN blocks or more
 // (512: a block takes the kernel ~0.1 s however few there are, the host stage ~10 ms per block and thread), else the host stage;
 // 0 = host stage only; 1 = row form, three waves; 2 = serial token walk (both codecs); 3 = row form, one wave (1-3: any batch).
 static int text_gpu_form(const kz_ctx* ctx, uint32_t entropyType, int nBlocks) {
   if (ctx->sw.textGpu >= 0) return ctx->sw.textGpu;
-  return (entropyType == KZ_E_FPAQ || nBlocks < ctx->sw.textGpuMin) ? 0 : 1;
+  return (text_codec1((int)entropyType) || nBlocks < ctx->sw.textGpuMin) ? 0 : 1;
 }
 static bool text_gpu_on(const kz_ctx* ctx, uint32_t entropyType, int nBlocks) { return text_gpu_form(ctx, entropyType, nBlocks) != 0; }
 // TEXT forward on the device (kz_text_fwd_gpu.hip): TextCodec2 streams (every entropy coder but FPAQ) in batches of KZ_TEXT_FWD_GPU_MIN
@@ -1475,7 +1480,7 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
     hipEvent_t e0; kz_stage_begin(ctx, &e0);
     int64_t inBytes = 0; for (int b = 0; b < B; b++) inBytes += bt.h_len[b];
     // copy blocks and NONE entropy: raw bytes (NullEntropyEncoder.java:66-81)
-    if (entropyType == KZ_E_ANS0 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_FPAQ) {
+    if (entropyType == KZ_E_ANS0 || entropyType == KZ_E_ANS1 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_FPAQ) {
       // small copy blocks use NONE: mask them out of the ANS stage by zero length, then copy raw
       for (int b = 0; b < B; b++) h_mask[b] = h_copy[b] ? 0 : 1;
       KZ_HIP(hipMemcpyAsync(P.d_mask, h_mask.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
@@ -1484,6 +1489,7 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
       std::vector<int32_t> saved = bt.h_len;
       for (int b = 0; b < B; b++) if (h_copy[b]) bt.h_len[b] = 0;
       rc = (entropyType == KZ_E_ANS0) ? kz_stage_ans0_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
+         : (entropyType == KZ_E_ANS1) ? kz_stage_ans1_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
          : (entropyType == KZ_E_HUFFMAN) ? kz_stage_huffman_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
                                          : kz_stage_fpaq_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits);
       if (rc) return rc;
@@ -1724,10 +1730,11 @@ static int32_t decode_blocks_impl(kz_ctx* ctx, uint64_t transformType, uint32_t 
       if (in) outBytes += bt.h_len[b];
       h_rawp[b] = (in && (entropyType == KZ_E_NONE || h_raw[b] || h_tc[b])) ? 1 : 0;
     }
-    if (entropyType == KZ_E_ANS0 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_FPAQ) {
+    if (entropyType == KZ_E_ANS0 || entropyType == KZ_E_ANS1 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_FPAQ) {
       for (int b = 0; b < B; b++) h_mask[b] = ((!part || (*part)[b]) && !(h_raw[b] || h_tc[b])) ? 1 : 0;
       int r = run_stage(ctx, P, h_mask, h_applied, [&](kz_batch& x) {
         return (entropyType == KZ_E_ANS0) ? kz_stage_ans0_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
+             : (entropyType == KZ_E_ANS1) ? kz_stage_ans1_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
              : (entropyType == KZ_E_HUFFMAN) ? kz_stage_huffman_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
                                              : kz_stage_fpaq_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd); }, d_part);
       if (r) return r;
@@ -1857,7 +1864,7 @@ static int32_t decode_blocks_impl(kz_ctx* ctx, uint64_t transformType, uint32_t 
       take[b] = t ? 1 : 0;
     }
     hipEvent_t e0; kz_stage_begin(ctx, &e0);
-    rc = kz_stage_text_inverse_gpu(ctx, bt, blockSize, dataCap, entropyType == KZ_E_FPAQ, take, done, text_gpu_form(ctx, (uint32_t)entropyType, B));
+    rc = kz_stage_text_inverse_gpu(ctx, bt, blockSize, dataCap, text_codec1(entropyType), take, done, text_gpu_form(ctx, (uint32_t)entropyType, B));
     if (rc) return rc;
     kz_stage_end(ctx, e0, KZ_STAGE_HOST_INV, 0);
     for (int b = 0; b < B; b++) if (done[b]) h_skipHost[b] |= 0x80;
@@ -2123,7 +2130,7 @@ extern "C" int64_t kz_entropy_encode(kz_ctx* ctx, uint32_t type, const uint8_t* 
   }
   KZ_HIP(hipSetDevice(ctx->device));
   Pipe P;
-  const int64_t oS = kz_max_block_stream_bytes(n);
+  const int64_t oS = (type == KZ_E_ANS1) ? kz_ans1_max_stream_bytes(n) : kz_max_block_stream_bytes(n);
   ChainSpec CS; CS.nb = 0; CS.entropy = (int)type;
   int rc = pipe_setup(ctx, P, 1, n, oS + 256, false, CS);
   if (rc) return rc;
@@ -2139,8 +2146,8 @@ extern "C" int64_t kz_entropy_encode(kz_ctx* ctx, uint32_t type, const uint8_t* 
   KZ_HIP(hipMemsetAsync(d_out, 0, (size_t)oS, st));
   KZ_HIP(hipMemsetAsync(d_hdr, 0, 64, st));
   int64_t bits = 0;
-  if (type == KZ_E_ANS0 || type == KZ_E_HUFFMAN || type == KZ_E_FPAQ) {
-    rc = (type == KZ_E_ANS0) ? kz_stage_ans0_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_HUFFMAN) ? kz_stage_huffman_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : kz_stage_fpaq_encode(ctx, bt, d_out, oS, d_hdr, d_bits);
+  if (type == KZ_E_ANS0 || type == KZ_E_ANS1 || type == KZ_E_HUFFMAN || type == KZ_E_FPAQ) {
+    rc = (type == KZ_E_ANS0) ? kz_stage_ans0_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_ANS1) ? kz_stage_ans1_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_HUFFMAN) ? kz_stage_huffman_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : kz_stage_fpaq_encode(ctx, bt, d_out, oS, d_hdr, d_bits);
     if (rc) return rc;
     KZ_HIP(hipMemcpyAsync(&bits, d_bits, 8, hipMemcpyDeviceToHost, st));
     KZ_HIP(kz_stream_sync(ctx, st));
@@ -2178,9 +2185,9 @@ extern "C" int32_t kz_entropy_decode(kz_ctx* ctx, uint32_t type, const uint8_t* 
   KZ_HIP(hipMemcpyAsync(d_off, h, 16, hipMemcpyHostToDevice, st));
   bt.h_len[0] = count;
   KZ_HIP(hipMemcpyAsync(bt.d_len, &count, 4, hipMemcpyHostToDevice, st));
-  if (type == KZ_E_ANS0 || type == KZ_E_HUFFMAN || type == KZ_E_FPAQ) {
+  if (type == KZ_E_ANS0 || type == KZ_E_ANS1 || type == KZ_E_HUFFMAN || type == KZ_E_FPAQ) {
     ctx->d_endBits = (long long*)(d_off + 2);
-    rc = (type == KZ_E_ANS0) ? kz_stage_ans0_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_HUFFMAN) ? kz_stage_huffman_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : kz_stage_fpaq_decode(ctx, bt, d_in, inS, d_off, d_off + 1);
+    rc = (type == KZ_E_ANS0) ? kz_stage_ans0_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_ANS1) ? kz_stage_ans1_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_HUFFMAN) ? kz_stage_huffman_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : kz_stage_fpaq_decode(ctx, bt, d_in, inS, d_off, d_off + 1);
     ctx->d_endBits = nullptr;
     if (rc) return rc;
     int32_t flag = 0;

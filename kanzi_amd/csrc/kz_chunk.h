@@ -17,6 +17,10 @@ struct AnsEnc {
   u32* tailBits;    // [B][C]
   u64* bitOff;      // [B][C] exclusive scan of chunk bit lengths
   int C;            // chunk stride per block
+  int chunk = ANS_CHUNK;                   // bytes per chunk (ANS1: 4 MiB)
+  int64_t hdrStride = ANS_HDR_BYTES;       // bytes between the chunks' header buffers
+  int64_t scrStride = ANS_SCRATCH;         // bytes between the chunks' payload buffers
+  int64_t outCap = INT64_MAX;              // bytes of a block's output slot the concatenation may write (the bit count is not clipped)
 };
 
 int kz_chunk_enc_alloc(kz_ctx* ctx, kz_batch& bt, AnsEnc& E, int* chunksOut);
