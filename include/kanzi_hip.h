@@ -167,6 +167,20 @@ typedef struct {
  * `lengths` and `results` are host arrays.  memKind says where in/out live (KZ_MEM_HOST: pageable or
  * pinned host memory, copied over PCIe inside the call; KZ_MEM_DEVICE: HBM pointers, no copies).
  * transformType = 8 x 6-bit ids, first transform in the top slot (TransformFactory.java:29-31).
+ *
+ * Layout contract (maxLength = the largest lengths[b]).  A call outside it returns -KZ_ERR_INVALID_PARAM before anything is
+ * copied or launched, `out` and `results` untouched.
+ *   in         any address, any inStride >= maxLength (nBlocks > 1), both memory kinds: blocks are read bytewise.  Host memory:
+ *              exactly lengths[b] bytes of row b are read.  Device memory: row b may be read up to maxLength bytes whatever
+ *              lengths[b] is (chains led by TEXT / UTF copy whole rows back), so in[0 .. (nBlocks-1)*inStride + maxLength) must be
+ *              readable; what lies behind lengths[b] never reaches the stream.
+ *   out        outStride >= kz_max_block_stream_bytes(maxLength) and a multiple of 4, both memory kinds.  Device memory: `out` itself
+ *              4-byte aligned as well (the coders OR 32-bit words into it in place); host memory: any address.
+ *   written    nothing outside out[0 .. nBlocks*outStride).  Row b holds the stream in its first (results[b].bits + 7) / 8 bytes,
+ *              the spare bits of the last byte zero.  The rest of the row is unspecified: device rows are zeroed and used as
+ *              working space, host rows are left as they were behind the stream.
+ * nBlocks <= 0 returns 0 and touches nothing.  Batches of more blocks than one launch takes (65 535, or fewer when the scratch
+ * arena says so) are coded as consecutive sub-batches; the results are those of the blocks coded one by one.
  */
 int32_t kz_encode_blocks(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType,
                          const uint8_t* in, int64_t inStride, const int32_t* lengths, int32_t nBlocks,
@@ -174,7 +188,22 @@ int32_t kz_encode_blocks(kz_ctx* ctx, uint64_t transformType, uint32_t entropyTy
 /*
  * Decode nBlocks block streams.  Stream b is in[b*inStride ..] with bitLengths[b] bits (W, header
  * included).  Decoded bytes go to out[b*outStride ..] (capacity outStride each, >= blockSize).
+ *
+ * Layout contract (maxBytes = the largest (bitLengths[b] + 7) / 8).  A call outside it returns -KZ_ERR_INVALID_PARAM before
+ * anything is copied or launched, `out` and `results` untouched.
+ *   in         any address, both memory kinds: streams are read bytewise or through unaligned loads.  Host memory: inStride >=
+ *              maxBytes (nBlocks > 1); exactly (bitLengths[b] + 7) / 8 bytes of slot b are read.  Device memory: inStride >=
+ *              maxBytes + KZ_STREAM_SLACK; slot b is read in place, only inside [b*inStride, (b+1)*inStride) and no further than
+ *              KZ_STREAM_SLACK bytes behind (bitLengths[b] + 7) / 8 (the decoders load a few bytes ahead of the bit they are at).
+ *   no effect  of the spare bits of a stream's last byte, nor of any byte behind it, on status, length or decoded bytes: a block's
+ *              result is a function of its bitLengths[b] bits alone (as in the reference, whose bit stream ends there).
+ *   out        any address, any outStride >= 0, both memory kinds.  A block that decodes to more than min(outStride, blockSize)
+ *              bytes fails with -KZ_ERR_PROCESS_BLOCK.
+ *   written    nothing outside out[0 .. nBlocks*outStride); row b holds results[b].length bytes (0 for a failed block), the rest
+ *              of the row is unspecified (chains led by TEXT / UTF undo those stages inside the row).
+ * nBlocks <= 0 returns 0 and touches nothing.  Larger batches than one launch takes are split like kz_encode_blocks's.
  */
+#define KZ_STREAM_SLACK 64
 int32_t kz_decode_blocks(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int32_t blockSize,
                          const uint8_t* in, int64_t inStride, const int64_t* bitLengths, int32_t nBlocks,
                          uint8_t* out, int64_t outStride, kz_block_result* results, int32_t memKind);

@@ -446,6 +446,9 @@ __global__ void k_ans_dec_index(const u8* __restrict__ in, int64_t inStride, con
       else {
         const int lastMask = (int)kz_peek(p, pos + 1, 5); pos += 6;
         asz = 0;
+        // (a header that runs past the block's bits fails this chunk either way: stop reading there, the slot behind the stream
+        // is not ours beyond KZ_STREAM_SLACK)
+        if (pos + 8ULL * (u64)(lastMask + 1) > endBits) { event = c * 4 + ANS_EV_FAIL; break; }
         for (int i = 0; i <= lastMask; i++) { asz += __popc(kz_peek(p, pos, 8)); pos += 8; }
       }
       if (asz == 0) { event = c * 4 + ANS_EV_FAIL; break; }          // ANSRangeDecoder.java:214-215 returns startChunk != count
@@ -453,7 +456,7 @@ __global__ void k_ans_dec_index(const u8* __restrict__ in, int64_t inStride, con
         const int chkSize = (asz >= 64) ? 8 : 6;
         int llr = 3;
         while ((1 << llr) <= lr) llr++;
-        for (int i = 1; i < asz; i += chkSize) {
+        for (int i = 1; i < asz && pos <= endBits; i += chkSize) {
           const int logMax = (int)kz_peek(p, pos, llr); pos += llr;
           const int endj = (i + chkSize < asz) ? i + chkSize : asz;
           pos += (u64)logMax * (u64)(endj - i);
@@ -474,6 +477,7 @@ __global__ void k_ans_dec_index(const u8* __restrict__ in, int64_t inStride, con
       pos += 128 + 8ULL * sz;
       if (pos > endBits) { nIdx = c; event = c * 4 + ANS_EV_FAIL; break; }
     }
+    if (event == ANS_EV_NONE) D.chunkBit[(int64_t)b * D.C + chunks] = pos;    // end of the last chunk (D.C = chunks of the longest block + 1)
   } else {                                                          // :193-196 bulk read of the raw bytes: past the block's bits it throws
     pos += 8ULL * (u64)(count > 0 ? count : 0);
     if (pos > endBits) event = ANS_EV_FAIL;                          // (chunk 0)
@@ -668,12 +672,15 @@ __global__ __launch_bounds__(64) void k_ans_dec_chunk(const u8* __restrict__ in,
 
 // one wave per block: verdict of the lowest-chunk event, zero fill of what the reference leaves unwritten
 __global__ __launch_bounds__(64) void k_ans_dec_fin(const int32_t* __restrict__ d_len, int32_t* __restrict__ d_len2, int32_t* __restrict__ d_flag,
-                                                     AnsDec D, u8* __restrict__ dst, int64_t stride) {
+                                                     AnsDec D, u8* __restrict__ dst, int64_t stride, long long* __restrict__ endOut) {
   const int b = blockIdx.x, lane = kz_lane();
   const int count = d_len[b];
   const int ev = D.event[b];
   if (lane == 0) { d_len2[b] = count; d_flag[b] = (ev == ANS_EV_NONE || (ev & 3) != ANS_EV_FAIL) ? 1 : 0; }
   if (ev == ANS_EV_NONE || (ev & 3) == ANS_EV_FAIL) return;
+  // the reference stops reading behind the payload of the chunk that ended the decode (:439): the bits consumed are that
+  // position, not the end of the chunks the index pass walked (ANS_EV_SKIP: the index pass stopped there itself)
+  if (endOut && lane == 0 && (ev & 3) == ANS_EV_STOP) endOut[b] = (long long)D.chunkBit[(int64_t)b * D.C + (ev >> 2) + 1];
   const int64_t from = (int64_t)((ev >> 2) + ((ev & 3) == ANS_EV_STOP ? 1 : 0)) * ANS_CHUNK;
   u8* o = dst + (int64_t)b * stride;
   for (int64_t i = from + lane; i < count; i += 64) o[i] = 0;
@@ -695,7 +702,7 @@ int kz_stage_ans0_decode(kz_ctx* ctx, kz_batch& bt, const uint8_t* in, int64_t i
   KZ_LAUNCH(ctx, KID_ANS_DEC_INDEX, k_ans_dec_index, dim3((B + 63) / 64), dim3(64), in, inStride, d_bitOff, d_bitEnd, bt.d_len, D, B, ctx->d_endBits);
   const int chunks = (maxN + ANS_CHUNK - 1) / ANS_CHUNK;
   if (chunks > 0) KZ_LAUNCH(ctx, KID_ANS_DEC_CHUNK, k_ans_dec_chunk, dim3(chunks, B), dim3(64), in, inStride, d_bitOff, bt.d_len, D, dst, bt.stride);
-  KZ_LAUNCH(ctx, KID_ANS_DEC_FIN, k_ans_dec_fin, dim3(B), dim3(64), bt.d_len, bt.d_len2, bt.d_flag, D, dst, bt.stride);
+  KZ_LAUNCH(ctx, KID_ANS_DEC_FIN, k_ans_dec_fin, dim3(B), dim3(64), bt.d_len, bt.d_len2, bt.d_flag, D, dst, bt.stride, ctx->d_endBits);
   KZ_HIP(hipGetLastError());
   bt.cur ^= 1;
   { int32_t* t = bt.d_len; bt.d_len = bt.d_len2; bt.d_len2 = t; }

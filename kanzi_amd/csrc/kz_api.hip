@@ -1195,6 +1195,16 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
   if (hp < 0) return hp;
   int maxN = 0;
   for (int b = 0; b < B; b++) { if (lengths[b] < 0) return -KZ_ERR_INVALID_PARAM; maxN = std::max(maxN, lengths[b]); }
+  // ---- the layout contract of include/kanzi_hip.h, checked on the WHOLE batch before anything is copied or launched (a batch
+  //      that is split below would otherwise code its first part before a later part is refused) ----
+  {
+    const int64_t needOut = kz_max_block_stream_bytes(maxN);
+    if ((!in && maxN > 0) || !out || !results) { snprintf(ctx->err, sizeof(ctx->err), "encode: null pointer"); return -KZ_ERR_INVALID_PARAM; }
+    if (outStride < needOut || (outStride & 3)) { snprintf(ctx->err, sizeof(ctx->err), "outStride %lld < %lld or not a multiple of 4", (long long)outStride, (long long)needOut); return -KZ_ERR_INVALID_PARAM; }
+    // device output is written in place with 32-bit read-modify-write words (the bit concatenation of the entropy coders)
+    if (memKind == KZ_MEM_DEVICE && ((uintptr_t)out & 3)) { snprintf(ctx->err, sizeof(ctx->err), "device out %p is not 4-byte aligned", (void*)out); return -KZ_ERR_INVALID_PARAM; }
+    if (B > 1 && inStride < (int64_t)maxN) { snprintf(ctx->err, sizeof(ctx->err), "inStride %lld < longest block %d", (long long)inStride, maxN); return -KZ_ERR_INVALID_PARAM; }
+  }
   const int maxLen = seq_max_len(types, nb, maxN);
   // blocks go up to the reference's 1 GiB (BWT.java:59); BWT / RANK / MTFT blocks of 2^24 bytes and more take the wide forms of the
   // inverse kernels (8-byte links in kz_bwt_inv.hip, the plain list in kz_sbrt.hip: round 5), slower but the same bytes
@@ -1923,6 +1933,21 @@ extern "C" int32_t kz_decode_blocks(kz_ctx* ctx, uint64_t transformType, uint32_
                                     const uint8_t* in, int64_t inStride, const int64_t* bitLengths, int32_t nBlocks,
                                     uint8_t* out, int64_t outStride, kz_block_result* results, int32_t memKind) {
   if (!ctx) return -KZ_ERR_INVALID_PARAM;
+  if (nBlocks <= 0) return 0;
+  // ---- the layout contract of include/kanzi_hip.h, checked on the whole batch before anything is copied or launched: a device
+  //      slot is read in place, a few bytes ahead of the bit the decoder is at, so it carries KZ_STREAM_SLACK bytes behind its
+  //      stream; a host stream is copied ((bits + 7) / 8 bytes) into a slot of the library's own ----
+  {
+    if (!in || !out || !bitLengths || !results) { snprintf(ctx->err, sizeof(ctx->err), "decode: null pointer"); return -KZ_ERR_INVALID_PARAM; }
+    int64_t maxInBytes = 0;
+    for (int b = 0; b < nBlocks; b++) {
+      if (bitLengths[b] < 0) { snprintf(ctx->err, sizeof(ctx->err), "bitLengths[%d] < 0", b); return -KZ_ERR_INVALID_PARAM; }
+      maxInBytes = std::max(maxInBytes, (bitLengths[b] + 7) >> 3);
+    }
+    const int64_t needIn = maxInBytes + (memKind == KZ_MEM_DEVICE ? KZ_STREAM_SLACK : 0);
+    if (inStride < needIn && (memKind == KZ_MEM_DEVICE || nBlocks > 1)) { snprintf(ctx->err, sizeof(ctx->err), "inStride %lld < %lld (longest stream%s)", (long long)inStride, (long long)needIn, memKind == KZ_MEM_DEVICE ? " + KZ_STREAM_SLACK" : ""); return -KZ_ERR_INVALID_PARAM; }
+    if (outStride < 0) { snprintf(ctx->err, sizeof(ctx->err), "outStride %lld < 0", (long long)outStride); return -KZ_ERR_INVALID_PARAM; }
+  }
   int types[8];
   const int nb = split_types(transformType, types);
   int hp = 0;

@@ -25,6 +25,7 @@ def _fwd(ctx, tid, data, cap=None):
     a = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)
     rc = ctx.lib.kz_transform_forward(ctx.h, tid, a.ctypes.data, len(data), out.ctypes.data, cap, ctypes.addressof(p))
     assert rc >= 0, ctx.error()
+    assert not out[cap:].any(), "kz_transform_forward wrote behind dstCap"
     return rc == 1, out[:p.value].tobytes()
 
 
@@ -34,6 +35,7 @@ def _inv(ctx, tid, data, cap):
     a = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)
     rc = ctx.lib.kz_transform_inverse(ctx.h, tid, a.ctypes.data, len(data), out.ctypes.data, cap, ctypes.addressof(p))
     assert rc >= 0, ctx.error()
+    assert not out[cap:].any(), "kz_transform_inverse wrote behind dstCap"
     return rc == 1, out[:p.value].tobytes()
 
 
