@@ -7,10 +7,23 @@
  *   kz_transform_forward / _inverse / _max_encoded_len
  *       K/ByteTransform.java:36,48,56  (boolean forward(SliceByteArray,SliceByteArray), inverse, getMaxEncodedLength)
  *       for the codecs K/transform/BWTBlockCodec.java:71-213, K/transform/SBRT.java:87-214 (RANK, MTFT),
- *       K/transform/ZRLT.java:54-233, K/transform/SRT.java:66-257, K/transform/LZCodec.java:299-756 (LZ, LZX),
+ *       K/transform/ZRLT.java:54-233, K/transform/RLT.java:69-410, K/transform/SRT.java:66-257, K/transform/LZCodec.java:299-756 (LZ, LZX),
  *       K/transform/FSDCodec.java:60-323 (MM), K/transform/AliasCodec.java:76-475 (PACK, DNA), and, as host (CPU) stages in front of
  *       the GPU chain, K/transform/TextCodec.java:482-531 (TEXT) and K/transform/UTFCodec.java:68-305 (UTF).
  *       "false" is a normal outcome (Sequence.java:95-105) -> return 0.
+ *       RLT is built with the context map, as TransformFactory does (new RLT(ctx)): its forward reads the entries "entropy"
+ *       (kz_ctx_set_entropy: the escape symbol is searched and the block's data type looked at under every coder but NONE / ANS0 /
+ *       HUFFMAN / RANGE, RLT.java:101-132) and "dataType" (kz_ctx_set_data_type; DNA / BASE64 / UTF8 decline, a detected type is
+ *       stored back: kz_ctx_get_data_type).  It bounds its output by dst.length, the length of the output ARRAY (RLT.java:115):
+ *         kz_transform_forward   dst.length = dstCap (a binding passes the array's length behind dst.index, not the slice's);
+ *         batched / stream calls dst.length = what the reference's writer with one job and equal block sizes gives the stage.
+ *                                Sequence.forward swaps its two buffers after every stage that was APPLIED (Sequence.java:107-114).
+ *                                After an even number of applied stages (host stages TEXT / UTF included) RLT writes into the task's
+ *                                `buffer`: Sequence.getMaxEncodedLength(blockSize) bytes (CompressedOutputStream.java:793,806-811);
+ *                                after an odd number into `data`: max(blockSize + blockSize / 8, 256 KiB) bytes (:215-216, or what
+ *                                the stage needs if that is more, Sequence.java:82-87).  blockSize = kz_ctx_set_block_size when set
+ *                                (kz_compress sets it), else the longest block of the call.
+ *       The bound only matters for a block whose coded length ends within a few bytes under its length.
  *   kz_entropy_encode / kz_entropy_decode
  *       K/EntropyEncoder.java:34 (int encode(byte[],int,int)) + dispose(), K/EntropyDecoder.java:33
  *       for K/entropy/ANSRangeEncoder.java:263-305, K/entropy/ANSRangeDecoder.java:189-236 (order 0 = ANS0 and
@@ -44,10 +57,10 @@ extern "C" {
 #define KZ_ABI_VERSION 3
 
 /* transform ids: K/transform/TransformFactory.java:36-60 */
-enum { KZ_T_NONE = 0, KZ_T_BWT = 1, KZ_T_LZ = 3, KZ_T_ZRLT = 6, KZ_T_MTFT = 7, KZ_T_RANK = 8, KZ_T_TEXT = 10 /* DICT_TYPE */,
+enum { KZ_T_NONE = 0, KZ_T_BWT = 1, KZ_T_LZ = 3, KZ_T_RLT = 5, KZ_T_ZRLT = 6, KZ_T_MTFT = 7, KZ_T_RANK = 8, KZ_T_TEXT = 10 /* DICT_TYPE */,
        KZ_T_SRT = 13, KZ_T_MM = 15, KZ_T_LZX = 16, KZ_T_UTF = 17, KZ_T_PACK = 18, KZ_T_DNA = 19 };
-/* Global.DataType (K/Global.java:40-80): the per-block context entry "dataType" that MM (FSDCodec.java:78-85,160-168)
-   and LZ/LZX (LZCodec.java:343-352) read and write.  The KZ_DT_* VALUES ARE THIS LIBRARY'S OWN and are NOT the Java enum's
+/* Global.DataType (K/Global.java:40-80): the per-block context entry "dataType" that MM (FSDCodec.java:78-85,160-168),
+   LZ/LZX (LZCodec.java:343-352) and RLT (RLT.java:95-132) read and write.  The KZ_DT_* VALUES ARE THIS LIBRARY'S OWN and are NOT the Java enum's
    ordinals (Java order: UNDEFINED, TEXT, MULTIMEDIA, EXE, NUMERIC, BASE64, DNA, BIN, UTF8, SMALL_ALPHABET); the value never
    reaches the stream, and a binding maps by NAME (integration/java/HipByteTransform.java). */
 enum { KZ_DT_UNDEFINED = 0, KZ_DT_DNA = 1, KZ_DT_SMALL_ALPHABET = 2, KZ_DT_TEXT = 3, KZ_DT_MULTIMEDIA = 4, KZ_DT_EXE = 5,

@@ -27,9 +27,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libkanzi_hip.so")
 
 # transform ids (K/transform/TransformFactory.java:36-60) and entropy ids (K/entropy/EntropyCodecFactory.java)
-NONE_TYPE, BWT_TYPE, LZ_TYPE, ZRLT_TYPE, MTFT_TYPE, RANK_TYPE, SRT_TYPE, MM_TYPE, LZX_TYPE, PACK_TYPE, DNA_TYPE = 0, 1, 3, 6, 7, 8, 13, 15, 16, 18, 19
+NONE_TYPE, BWT_TYPE, LZ_TYPE, RLT_TYPE, ZRLT_TYPE, MTFT_TYPE, RANK_TYPE, SRT_TYPE, MM_TYPE, LZX_TYPE, PACK_TYPE, DNA_TYPE = 0, 1, 3, 5, 6, 7, 8, 13, 15, 16, 18, 19
 E_NONE, E_HUFFMAN, E_FPAQ, E_ANS0, E_ANS1 = 0, 1, 2, 5, 8
-TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "LZ": 3, "ZRLT": 6, "MTFT": 7, "RANK": 8, "TEXT": 10, "SRT": 13, "MM": 15, "LZX": 16, "UTF": 17, "PACK": 18, "DNA": 19}
+TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "TEXT": 10, "SRT": 13, "MM": 15, "LZX": 16, "UTF": 17, "PACK": 18, "DNA": 19}
 TEXT_TYPE, UTF_TYPE = 10, 17
 # Global.DataType (K/Global.java:40-80), numbered as KZ_DT_* in include/kanzi_hip.h
 DATA_TYPES = {"UNDEFINED": 0, "DNA": 1, "SMALL_ALPHABET": 2, "TEXT": 3, "MULTIMEDIA": 4, "EXE": 5, "NUMERIC": 6, "BASE64": 7, "BIN": 8, "UTF8": 9}
@@ -336,11 +336,12 @@ class _Transform:
     def getMaxEncodedLength(self, n):
         return int(self.ctx.lib.kz_transform_max_encoded_len(self.TYPE, n))
 
-    def _run(self, fn, src, dst):
+    def _run(self, fn, src, dst, cap=None):
         if src.length == 0:
             return True
         s = np.ascontiguousarray(src.array[src.index:src.index + src.length], dtype=np.uint8)
-        cap = len(dst.array) - dst.index if fn is self.ctx.lib.kz_transform_inverse else dst.length - dst.index
+        if cap is None:
+            cap = len(dst.array) - dst.index if fn is self.ctx.lib.kz_transform_inverse else dst.length - dst.index
         if cap <= 0:
             return False
         out = np.empty(cap, dtype=np.uint8)
@@ -382,6 +383,23 @@ class UTFCodec(_Transform):
 
 class ZRLT(_Transform):
     TYPE = ZRLT_TYPE           # K/transform/ZRLT.java
+
+
+class RLT(_Transform):
+    """K/transform/RLT.java.  Like the reference's constructor with a context map it reads the entropy coder (the escape symbol is
+    searched, and the block's data type looked at, under every coder but NONE / ANS0 / HUFFMAN / RANGE) and the context's
+    "dataType" entry (``ctx.set_data_type``), which it may rewrite.  Its forward bounds the output by the length of the output ARRAY
+    (RLT.java:115), so the whole array behind ``dst.index`` is handed down, not the slice."""
+    TYPE = RLT_TYPE
+
+    def __init__(self, ctx, entropy="NONE"):
+        super().__init__(ctx)
+        ctx.set_entropy(entropy)
+
+    def forward(self, src, dst):
+        if dst.length - dst.index < self.getMaxEncodedLength(src.length):      # RLT.java:86-87
+            return False
+        return self._run(self.ctx.lib.kz_transform_forward, src, dst, cap=len(dst.array) - dst.index)
 
 
 class SRT(_Transform):

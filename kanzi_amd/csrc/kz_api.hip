@@ -280,6 +280,7 @@ extern "C" int32_t kz_transform_max_encoded_len(uint32_t type, int32_t n) {
     case KZ_T_MM: return n + std::max(64, n >> 4);                   // FSDCodec.java:320-323
     case KZ_T_PACK: case KZ_T_DNA: return n + 1024;                  // AliasCodec.java:472-475
     case KZ_T_UTF: return n + 8192;                                  // UTFCodec.java:308-310
+    case KZ_T_RLT: return (n <= 512) ? n + 32 : n;                   // RLT.java:419-421
     default: return n;                                               // ZRLT.java:243, SBRT.java:224
   }
 }
@@ -296,7 +297,7 @@ static int split_types(uint64_t tt, int* types) {                    // Transfor
   for (int i = 0; i < nbtr; i++) { int t = (int)((tt >> (42 - 6 * i)) & 0x3F); if (t != KZ_T_NONE || i == 0) types[k++] = t; }
   return k;
 }
-static bool transform_supported(int t) { return t == KZ_T_NONE || t == KZ_T_TEXT || t == KZ_T_UTF || t == KZ_T_BWT || t == KZ_T_RANK || t == KZ_T_MTFT || t == KZ_T_ZRLT || t == KZ_T_SRT || t == KZ_T_LZ || t == KZ_T_LZX || t == KZ_T_MM || t == KZ_T_PACK || t == KZ_T_DNA; }
+static bool transform_supported(int t) { return t == KZ_T_NONE || t == KZ_T_TEXT || t == KZ_T_UTF || t == KZ_T_BWT || t == KZ_T_RANK || t == KZ_T_MTFT || t == KZ_T_ZRLT || t == KZ_T_RLT || t == KZ_T_SRT || t == KZ_T_LZ || t == KZ_T_LZX || t == KZ_T_MM || t == KZ_T_PACK || t == KZ_T_DNA; }
 static bool entropy_supported(int e) { return e == KZ_E_NONE || e == KZ_E_ANS0 || e == KZ_E_ANS1 || e == KZ_E_HUFFMAN || e == KZ_E_FPAQ; }
 // TEXT is TextCodec2 under NONE / ANS0 / HUFFMAN / RANGE and TextCodec1 under every other coder (TransformFactory.java:275-286)
 static bool text_codec1(int e) { return !(e == KZ_E_NONE || e == KZ_E_ANS0 || e == KZ_E_HUFFMAN || e == 4 /* RANGE */); }
@@ -515,6 +516,7 @@ static size_t pipeline_scratch(int B, int maxLen, bool decode, const ChainSpec& 
       case KZ_T_BWT: s += decode ? kz_bwt_inverse_scratch(B, maxLen) : kz_bwt_forward_scratch(bwt_group_blocks(B, maxLen), maxLen); break;
       case KZ_T_RANK: case KZ_T_MTFT: s += kz_sbrt_scratch(B, maxLen); break;
       case KZ_T_ZRLT: s += kz_zrlt_scratch(B, maxLen); break;
+      case KZ_T_RLT: s += kz_rlt_scratch(B, maxLen) + (size_t)B * 4 + 256; break;     // + the per-block dst.length of the batched forward
       case KZ_T_SRT: s += decode ? 4096 : kz_srt_scratch(B, maxLen); break;
       case KZ_T_LZ: case KZ_T_LZX: s += decode ? 4096 : kz_lz_scratch(B, maxLen); break;
       case KZ_T_MM: s += kz_mm_scratch(B, maxLen); break;
@@ -577,12 +579,13 @@ static int bwt_forward_grouped(kz_ctx* ctx, kz_batch& bt) {
   return 0;
 }
 
-static int run_transform_stage(kz_ctx* ctx, kz_batch& bt, int type, bool forward, int dstCap) {
+static int run_transform_stage(kz_ctx* ctx, kz_batch& bt, int type, bool forward, int dstCap, int entropy) {
   switch (type) {
     case KZ_T_BWT: return forward ? bwt_forward_grouped(ctx, bt) : kz_stage_bwt_inverse(ctx, bt);
     case KZ_T_RANK: return forward ? kz_stage_sbrt_forward(ctx, bt, 2) : kz_stage_sbrt_inverse(ctx, bt, 2);
     case KZ_T_MTFT: return forward ? kz_stage_sbrt_forward(ctx, bt, 1) : kz_stage_sbrt_inverse(ctx, bt, 1);
     case KZ_T_ZRLT: return forward ? kz_stage_zrlt_forward(ctx, bt) : kz_stage_zrlt_inverse(ctx, bt, dstCap);
+    case KZ_T_RLT: return forward ? kz_stage_rlt_forward(ctx, bt, entropy) : kz_stage_rlt_inverse(ctx, bt, dstCap);
     case KZ_T_SRT: return forward ? kz_stage_srt_forward(ctx, bt) : kz_stage_srt_inverse(ctx, bt);
     case KZ_T_LZ: return forward ? kz_stage_lz_forward(ctx, bt, 0) : kz_stage_lz_inverse(ctx, bt, 0, dstCap);
     case KZ_T_LZX: return forward ? kz_stage_lz_forward(ctx, bt, 1) : kz_stage_lz_inverse(ctx, bt, 1, dstCap);
@@ -1206,6 +1209,9 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
     if (B > 1 && inStride < (int64_t)maxN) { snprintf(ctx->err, sizeof(ctx->err), "inStride %lld < longest block %d", (long long)inStride, maxN); return -KZ_ERR_INVALID_PARAM; }
   }
   const int maxLen = seq_max_len(types, nb, maxN);
+  // RLT's dst.length rule (below) goes by the block size of the WHOLE call, also where the batch is split into sub-batches or chunks
+  struct RltBsScope { kz_ctx* c; bool own; RltBsScope(kz_ctx* c_, int v) : c(c_), own(c_->rltBlockSize == 0) { if (own) c->rltBlockSize = v; }
+                      ~RltBsScope() { if (own) c->rltBlockSize = 0; } } rltScope(ctx, std::max(1, ctx->blockSizeSet ? std::max(blockSize, maxN) : maxN));
   // blocks go up to the reference's 1 GiB (BWT.java:59); BWT / RANK / MTFT blocks of 2^24 bytes and more take the wide forms of the
   // inverse kernels (8-byte links in kz_bwt_inv.hip, the plain list in kz_sbrt.hip: round 5), slower but the same bytes
   if (maxLen > KZ_MAX_BLOCK) { snprintf(ctx->err, sizeof(ctx->err), "block of %d bytes: blocks go up to %d bytes", maxN, KZ_MAX_BLOCK - 1057); return -KZ_ERR_BLOCK_SIZE; }
@@ -1471,7 +1477,24 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
     hipEvent_t e0; kz_stage_begin(ctx, &e0);
     int64_t inBytes = 0; for (int b = 0; b < B; b++) if (h_mask[b]) inBytes += bt.h_len[b];
     const int type = types[i];
-    rc = run_stage(ctx, P, h_mask, h_applied, [&](kz_batch& x) { return run_transform_stage(ctx, x, type, true, 0); });
+    if (type == KZ_T_RLT) {
+      // RLT bounds its output by the length of the ARRAY it writes into (RLT.java:115).  In the reference's writer (one job, equal
+      // block sizes) Sequence.forward swaps its two buffers after every stage that was applied (Sequence.java:107-114): after an even
+      // number of applied stages RLT writes into the task's `buffer`, grown to Sequence.getMaxEncodedLength(blockSize)
+      // (CompressedOutputStream.java:793,806-811), after an odd number into `data`, max(blockSize + blockSize / 8, 256 KiB) bytes
+      // (:215-216) unless the stage needs more (Sequence.java:82-87).  blockSize: the context's when set, else the longest block.
+      const int bs = ctx->rltBlockSize;
+      const int evenLen = seq_max_len(types, nb, bs);
+      const int oddLen = std::max(std::max(bs + (bs >> 3), 256 * 1024), evenLen);
+      std::vector<int32_t> h_end(B);
+      for (int b = 0; b < B; b++) h_end[b] = (__builtin_popcount(~h_skip[b] & 0xFF & ~((1 << (8 - i)) - 1)) & 1) ? oddLen : evenLen;
+      int32_t* d_end = (int32_t*)kz_arena_alloc(ctx, (size_t)B * 4);
+      if (!d_end) { snprintf(ctx->err, sizeof(ctx->err), "encode: arena overflow"); return -KZ_ERR_DEVICE; }
+      KZ_HIP(hipMemcpyAsync(d_end, h_end.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+      KZ_HIP(kz_stream_sync(ctx, st));                                 // h_end is a local
+      bt.d_rltEnd = d_end;
+    }
+    rc = run_stage(ctx, P, h_mask, h_applied, [&](kz_batch& x) { return run_transform_stage(ctx, x, type, true, 0, (int)entropyType); });
     if (rc) return rc;
     kz_stage_end(ctx, e0, stage_id(type, true), inBytes);
     for (int b = 0; b < B; b++) {
@@ -1768,7 +1791,7 @@ static int32_t decode_blocks_impl(kz_ctx* ctx, uint64_t transformType, uint32_t 
     }
     if (!any && !part) return 0;
     hipEvent_t e1; kz_stage_begin(ctx, &e1);
-    int r = run_stage(ctx, P, h_mask, h_applied, [&](kz_batch& x) { return run_transform_stage(ctx, x, type, false, dataCap); }, d_part);
+    int r = run_stage(ctx, P, h_mask, h_applied, [&](kz_batch& x) { return run_transform_stage(ctx, x, type, false, dataCap, (int)entropyType); }, d_part);
     if (r) return r;
     int64_t outBytes = 0; for (int b = 0; b < B; b++) if (h_mask[b]) outBytes += bt.h_len[b];
     kz_stage_end(ctx, e1, stage_id(type, false), outBytes);
@@ -2114,11 +2137,12 @@ static int32_t transform_one(kz_ctx* ctx, uint32_t type, bool forward, const uin
   KZ_HIP(hipMemcpyAsync(bt.buf[0], src, (size_t)n, hipMemcpyHostToDevice, st));
   bt.h_len[0] = n;
   KZ_HIP(hipMemcpyAsync(bt.d_len, &n, 4, hipMemcpyHostToDevice, st));
-  // the instance's context entry "dataType" (kz_ctx_set_data_type): read by MM and LZ/LZX forward, rewritten by MM
+  bt.rltEndAll = dstCap;                                            // RLT forward: dst.length (the Java adapter passes the array's length)
+  // the instance's context entry "dataType" (kz_ctx_set_data_type): read by MM, LZ/LZX and RLT forward, rewritten by MM and RLT
   rc = kz_block_data_types(ctx, bt, ctx->dataType, false);
   if (rc) return rc;
   std::vector<int32_t> mask(1, 1), applied;
-  rc = run_stage(ctx, P, mask, applied, [&](kz_batch& x) { return run_transform_stage(ctx, x, (int)type, forward, dstCap); });
+  rc = run_stage(ctx, P, mask, applied, [&](kz_batch& x) { return run_transform_stage(ctx, x, (int)type, forward, dstCap, ctx->entropy); });
   if (rc) return rc;
   if (forward) {
     int32_t dt = 0;
