@@ -30,6 +30,7 @@
  *       order 1 = ANS1, K/entropy/EntropyCodecFactory.java:124-128,175-179),
  *       K/entropy/HuffmanEncoder.java:380-416, K/entropy/HuffmanDecoder.java:353-390,
  *       K/entropy/FPAQEncoder.java:128-238, K/entropy/FPAQDecoder.java:161-335,
+ *       K/entropy/RangeEncoder.java:244-316, K/entropy/RangeDecoder.java:161-327,
  *       K/entropy/NullEntropyEncoder.java:66-81.  The codec's output is a bit string (MSB first,
  *       K/bitstream/DefaultOutputBitStream.java:103-123): the Java adapter calls
  *       obs.writeBits(out, 0, nbits) once.
@@ -68,7 +69,13 @@ enum { KZ_DT_UNDEFINED = 0, KZ_DT_DNA = 1, KZ_DT_SMALL_ALPHABET = 2, KZ_DT_TEXT 
 /* entropy ids: K/entropy/EntropyCodecFactory.java (ANS1_TYPE = 8: order-1 ANS, 4 MiB chunks).  An ANS1 stream carries up to 256
    context headers per chunk: kz_entropy_encode may need more than kz_max_block_stream_bytes(n) for it (n + n/8 + 1024 + 102400
    per started 4 MiB is always enough); the batched calls store such a block as a raw copy, as the reference does (:926-973). */
-enum { KZ_E_NONE = 0, KZ_E_HUFFMAN = 1, KZ_E_FPAQ = 2, KZ_E_ANS0 = 5, KZ_E_ANS1 = 8 };
+/* KZ_E_RANGE = RANGE_TYPE 4: K/entropy/RangeEncoder.java:244-316, K/entropy/RangeDecoder.java:161-327 as EntropyCodecFactory builds
+   them (32 KiB chunks, logRange 12).  Its frequencies come from each chunk's own histogram, so real data codes below 8.1 bits per
+   byte and fits kz_max_block_stream_bytes(n); the coder's worst case is 12 bits per byte and more, so kz_entropy_encode sizes its
+   own buffer by the encoder's payload bound (50 KiB per started 32 KiB) and returns KZ_ERR_WRITE_FILE when the caller's is too
+   small; the batched calls store such a block as a raw copy, as the reference does (:926-973).  A chunk that outgrows even that
+   bound fails its block with KZ_ERR_PROCESS_BLOCK. */
+enum { KZ_E_NONE = 0, KZ_E_HUFFMAN = 1, KZ_E_FPAQ = 2, KZ_E_RANGE = 4, KZ_E_ANS0 = 5, KZ_E_ANS1 = 8 };
 /* error codes: K/Error.java:24-43 (returned negated); KZ_ERR_DEVICE is the one code the reference has no equivalent for */
 enum { KZ_ERR_MISSING_PARAM = 1, KZ_ERR_BLOCK_SIZE = 2, KZ_ERR_INVALID_CODEC = 3, KZ_ERR_READ_FILE = 11,
        KZ_ERR_WRITE_FILE = 12, KZ_ERR_PROCESS_BLOCK = 13, KZ_ERR_INVALID_FILE = 15, KZ_ERR_STREAM_VERSION = 16,

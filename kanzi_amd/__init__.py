@@ -28,12 +28,12 @@ LIB_PATH = os.path.join(_HERE, "libkanzi_hip.so")
 
 # transform ids (K/transform/TransformFactory.java:36-60) and entropy ids (K/entropy/EntropyCodecFactory.java)
 NONE_TYPE, BWT_TYPE, LZ_TYPE, RLT_TYPE, ZRLT_TYPE, MTFT_TYPE, RANK_TYPE, SRT_TYPE, MM_TYPE, LZX_TYPE, PACK_TYPE, DNA_TYPE = 0, 1, 3, 5, 6, 7, 8, 13, 15, 16, 18, 19
-E_NONE, E_HUFFMAN, E_FPAQ, E_ANS0, E_ANS1 = 0, 1, 2, 5, 8
+E_NONE, E_HUFFMAN, E_FPAQ, E_RANGE, E_ANS0, E_ANS1 = 0, 1, 2, 4, 5, 8
 TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "TEXT": 10, "SRT": 13, "MM": 15, "LZX": 16, "UTF": 17, "PACK": 18, "DNA": 19}
 TEXT_TYPE, UTF_TYPE = 10, 17
 # Global.DataType (K/Global.java:40-80), numbered as KZ_DT_* in include/kanzi_hip.h
 DATA_TYPES = {"UNDEFINED": 0, "DNA": 1, "SMALL_ALPHABET": 2, "TEXT": 3, "MULTIMEDIA": 4, "EXE": 5, "NUMERIC": 6, "BASE64": 7, "BIN": 8, "UTF8": 9}
-ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "ANS0": 5, "ANS1": 8}
+ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "RANGE": 4, "ANS0": 5, "ANS1": 8}
 MEM_HOST, MEM_DEVICE = 0, 1
 
 STAGE_NAMES = ["bwt_fwd", "sbrt_fwd", "zrlt_fwd", "entropy_enc", "frame_enc",
@@ -449,6 +449,8 @@ class _EntropyEncoder:
         cap = int(self.ctx.lib.kz_max_block_stream_bytes(count))
         if self.TYPE == E_ANS1:
             cap += 102400 * (count // (1 << 22) + 1)            # up to 256 context headers per 4 MiB chunk (include/kanzi_hip.h)
+        if self.TYPE == E_RANGE:
+            cap = max(cap, (count // (1 << 15) + 1) * (512 + 51200) + 1024)   # the encoder's payload bound per 32 KiB chunk (include/kanzi_hip.h)
         out = np.zeros(cap, dtype=np.uint8)
         nbits = self.ctx.lib.kz_entropy_encode(self.ctx.h, self.TYPE, s.ctypes.data, count, out.ctypes.data, cap)
         self.ctx.check(nbits)
@@ -515,6 +517,14 @@ class FPAQEncoder(_EntropyEncoder):
 
 class FPAQDecoder(_EntropyDecoder):
     TYPE = E_FPAQ
+
+
+class RangeEncoder(_EntropyEncoder):
+    TYPE = E_RANGE             # K/entropy/RangeEncoder.java as EntropyCodecFactory builds it (32 KiB chunks, logRange 12)
+
+
+class RangeDecoder(_EntropyDecoder):
+    TYPE = E_RANGE             # K/entropy/RangeDecoder.java
 
 
 class NullEntropyEncoder(_EntropyEncoder):

@@ -298,9 +298,9 @@ static int split_types(uint64_t tt, int* types) {                    // Transfor
   return k;
 }
 static bool transform_supported(int t) { return t == KZ_T_NONE || t == KZ_T_TEXT || t == KZ_T_UTF || t == KZ_T_BWT || t == KZ_T_RANK || t == KZ_T_MTFT || t == KZ_T_ZRLT || t == KZ_T_RLT || t == KZ_T_SRT || t == KZ_T_LZ || t == KZ_T_LZX || t == KZ_T_MM || t == KZ_T_PACK || t == KZ_T_DNA; }
-static bool entropy_supported(int e) { return e == KZ_E_NONE || e == KZ_E_ANS0 || e == KZ_E_ANS1 || e == KZ_E_HUFFMAN || e == KZ_E_FPAQ; }
+static bool entropy_supported(int e) { return e == KZ_E_NONE || e == KZ_E_ANS0 || e == KZ_E_ANS1 || e == KZ_E_HUFFMAN || e == KZ_E_FPAQ || e == KZ_E_RANGE; }
 // TEXT is TextCodec2 under NONE / ANS0 / HUFFMAN / RANGE and TextCodec1 under every other coder (TransformFactory.java:275-286)
-static bool text_codec1(int e) { return !(e == KZ_E_NONE || e == KZ_E_ANS0 || e == KZ_E_HUFFMAN || e == 4 /* RANGE */); }
+static bool text_codec1(int e) { return !(e == KZ_E_NONE || e == KZ_E_ANS0 || e == KZ_E_HUFFMAN || e == KZ_E_RANGE); }
 int64_t kz_ans1_max_stream_bytes(int n) { return (int64_t)kz_align((size_t)n + (size_t)(n >> 3) + 1024 + 102400 * ((size_t)n / (1 << 22) + 1), 256); }
 static int seq_max_len(const int* types, int nb, int n) {             // Sequence.java:215-226
   int req = n;
@@ -530,6 +530,8 @@ static size_t pipeline_scratch(int B, int maxLen, bool decode, const ChainSpec& 
     s += kz_ans1_scratch(B, maxLen, decode);
   else if (C.entropy == KZ_E_FPAQ)
     s += decode ? 4096 : kz_fpaq_scratch(B, maxLen);
+  else if (C.entropy == KZ_E_RANGE)
+    s += kz_range_scratch(B, maxLen, decode);
   return s;
 }
 
@@ -1513,7 +1515,7 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
     hipEvent_t e0; kz_stage_begin(ctx, &e0);
     int64_t inBytes = 0; for (int b = 0; b < B; b++) inBytes += bt.h_len[b];
     // copy blocks and NONE entropy: raw bytes (NullEntropyEncoder.java:66-81)
-    if (entropyType == KZ_E_ANS0 || entropyType == KZ_E_ANS1 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_FPAQ) {
+    if (entropyType == KZ_E_ANS0 || entropyType == KZ_E_ANS1 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_FPAQ || entropyType == KZ_E_RANGE) {
       // small copy blocks use NONE: mask them out of the ANS stage by zero length, then copy raw
       for (int b = 0; b < B; b++) h_mask[b] = h_copy[b] ? 0 : 1;
       KZ_HIP(hipMemcpyAsync(P.d_mask, h_mask.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
@@ -1524,8 +1526,15 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
       rc = (entropyType == KZ_E_ANS0) ? kz_stage_ans0_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
          : (entropyType == KZ_E_ANS1) ? kz_stage_ans1_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
          : (entropyType == KZ_E_HUFFMAN) ? kz_stage_huffman_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
+         : (entropyType == KZ_E_RANGE) ? kz_stage_range_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
                                          : kz_stage_fpaq_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits);
       if (rc) return rc;
+      if (entropyType == KZ_E_RANGE) {                                  // a chunk that outgrew its payload buffer fails its block (kz_range.hip)
+        std::vector<int32_t> ok(B);
+        KZ_HIP(hipMemcpyAsync(ok.data(), bt.d_flag, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        KZ_HIP(kz_stream_sync(ctx, st));
+        for (int b = 0; b < B; b++) if (!h_copy[b] && !ok[b]) h_threw[b] = 1;
+      }
       bt.h_len = saved;
       KZ_HIP(hipMemcpyAsync(bt.d_len, P.d_lenSave, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
     }
@@ -1763,12 +1772,13 @@ static int32_t decode_blocks_impl(kz_ctx* ctx, uint64_t transformType, uint32_t 
       if (in) outBytes += bt.h_len[b];
       h_rawp[b] = (in && (entropyType == KZ_E_NONE || h_raw[b] || h_tc[b])) ? 1 : 0;
     }
-    if (entropyType == KZ_E_ANS0 || entropyType == KZ_E_ANS1 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_FPAQ) {
+    if (entropyType == KZ_E_ANS0 || entropyType == KZ_E_ANS1 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_FPAQ || entropyType == KZ_E_RANGE) {
       for (int b = 0; b < B; b++) h_mask[b] = ((!part || (*part)[b]) && !(h_raw[b] || h_tc[b])) ? 1 : 0;
       int r = run_stage(ctx, P, h_mask, h_applied, [&](kz_batch& x) {
         return (entropyType == KZ_E_ANS0) ? kz_stage_ans0_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
              : (entropyType == KZ_E_ANS1) ? kz_stage_ans1_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
              : (entropyType == KZ_E_HUFFMAN) ? kz_stage_huffman_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
+             : (entropyType == KZ_E_RANGE) ? kz_stage_range_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
                                              : kz_stage_fpaq_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd); }, d_part);
       if (r) return r;
       for (int b = 0; b < B; b++) if (h_mask[b] && !h_applied[b] && !h_status[b]) h_status[b] = -KZ_ERR_PROCESS_BLOCK;
@@ -2179,7 +2189,7 @@ extern "C" int64_t kz_entropy_encode(kz_ctx* ctx, uint32_t type, const uint8_t* 
   }
   KZ_HIP(hipSetDevice(ctx->device));
   Pipe P;
-  const int64_t oS = (type == KZ_E_ANS1) ? kz_ans1_max_stream_bytes(n) : kz_max_block_stream_bytes(n);
+  const int64_t oS = (type == KZ_E_ANS1) ? kz_ans1_max_stream_bytes(n) : (type == KZ_E_RANGE) ? kz_range_max_stream_bytes(n) : kz_max_block_stream_bytes(n);
   ChainSpec CS; CS.nb = 0; CS.entropy = (int)type;
   int rc = pipe_setup(ctx, P, 1, n, oS + 256, false, CS);
   if (rc) return rc;
@@ -2195,9 +2205,15 @@ extern "C" int64_t kz_entropy_encode(kz_ctx* ctx, uint32_t type, const uint8_t* 
   KZ_HIP(hipMemsetAsync(d_out, 0, (size_t)oS, st));
   KZ_HIP(hipMemsetAsync(d_hdr, 0, 64, st));
   int64_t bits = 0;
-  if (type == KZ_E_ANS0 || type == KZ_E_ANS1 || type == KZ_E_HUFFMAN || type == KZ_E_FPAQ) {
-    rc = (type == KZ_E_ANS0) ? kz_stage_ans0_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_ANS1) ? kz_stage_ans1_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_HUFFMAN) ? kz_stage_huffman_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : kz_stage_fpaq_encode(ctx, bt, d_out, oS, d_hdr, d_bits);
+  if (type == KZ_E_ANS0 || type == KZ_E_ANS1 || type == KZ_E_HUFFMAN || type == KZ_E_FPAQ || type == KZ_E_RANGE) {
+    rc = (type == KZ_E_ANS0) ? kz_stage_ans0_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_ANS1) ? kz_stage_ans1_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_HUFFMAN) ? kz_stage_huffman_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_RANGE) ? kz_stage_range_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : kz_stage_fpaq_encode(ctx, bt, d_out, oS, d_hdr, d_bits);
     if (rc) return rc;
+    if (type == KZ_E_RANGE) {                                           // the chunk outgrew its payload buffer (kz_range.hip)
+      int32_t ok = 1;
+      KZ_HIP(hipMemcpyAsync(&ok, bt.d_flag, 4, hipMemcpyDeviceToHost, st));
+      KZ_HIP(kz_stream_sync(ctx, st));
+      if (!ok) { snprintf(ctx->err, sizeof(ctx->err), "range encode: a chunk's payload does not fit its buffer"); return -KZ_ERR_PROCESS_BLOCK; }
+    }
     KZ_HIP(hipMemcpyAsync(&bits, d_bits, 8, hipMemcpyDeviceToHost, st));
     KZ_HIP(kz_stream_sync(ctx, st));
   } else {
@@ -2234,9 +2250,9 @@ extern "C" int32_t kz_entropy_decode(kz_ctx* ctx, uint32_t type, const uint8_t* 
   KZ_HIP(hipMemcpyAsync(d_off, h, 16, hipMemcpyHostToDevice, st));
   bt.h_len[0] = count;
   KZ_HIP(hipMemcpyAsync(bt.d_len, &count, 4, hipMemcpyHostToDevice, st));
-  if (type == KZ_E_ANS0 || type == KZ_E_ANS1 || type == KZ_E_HUFFMAN || type == KZ_E_FPAQ) {
+  if (type == KZ_E_ANS0 || type == KZ_E_ANS1 || type == KZ_E_HUFFMAN || type == KZ_E_FPAQ || type == KZ_E_RANGE) {
     ctx->d_endBits = (long long*)(d_off + 2);
-    rc = (type == KZ_E_ANS0) ? kz_stage_ans0_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_ANS1) ? kz_stage_ans1_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_HUFFMAN) ? kz_stage_huffman_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : kz_stage_fpaq_decode(ctx, bt, d_in, inS, d_off, d_off + 1);
+    rc = (type == KZ_E_ANS0) ? kz_stage_ans0_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_ANS1) ? kz_stage_ans1_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_HUFFMAN) ? kz_stage_huffman_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_RANGE) ? kz_stage_range_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : kz_stage_fpaq_decode(ctx, bt, d_in, inS, d_off, d_off + 1);
     ctx->d_endBits = nullptr;
     if (rc) return rc;
     int32_t flag = 0;
