@@ -28,8 +28,9 @@ LIB_PATH = os.path.join(_HERE, "libkanzi_hip.so")
 
 # transform ids (K/transform/TransformFactory.java:36-60) and entropy ids (K/entropy/EntropyCodecFactory.java)
 NONE_TYPE, BWT_TYPE, LZ_TYPE, RLT_TYPE, ZRLT_TYPE, MTFT_TYPE, RANK_TYPE, SRT_TYPE, MM_TYPE, LZX_TYPE, PACK_TYPE, DNA_TYPE = 0, 1, 3, 5, 6, 7, 8, 13, 15, 16, 18, 19
+LZP_TYPE = 14
 E_NONE, E_HUFFMAN, E_FPAQ, E_RANGE, E_ANS0, E_ANS1 = 0, 1, 2, 4, 5, 8
-TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "TEXT": 10, "SRT": 13, "MM": 15, "LZX": 16, "UTF": 17, "PACK": 18, "DNA": 19}
+TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "TEXT": 10, "SRT": 13, "LZP": 14, "MM": 15, "LZX": 16, "UTF": 17, "PACK": 18, "DNA": 19}
 TEXT_TYPE, UTF_TYPE = 10, 17
 # Global.DataType (K/Global.java:40-80), numbered as KZ_DT_* in include/kanzi_hip.h
 DATA_TYPES = {"UNDEFINED": 0, "DNA": 1, "SMALL_ALPHABET": 2, "TEXT": 3, "MULTIMEDIA": 4, "EXE": 5, "NUMERIC": 6, "BASE64": 7, "BIN": 8, "UTF8": 9}
@@ -424,6 +425,10 @@ class LZCodec(_Transform):
     def __init__(self, ctx, lz=LZ_TYPE):
         super().__init__(ctx)
         self.TYPE = lz
+
+
+class LZPCodec(_Transform):
+    TYPE = LZP_TYPE            # K/transform/LZCodec.java:973-1287 (LZPCodec), bitstream 7: minMatch 64
 
 
 class SBRT(_Transform):
