@@ -7,7 +7,7 @@
  *   kz_transform_forward / _inverse / _max_encoded_len
  *       K/ByteTransform.java:36,48,56  (boolean forward(SliceByteArray,SliceByteArray), inverse, getMaxEncodedLength)
  *       for the codecs K/transform/BWTBlockCodec.java:71-213, K/transform/SBRT.java:87-214 (RANK, MTFT),
- *       K/transform/ZRLT.java:54-233, K/transform/RLT.java:69-410, K/transform/SRT.java:66-257, K/transform/LZCodec.java:299-756 (LZ, LZX), :1023-1286 (LZP),
+ *       K/transform/ZRLT.java:54-233, K/transform/RLT.java:69-410, K/transform/SRT.java:66-257, K/transform/LZCodec.java:299-756 (LZ, LZX), :1023-1286 (LZP), K/transform/EXECodec.java:110-772 (EXE),
  *       K/transform/FSDCodec.java:60-323 (MM), K/transform/AliasCodec.java:76-475 (PACK, DNA), and, as host (CPU) stages in front of
  *       the GPU chain, K/transform/TextCodec.java:482-531 (TEXT) and K/transform/UTFCodec.java:68-305 (UTF).
  *       "false" is a normal outcome (Sequence.java:95-105) -> return 0.
@@ -58,10 +58,10 @@ extern "C" {
 #define KZ_ABI_VERSION 3
 
 /* transform ids: K/transform/TransformFactory.java:36-60 */
-enum { KZ_T_NONE = 0, KZ_T_BWT = 1, KZ_T_LZ = 3, KZ_T_RLT = 5, KZ_T_ZRLT = 6, KZ_T_MTFT = 7, KZ_T_RANK = 8, KZ_T_TEXT = 10 /* DICT_TYPE */,
+enum { KZ_T_NONE = 0, KZ_T_BWT = 1, KZ_T_LZ = 3, KZ_T_RLT = 5, KZ_T_ZRLT = 6, KZ_T_MTFT = 7, KZ_T_RANK = 8, KZ_T_EXE = 9, KZ_T_TEXT = 10 /* DICT_TYPE */,
        KZ_T_SRT = 13, KZ_T_LZP = 14, KZ_T_MM = 15, KZ_T_LZX = 16, KZ_T_UTF = 17, KZ_T_PACK = 18, KZ_T_DNA = 19 };
 /* Global.DataType (K/Global.java:40-80): the per-block context entry "dataType" that MM (FSDCodec.java:78-85,160-168),
-   LZ/LZX (LZCodec.java:343-352) and RLT (RLT.java:95-132) read and write.  The KZ_DT_* VALUES ARE THIS LIBRARY'S OWN and are NOT the Java enum's
+   LZ/LZX (LZCodec.java:343-352), RLT (RLT.java:95-132) and EXE (EXECodec.java:130-137,156-157) read and write.  The KZ_DT_* VALUES ARE THIS LIBRARY'S OWN and are NOT the Java enum's
    ordinals (Java order: UNDEFINED, TEXT, MULTIMEDIA, EXE, NUMERIC, BASE64, DNA, BIN, UTF8, SMALL_ALPHABET); the value never
    reaches the stream, and a binding maps by NAME (integration/java/HipByteTransform.java). */
 enum { KZ_DT_UNDEFINED = 0, KZ_DT_DNA = 1, KZ_DT_SMALL_ALPHABET = 2, KZ_DT_TEXT = 3, KZ_DT_MULTIMEDIA = 4, KZ_DT_EXE = 5,

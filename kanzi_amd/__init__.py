@@ -29,8 +29,9 @@ LIB_PATH = os.path.join(_HERE, "libkanzi_hip.so")
 # transform ids (K/transform/TransformFactory.java:36-60) and entropy ids (K/entropy/EntropyCodecFactory.java)
 NONE_TYPE, BWT_TYPE, LZ_TYPE, RLT_TYPE, ZRLT_TYPE, MTFT_TYPE, RANK_TYPE, SRT_TYPE, MM_TYPE, LZX_TYPE, PACK_TYPE, DNA_TYPE = 0, 1, 3, 5, 6, 7, 8, 13, 15, 16, 18, 19
 LZP_TYPE = 14
+EXE_TYPE = 9
 E_NONE, E_HUFFMAN, E_FPAQ, E_RANGE, E_ANS0, E_ANS1 = 0, 1, 2, 4, 5, 8
-TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "TEXT": 10, "SRT": 13, "LZP": 14, "MM": 15, "LZX": 16, "UTF": 17, "PACK": 18, "DNA": 19}
+TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "EXE": 9, "TEXT": 10, "SRT": 13, "LZP": 14, "MM": 15, "LZX": 16, "UTF": 17, "PACK": 18, "DNA": 19}
 TEXT_TYPE, UTF_TYPE = 10, 17
 # Global.DataType (K/Global.java:40-80), numbered as KZ_DT_* in include/kanzi_hip.h
 DATA_TYPES = {"UNDEFINED": 0, "DNA": 1, "SMALL_ALPHABET": 2, "TEXT": 3, "MULTIMEDIA": 4, "EXE": 5, "NUMERIC": 6, "BASE64": 7, "BIN": 8, "UTF8": 9}
@@ -143,7 +144,7 @@ ABI_SYMBOLS = ["kz_abi_version", "kz_ctx_create", "kz_ctx_destroy", "kz_last_err
 
 # The reference's compression levels (K/app/BlockCompressor.java:537-573, getTransformAndCodec) as "transforms&entropy".
 # Levels 0-3, 5 and 6 consist of stages built here (TEXT and UTF run as host stages in front of the GPU chain);
-# 4 and 7-9 need ROLZ / EXE / LZP / CM / TPAQ.
+# 4 and 7-9 need ROLZ / CM / TPAQ (EXE and LZP are built; EXE in front of the host stages, as levels 8 and 9 put it, is not).
 LEVELS = {0: "NONE&NONE", 1: "LZX&NONE", 2: "DNA+LZ&HUFFMAN", 3: "TEXT+UTF+PACK+MM+LZX&HUFFMAN", 4: "TEXT+UTF+EXE+PACK+MM+ROLZ&NONE",
           5: "TEXT+UTF+BWT+RANK+ZRLT&ANS0", 6: "TEXT+UTF+BWT+SRT+ZRLT&FPAQ", 7: "LZP+TEXT+UTF+BWT+LZP&CM",
           8: "EXE+RLT+TEXT+UTF+DNA&TPAQ", 9: "EXE+RLT+TEXT+UTF+DNA&TPAQX"}
@@ -429,6 +430,12 @@ class LZCodec(_Transform):
 
 class LZPCodec(_Transform):
     TYPE = LZP_TYPE            # K/transform/LZCodec.java:973-1287 (LZPCodec), bitstream 7: minMatch 64
+
+
+class EXECodec(_Transform):
+    """K/transform/EXECodec.java, bitstream >= 3.  Its forward reads the context's "dataType" entry (``ctx.set_data_type``: only
+    UNDEFINED, EXE and BIN blocks are looked at) and writes EXE when it applies."""
+    TYPE = EXE_TYPE
 
 
 class SBRT(_Transform):
