@@ -75,7 +75,14 @@ enum { KZ_DT_UNDEFINED = 0, KZ_DT_DNA = 1, KZ_DT_SMALL_ALPHABET = 2, KZ_DT_TEXT 
    own buffer by the encoder's payload bound (50 KiB per started 32 KiB) and returns KZ_ERR_WRITE_FILE when the caller's is too
    small; the batched calls store such a block as a raw copy, as the reference does (:926-973).  A chunk that outgrows even that
    bound fails its block with KZ_ERR_PROCESS_BLOCK. */
-enum { KZ_E_NONE = 0, KZ_E_HUFFMAN = 1, KZ_E_FPAQ = 2, KZ_E_RANGE = 4, KZ_E_ANS0 = 5, KZ_E_ANS1 = 8 };
+/* KZ_E_CM = CM_TYPE 6: K/entropy/CMPredictor.java:100-186 behind K/entropy/BinaryEntropyEncoder.java:117-155, :187-218, :250-255 and
+   K/entropy/BinaryEntropyDecoder.java:117-167, :196-239, one coder and one fresh predictor per block.  Blocks of 1 << 26 bytes and
+   more, which the reference codes in 8 or 16 chunks, are refused with KZ_ERR_INVALID_CODEC in both directions.  A block's stream
+   (varint, payload, 7-byte tail) must fit what its block header leaves of the output row and a payload buffer of
+   kz_max_block_stream_bytes(n) bytes; no input known comes near that (the worst found expands by 3.7 %), but the coder's worst
+   case is 11 bits per bit, so the encoder checks, and a block that does not fit fails with KZ_ERR_PROCESS_BLOCK, its row
+   untouched behind the header bytes. */
+enum { KZ_E_NONE = 0, KZ_E_HUFFMAN = 1, KZ_E_FPAQ = 2, KZ_E_RANGE = 4, KZ_E_ANS0 = 5, KZ_E_CM = 6, KZ_E_ANS1 = 8 };
 /* error codes: K/Error.java:24-43 (returned negated); KZ_ERR_DEVICE is the one code the reference has no equivalent for */
 enum { KZ_ERR_MISSING_PARAM = 1, KZ_ERR_BLOCK_SIZE = 2, KZ_ERR_INVALID_CODEC = 3, KZ_ERR_READ_FILE = 11,
        KZ_ERR_WRITE_FILE = 12, KZ_ERR_PROCESS_BLOCK = 13, KZ_ERR_INVALID_FILE = 15, KZ_ERR_STREAM_VERSION = 16,

@@ -20,7 +20,7 @@ public final class HipEntropyDecoder implements EntropyDecoder {
   private final long bitLen;
   private final long[] used = new long[1];
 
-  public static boolean supports(int type) { return (type == 0) || (type == 1) || (type == 2) || (type == 4) || (type == 5) || (type == 8); }
+  public static boolean supports(int type) { return (type == 0) || (type == 1) || (type == 2) || (type == 4) || (type == 5) || (type == 6) || (type == 8); }
   public HipEntropyDecoder(long ctx, int type, InputBitStream bs, byte[] payload, long bitLen) {
     this.ctx = ctx; this.type = type; this.bitstream = bs; this.payload = payload; this.bitLen = bitLen;
     this.bitPos = bs.read();      // the block header (and checksum) in front of the payload have been read from the same stream

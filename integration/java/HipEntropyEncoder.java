@@ -12,7 +12,7 @@ public final class HipEntropyEncoder implements EntropyEncoder {
   private final OutputBitStream bitstream;
   private byte[] buf = new byte[0];
 
-  public static boolean supports(int type) { return (type == 0) || (type == 1) || (type == 2) || (type == 4) || (type == 5) || (type == 8); }   // NONE, HUFFMAN, FPAQ, RANGE, ANS0, ANS1
+  public static boolean supports(int type) { return (type == 0) || (type == 1) || (type == 2) || (type == 4) || (type == 5) || (type == 6) || (type == 8); }   // NONE, HUFFMAN, FPAQ, RANGE, ANS0, CM, ANS1
   public HipEntropyEncoder(long ctx, int type, OutputBitStream bs) { this.ctx = ctx; this.type = type; this.bitstream = bs; }
 
   @Override public int encode(byte[] block, int blkptr, int count) {
@@ -20,6 +20,7 @@ public final class HipEntropyEncoder implements EntropyEncoder {
     if (count == 0) return 0;
     int cap = count + (count >> 3) + 1024 + ((this.type == 8) ? 102400 * (count / (1 << 22) + 1) : 0);   // ANS1: 256 context headers per chunk
     if (this.type == 4) cap = Math.max(cap, (count / (1 << 15) + 1) * (512 + 51200) + 1024);               // RANGE: the encoder's payload bound per 32 KiB chunk
+    if (this.type == 6) cap = (cap + 255) & ~255;                                                          // CM: a stream fills at most kz_max_block_stream_bytes(count), the encoder checks
     if (this.buf.length < cap) this.buf = new byte[cap];
     long bits = KanziHip.entropyEncode(this.ctx, this.type, block, blkptr, count, this.buf);
     if (bits < 0) return -1;

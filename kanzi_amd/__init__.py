@@ -30,12 +30,12 @@ LIB_PATH = os.path.join(_HERE, "libkanzi_hip.so")
 NONE_TYPE, BWT_TYPE, LZ_TYPE, RLT_TYPE, ZRLT_TYPE, MTFT_TYPE, RANK_TYPE, SRT_TYPE, MM_TYPE, LZX_TYPE, PACK_TYPE, DNA_TYPE = 0, 1, 3, 5, 6, 7, 8, 13, 15, 16, 18, 19
 LZP_TYPE = 14
 EXE_TYPE = 9
-E_NONE, E_HUFFMAN, E_FPAQ, E_RANGE, E_ANS0, E_ANS1 = 0, 1, 2, 4, 5, 8
+E_NONE, E_HUFFMAN, E_FPAQ, E_RANGE, E_ANS0, E_CM, E_ANS1 = 0, 1, 2, 4, 5, 6, 8
 TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "EXE": 9, "TEXT": 10, "SRT": 13, "LZP": 14, "MM": 15, "LZX": 16, "UTF": 17, "PACK": 18, "DNA": 19}
 TEXT_TYPE, UTF_TYPE = 10, 17
 # Global.DataType (K/Global.java:40-80), numbered as KZ_DT_* in include/kanzi_hip.h
 DATA_TYPES = {"UNDEFINED": 0, "DNA": 1, "SMALL_ALPHABET": 2, "TEXT": 3, "MULTIMEDIA": 4, "EXE": 5, "NUMERIC": 6, "BASE64": 7, "BIN": 8, "UTF8": 9}
-ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "RANGE": 4, "ANS0": 5, "ANS1": 8}
+ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "RANGE": 4, "ANS0": 5, "CM": 6, "ANS1": 8}
 MEM_HOST, MEM_DEVICE = 0, 1
 
 STAGE_NAMES = ["bwt_fwd", "sbrt_fwd", "zrlt_fwd", "entropy_enc", "frame_enc",
@@ -144,7 +144,8 @@ ABI_SYMBOLS = ["kz_abi_version", "kz_ctx_create", "kz_ctx_destroy", "kz_last_err
 
 # The reference's compression levels (K/app/BlockCompressor.java:537-573, getTransformAndCodec) as "transforms&entropy".
 # Levels 0-3, 5 and 6 consist of stages built here (TEXT and UTF run as host stages in front of the GPU chain);
-# 4 and 7-9 need ROLZ / CM / TPAQ (EXE and LZP are built; EXE in front of the host stages, as levels 8 and 9 put it, is not).
+# 4, 8 and 9 need ROLZ / TPAQ.  Every stage of level 7 is built (LZP, CM), but it puts LZP in front of TEXT and UTF, and the host
+# stages only run in front of the GPU stages: level_chain refuses that order, as it refuses levels 8 and 9 for EXE + RLT there.
 LEVELS = {0: "NONE&NONE", 1: "LZX&NONE", 2: "DNA+LZ&HUFFMAN", 3: "TEXT+UTF+PACK+MM+LZX&HUFFMAN", 4: "TEXT+UTF+EXE+PACK+MM+ROLZ&NONE",
           5: "TEXT+UTF+BWT+RANK+ZRLT&ANS0", 6: "TEXT+UTF+BWT+SRT+ZRLT&FPAQ", 7: "LZP+TEXT+UTF+BWT+LZP&CM",
           8: "EXE+RLT+TEXT+UTF+DNA&TPAQ", 9: "EXE+RLT+TEXT+UTF+DNA&TPAQX"}
@@ -160,6 +161,10 @@ def level_chain(level, allow_partial=False):
     missing = [n for n in names if n not in TRANSFORM_IDS] + ([e] if e not in ENTROPY_IDS else [])
     if missing:
         raise KanziError(3, "level %d needs %s, not built here" % (level, "/".join(missing)))       # ERR_INVALID_CODEC
+    host = [n in ("TEXT", "UTF") for n in names]
+    if any(host[i] and not host[i - 1] for i in range(1, len(names))):
+        raise KanziError(3, "level %d puts %s in front of TEXT / UTF: the host stages run only in front of the GPU stages (stage order)"
+                         % (level, "+".join(names[:host.index(True)])))
     return "+".join(names), e
 
 
@@ -537,6 +542,14 @@ class RangeEncoder(_EntropyEncoder):
 
 class RangeDecoder(_EntropyDecoder):
     TYPE = E_RANGE             # K/entropy/RangeDecoder.java
+
+
+class CMEncoder(_EntropyEncoder):
+    TYPE = E_CM                # K/entropy/BinaryEntropyEncoder.java over K/entropy/CMPredictor.java (encode + dispose); blocks below 1 << 26 bytes
+
+
+class CMDecoder(_EntropyDecoder):
+    TYPE = E_CM                # K/entropy/BinaryEntropyDecoder.java over K/entropy/CMPredictor.java
 
 
 class NullEntropyEncoder(_EntropyEncoder):

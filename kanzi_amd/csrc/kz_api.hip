@@ -4,6 +4,7 @@
 #include <dirent.h>
 #include "kz_device.h"
 #include "kz_internal.h"
+#include "kz_cm_host.h"
 #include <stdlib.h>
 #include <algorithm>
 #include <atomic>
@@ -71,6 +72,7 @@ void kz_switches_read(kz_switches& s) {
   s.bwtDmax = num("KZ_BWT_DMAX", -1); s.bwtRetire = num("KZ_BWT_RETIRE", -1); s.bwtLazyRank = num("KZ_BWT_LAZYRANK", -1);
   s.bwtTrace = flag("KZ_BWT_TRACE");
   s.bwtTestTrieOverflow = digit("KZ_BWT_TEST_TRIE_OVERFLOW", 0, 9, -1);
+  s.cmTestRowBytes = num("KZ_CM_TEST_ROW_BYTES", 0);
   { const char* f = getenv("KZ_FPAQ_FORCE"); s.fpaqForce = f ? ((f[0] == 'w' || f[0] == 'W' || f[0] == '1') ? 1 : ((f[0] == 'l' || f[0] == 'L' || f[0] == '2') ? 2 : 0)) : 0; }
   s.sbrtForm = num("KZ_SBRT_FORM", -1);
 }
@@ -300,7 +302,7 @@ static int split_types(uint64_t tt, int* types) {                    // Transfor
   return k;
 }
 static bool transform_supported(int t) { return t == KZ_T_NONE || t == KZ_T_TEXT || t == KZ_T_UTF || t == KZ_T_BWT || t == KZ_T_RANK || t == KZ_T_MTFT || t == KZ_T_ZRLT || t == KZ_T_RLT || t == KZ_T_SRT || t == KZ_T_LZ || t == KZ_T_LZX || t == KZ_T_LZP || t == KZ_T_EXE || t == KZ_T_MM || t == KZ_T_PACK || t == KZ_T_DNA; }
-static bool entropy_supported(int e) { return e == KZ_E_NONE || e == KZ_E_ANS0 || e == KZ_E_ANS1 || e == KZ_E_HUFFMAN || e == KZ_E_FPAQ || e == KZ_E_RANGE; }
+static bool entropy_supported(int e) { return e == KZ_E_NONE || e == KZ_E_ANS0 || e == KZ_E_ANS1 || e == KZ_E_HUFFMAN || e == KZ_E_FPAQ || e == KZ_E_RANGE || e == KZ_E_CM; }
 // TEXT is TextCodec2 under NONE / ANS0 / HUFFMAN / RANGE and TextCodec1 under every other coder (TransformFactory.java:275-286)
 static bool text_codec1(int e) { return !(e == KZ_E_NONE || e == KZ_E_ANS0 || e == KZ_E_HUFFMAN || e == KZ_E_RANGE); }
 int64_t kz_ans1_max_stream_bytes(int n) { return (int64_t)kz_align((size_t)n + (size_t)(n >> 3) + 1024 + 102400 * ((size_t)n / (1 << 22) + 1), 256); }
@@ -536,6 +538,8 @@ static size_t pipeline_scratch(int B, int maxLen, bool decode, const ChainSpec& 
     s += decode ? 4096 : kz_fpaq_scratch(B, maxLen);
   else if (C.entropy == KZ_E_RANGE)
     s += kz_range_scratch(B, maxLen, decode);
+  else if (C.entropy == KZ_E_CM)
+    s += kz_cm_scratch(B, maxLen, decode);
   return s;
 }
 
@@ -1521,7 +1525,7 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
     hipEvent_t e0; kz_stage_begin(ctx, &e0);
     int64_t inBytes = 0; for (int b = 0; b < B; b++) inBytes += bt.h_len[b];
     // copy blocks and NONE entropy: raw bytes (NullEntropyEncoder.java:66-81)
-    if (entropyType == KZ_E_ANS0 || entropyType == KZ_E_ANS1 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_FPAQ || entropyType == KZ_E_RANGE) {
+    if (entropyType == KZ_E_ANS0 || entropyType == KZ_E_ANS1 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_FPAQ || entropyType == KZ_E_RANGE || entropyType == KZ_E_CM) {
       // small copy blocks use NONE: mask them out of the ANS stage by zero length, then copy raw
       for (int b = 0; b < B; b++) h_mask[b] = h_copy[b] ? 0 : 1;
       KZ_HIP(hipMemcpyAsync(P.d_mask, h_mask.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
@@ -1533,9 +1537,10 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
          : (entropyType == KZ_E_ANS1) ? kz_stage_ans1_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
          : (entropyType == KZ_E_HUFFMAN) ? kz_stage_huffman_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
          : (entropyType == KZ_E_RANGE) ? kz_stage_range_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
+         : (entropyType == KZ_E_CM) ? kz_stage_cm_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
                                          : kz_stage_fpaq_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits);
       if (rc) return rc;
-      if (entropyType == KZ_E_RANGE) {                                  // a chunk that outgrew its payload buffer fails its block (kz_range.hip)
+      if (entropyType == KZ_E_RANGE || entropyType == KZ_E_CM) {        // a chunk that outgrew its payload buffer (kz_range.hip), a stream that outgrew its row (kz_cm.hip): the block fails
         std::vector<int32_t> ok(B);
         KZ_HIP(hipMemcpyAsync(ok.data(), bt.d_flag, (size_t)B * 4, hipMemcpyDeviceToHost, st));
         KZ_HIP(kz_stream_sync(ctx, st));
@@ -1778,13 +1783,14 @@ static int32_t decode_blocks_impl(kz_ctx* ctx, uint64_t transformType, uint32_t 
       if (in) outBytes += bt.h_len[b];
       h_rawp[b] = (in && (entropyType == KZ_E_NONE || h_raw[b] || h_tc[b])) ? 1 : 0;
     }
-    if (entropyType == KZ_E_ANS0 || entropyType == KZ_E_ANS1 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_FPAQ || entropyType == KZ_E_RANGE) {
+    if (entropyType == KZ_E_ANS0 || entropyType == KZ_E_ANS1 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_FPAQ || entropyType == KZ_E_RANGE || entropyType == KZ_E_CM) {
       for (int b = 0; b < B; b++) h_mask[b] = ((!part || (*part)[b]) && !(h_raw[b] || h_tc[b])) ? 1 : 0;
       int r = run_stage(ctx, P, h_mask, h_applied, [&](kz_batch& x) {
         return (entropyType == KZ_E_ANS0) ? kz_stage_ans0_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
              : (entropyType == KZ_E_ANS1) ? kz_stage_ans1_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
              : (entropyType == KZ_E_HUFFMAN) ? kz_stage_huffman_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
              : (entropyType == KZ_E_RANGE) ? kz_stage_range_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
+             : (entropyType == KZ_E_CM) ? kz_stage_cm_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
                                              : kz_stage_fpaq_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd); }, d_part);
       if (r) return r;
       for (int b = 0; b < B; b++) if (h_mask[b] && !h_applied[b] && !h_status[b]) h_status[b] = -KZ_ERR_PROCESS_BLOCK;
@@ -2184,10 +2190,11 @@ extern "C" int32_t kz_transform_inverse(kz_ctx* ctx, uint32_t type, const uint8_
 extern "C" int64_t kz_entropy_encode(kz_ctx* ctx, uint32_t type, const uint8_t* src, int32_t n, uint8_t* out, int64_t outCapBytes) {
   if (!ctx || !src || !out || n < 0) return -KZ_ERR_INVALID_PARAM;
   if (!entropy_supported((int)type)) return -KZ_ERR_INVALID_CODEC;
+  if (type == KZ_E_CM && n >= KZ_CM_MAX_BLOCK) { snprintf(ctx->err, sizeof(ctx->err), "cm encode: block of %d bytes: CM blocks go up to (1 << 26) - 1 bytes", n); return -KZ_ERR_INVALID_CODEC; }
   if (n == 0) {
     // encode() of nothing writes nothing; FPAQ's dispose() still flushes its 56-bit low register, all zero but the
     // 24 padding ones (FPAQEncoder.java:232-238): the call stands for encode + dispose
-    if (type != KZ_E_FPAQ) return 0;
+    if (type != KZ_E_FPAQ && type != KZ_E_CM) return 0;                  // (BinaryEntropyEncoder.java:250-255 for CM: the same tail)
     if (outCapBytes < 7) return -KZ_ERR_INVALID_PARAM;
     const uint8_t flush[7] = {0, 0, 0, 0, 0xFF, 0xFF, 0xFF};
     memcpy(out, flush, 7);
@@ -2211,14 +2218,14 @@ extern "C" int64_t kz_entropy_encode(kz_ctx* ctx, uint32_t type, const uint8_t* 
   KZ_HIP(hipMemsetAsync(d_out, 0, (size_t)oS, st));
   KZ_HIP(hipMemsetAsync(d_hdr, 0, 64, st));
   int64_t bits = 0;
-  if (type == KZ_E_ANS0 || type == KZ_E_ANS1 || type == KZ_E_HUFFMAN || type == KZ_E_FPAQ || type == KZ_E_RANGE) {
-    rc = (type == KZ_E_ANS0) ? kz_stage_ans0_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_ANS1) ? kz_stage_ans1_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_HUFFMAN) ? kz_stage_huffman_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_RANGE) ? kz_stage_range_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : kz_stage_fpaq_encode(ctx, bt, d_out, oS, d_hdr, d_bits);
+  if (type == KZ_E_ANS0 || type == KZ_E_ANS1 || type == KZ_E_HUFFMAN || type == KZ_E_FPAQ || type == KZ_E_RANGE || type == KZ_E_CM) {
+    rc = (type == KZ_E_ANS0) ? kz_stage_ans0_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_ANS1) ? kz_stage_ans1_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_HUFFMAN) ? kz_stage_huffman_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_RANGE) ? kz_stage_range_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_CM) ? kz_stage_cm_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : kz_stage_fpaq_encode(ctx, bt, d_out, oS, d_hdr, d_bits);
     if (rc) return rc;
-    if (type == KZ_E_RANGE) {                                           // the chunk outgrew its payload buffer (kz_range.hip)
+    if (type == KZ_E_RANGE || type == KZ_E_CM) {                        // the chunk outgrew its payload buffer (kz_range.hip), the stream its row (kz_cm.hip)
       int32_t ok = 1;
       KZ_HIP(hipMemcpyAsync(&ok, bt.d_flag, 4, hipMemcpyDeviceToHost, st));
       KZ_HIP(kz_stream_sync(ctx, st));
-      if (!ok) { snprintf(ctx->err, sizeof(ctx->err), "range encode: a chunk's payload does not fit its buffer"); return -KZ_ERR_PROCESS_BLOCK; }
+      if (!ok) { snprintf(ctx->err, sizeof(ctx->err), type == KZ_E_CM ? "cm encode: the block's stream does not fit its buffer" : "range encode: a chunk's payload does not fit its buffer"); return -KZ_ERR_PROCESS_BLOCK; }
     }
     KZ_HIP(hipMemcpyAsync(&bits, d_bits, 8, hipMemcpyDeviceToHost, st));
     KZ_HIP(kz_stream_sync(ctx, st));
@@ -2236,6 +2243,7 @@ extern "C" int64_t kz_entropy_encode(kz_ctx* ctx, uint32_t type, const uint8_t* 
 extern "C" int32_t kz_entropy_decode(kz_ctx* ctx, uint32_t type, const uint8_t* in, int64_t inBits, uint8_t* dst, int32_t count, int64_t* bitsConsumed) {
   if (!ctx || !in || !dst || count < 0) return -KZ_ERR_INVALID_PARAM;
   if (!entropy_supported((int)type)) return -KZ_ERR_INVALID_CODEC;
+  if (type == KZ_E_CM && count >= KZ_CM_MAX_BLOCK) { snprintf(ctx->err, sizeof(ctx->err), "cm decode: block of %d bytes: CM blocks go up to (1 << 26) - 1 bytes", count); return -KZ_ERR_INVALID_CODEC; }
   if (bitsConsumed) *bitsConsumed = 0;
   if (count == 0) return 0;
   KZ_HIP(hipSetDevice(ctx->device));
@@ -2256,9 +2264,9 @@ extern "C" int32_t kz_entropy_decode(kz_ctx* ctx, uint32_t type, const uint8_t* 
   KZ_HIP(hipMemcpyAsync(d_off, h, 16, hipMemcpyHostToDevice, st));
   bt.h_len[0] = count;
   KZ_HIP(hipMemcpyAsync(bt.d_len, &count, 4, hipMemcpyHostToDevice, st));
-  if (type == KZ_E_ANS0 || type == KZ_E_ANS1 || type == KZ_E_HUFFMAN || type == KZ_E_FPAQ || type == KZ_E_RANGE) {
+  if (type == KZ_E_ANS0 || type == KZ_E_ANS1 || type == KZ_E_HUFFMAN || type == KZ_E_FPAQ || type == KZ_E_RANGE || type == KZ_E_CM) {
     ctx->d_endBits = (long long*)(d_off + 2);
-    rc = (type == KZ_E_ANS0) ? kz_stage_ans0_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_ANS1) ? kz_stage_ans1_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_HUFFMAN) ? kz_stage_huffman_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_RANGE) ? kz_stage_range_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : kz_stage_fpaq_decode(ctx, bt, d_in, inS, d_off, d_off + 1);
+    rc = (type == KZ_E_ANS0) ? kz_stage_ans0_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_ANS1) ? kz_stage_ans1_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_HUFFMAN) ? kz_stage_huffman_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_RANGE) ? kz_stage_range_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_CM) ? kz_stage_cm_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : kz_stage_fpaq_decode(ctx, bt, d_in, inS, d_off, d_off + 1);
     ctx->d_endBits = nullptr;
     if (rc) return rc;
     int32_t flag = 0;

@@ -14,8 +14,8 @@
 #include <thread>
 #include "../../include/kanzi_hip.h"
 
-enum KzKernelId { KID_ANS_ENC_CHUNK, KID_ANS_ENC_SCAN, KID_ANS_ENC_CONCAT, KID_ANS_DEC_INDEX, KID_ANS_DEC_CHUNK, KID_ANS_DEC_FIN, KID_MASK_LEN, KID_PASSTHROUGH, KID_FRAME_PREPARE, KID_COPY_BYTES, KID_FRAME_DECIDE, KID_FRAME_HEADER, KID_FRAME_PARSE, KID_COPY_PAYLOAD, KID_BWT_INIT, KID_RADIX_HIST, KID_RADIX_SCAN, KID_RADIX_SCATTER, KID_SEG_REDUCE, KID_SEG_SCAN, KID_SEG_APPLY, KID_LIVE_EMIT, KID_BWT_EMIT, KID_BWTI_PARSE, KID_BWTI_HIST, KID_BWTI_SCAN, KID_BWTI_SCATTER, KID_BWTI_WALK1, KID_BWTI_RESOLVE, KID_BWTI_COPY, KID_BWTI_LITERAL, KID_BWTI_FIN, KID_SBRT_LAST2, KID_SBRT_SCAN, KID_SBRT_REPLAY, KID_COPY_LEN, KID_SBRT_INVERSE, KID_ZRLT_F1, KID_ZRLT_F2, KID_ZRLT_F3, KID_ZRLT_FFIN, KID_ZRLT_I1, KID_ZRLT_I2, KID_ZRLT_I3, KID_ZRLT_IFIN, KID_RLT_F0, KID_RLT_FSCAN, KID_RLT_F1, KID_RLT_FSUM, KID_RLT_F3, KID_RLT_FTAIL, KID_RLT_I1, KID_RLT_ISCAN, KID_RLT_I2, KID_RLT_ISUM, KID_RLT_I3, KID_RLT_IFIN, KID_HUF_ENC_CHUNK, KID_HUF_DEC_INDEX, KID_HUF_DEC_CHUNK, KID_HUF_DEC_FIN, KID_FPAQ_ENC, KID_FPAQ_PACK, KID_FPAQ_DEC, KID_SRT_HIST, KID_SRT_PREP, KID_SRT_SCATTER, KID_SRT_INV, KID_LZ_FWD, KID_LZ_INV, KID_XXHASH, KID_BLOCK_MAGIC, KID_MM_ANALYZE, KID_MM_EMIT, KID_MM_CHECK, KID_MM_INV, KID_ALIAS_ANALYZE, KID_ALIAS_HIST1, KID_ALIAS_SELECT, KID_ALIAS_EMIT, KID_ALIAS_INV, KID_SKIP_DECIDE, KID_MSD_HIST, KID_MSD_SCAN, KID_MSD_SCATTER, KID_BUCKET_SORT, KID_BUCKET_COUNT, KID_BUCKET_COUNT_S, KID_TR_HIST16, KID_TR_ASSIGN, KID_TR_COUNT, KID_TR_SCATTER, KID_TR_SORT, KID_TEXT_INV, KID_UTF_INV, KID_TEXT_FWD, KID_TEXT_WALK, KID_UTF_FWD, KID_ANS1_HIST, KID_ANS1_NORM, KID_ANS1_HDR, KID_ANS1_ENC, KID_ANS1_DEC_INDEX, KID_ANS1_DEC_TABLE, KID_ANS1_DEC_CHUNK, KID_ANS1_DEC_FIN, KID_RANGE_ENC_CHUNK, KID_RANGE_ENC_FIN, KID_RANGE_DEC, KID_LZP_FWD, KID_LZP_INV, KID_EXE_SETUP, KID_EXE_MAP, KID_EXE_SCAN, KID_EXE_HIST, KID_EXE_DECIDE, KID_EXE_SIZE, KID_EXE_VERDICT, KID_EXE_EMIT, KID_COUNT };
-#define KZ_KERNEL_NAMES { "k_ans_enc_chunk", "k_ans_enc_scan", "k_ans_enc_concat", "k_ans_dec_index", "k_ans_dec_chunk", "k_ans_dec_fin", "k_mask_len", "k_passthrough", "k_frame_prepare", "k_copy_bytes", "k_frame_decide", "k_frame_header", "k_frame_parse", "k_copy_payload", "k_bwt_init", "k_radix_hist", "k_radix_scan", "k_radix_scatter", "k_seg_reduce", "k_seg_scan", "k_seg_apply", "k_live_emit", "k_bwt_emit", "k_bwti_parse", "k_bwti_hist", "k_bwti_scan", "k_bwti_scatter", "k_bwti_walk1", "k_bwti_resolve", "k_bwti_copy", "k_bwti_literal", "k_bwti_fin", "k_sbrt_last2", "k_sbrt_scan", "k_sbrt_replay", "k_copy_len", "k_sbrt_inverse", "k_zrlt_f1", "k_zrlt_f2", "k_zrlt_f3", "k_zrlt_ffin", "k_zrlt_i1", "k_zrlt_i2", "k_zrlt_i3", "k_zrlt_ifin", "k_rlt_f0", "k_rlt_fscan", "k_rlt_f1", "k_rlt_fsum", "k_rlt_f3", "k_rlt_ftail", "k_rlt_i1", "k_rlt_iscan", "k_rlt_i2", "k_rlt_isum", "k_rlt_i3", "k_rlt_ifin", "k_huf_enc_chunk", "k_huf_dec_index", "k_huf_dec_chunk", "k_huf_dec_fin", "k_fpaq_enc", "k_fpaq_pack", "k_fpaq_dec", "k_srt_hist", "k_srt_prep", "k_srt_scatter", "k_srt_inv", "k_lz_fwd", "k_lz_inv", "k_xxhash", "k_block_magic", "k_mm_analyze", "k_mm_emit", "k_mm_check", "k_mm_inv", "k_alias_analyze", "k_alias_hist1", "k_alias_select", "k_alias_emit", "k_alias_inv", "k_skip_decide", "k_msd_hist", "k_msd_scan", "k_msd_scatter", "k_bucket_sort", "k_bucket_count", "k_bucket_count_s", "k_tr_hist16", "k_tr_assign", "k_tr_count", "k_tr_scatter", "k_tr_sort", "k_text_inv", "k_utf_inv", "k_text_fwd", "k_text_walk", "k_utf_fwd", "k_ans1_hist", "k_ans1_norm", "k_ans1_hdr", "k_ans1_enc", "k_ans1_dec_index", "k_ans1_dec_table", "k_ans1_dec_chunk", "k_ans1_dec_fin", "k_range_enc_chunk", "k_range_enc_fin", "k_range_dec", "k_lzp_fwd", "k_lzp_inv", "k_exe_setup", "k_exe_map", "k_exe_scan", "k_exe_hist", "k_exe_decide", "k_exe_size", "k_exe_verdict", "k_exe_emit" }
+enum KzKernelId { KID_ANS_ENC_CHUNK, KID_ANS_ENC_SCAN, KID_ANS_ENC_CONCAT, KID_ANS_DEC_INDEX, KID_ANS_DEC_CHUNK, KID_ANS_DEC_FIN, KID_MASK_LEN, KID_PASSTHROUGH, KID_FRAME_PREPARE, KID_COPY_BYTES, KID_FRAME_DECIDE, KID_FRAME_HEADER, KID_FRAME_PARSE, KID_COPY_PAYLOAD, KID_BWT_INIT, KID_RADIX_HIST, KID_RADIX_SCAN, KID_RADIX_SCATTER, KID_SEG_REDUCE, KID_SEG_SCAN, KID_SEG_APPLY, KID_LIVE_EMIT, KID_BWT_EMIT, KID_BWTI_PARSE, KID_BWTI_HIST, KID_BWTI_SCAN, KID_BWTI_SCATTER, KID_BWTI_WALK1, KID_BWTI_RESOLVE, KID_BWTI_COPY, KID_BWTI_LITERAL, KID_BWTI_FIN, KID_SBRT_LAST2, KID_SBRT_SCAN, KID_SBRT_REPLAY, KID_COPY_LEN, KID_SBRT_INVERSE, KID_ZRLT_F1, KID_ZRLT_F2, KID_ZRLT_F3, KID_ZRLT_FFIN, KID_ZRLT_I1, KID_ZRLT_I2, KID_ZRLT_I3, KID_ZRLT_IFIN, KID_RLT_F0, KID_RLT_FSCAN, KID_RLT_F1, KID_RLT_FSUM, KID_RLT_F3, KID_RLT_FTAIL, KID_RLT_I1, KID_RLT_ISCAN, KID_RLT_I2, KID_RLT_ISUM, KID_RLT_I3, KID_RLT_IFIN, KID_HUF_ENC_CHUNK, KID_HUF_DEC_INDEX, KID_HUF_DEC_CHUNK, KID_HUF_DEC_FIN, KID_FPAQ_ENC, KID_FPAQ_PACK, KID_FPAQ_DEC, KID_SRT_HIST, KID_SRT_PREP, KID_SRT_SCATTER, KID_SRT_INV, KID_LZ_FWD, KID_LZ_INV, KID_XXHASH, KID_BLOCK_MAGIC, KID_MM_ANALYZE, KID_MM_EMIT, KID_MM_CHECK, KID_MM_INV, KID_ALIAS_ANALYZE, KID_ALIAS_HIST1, KID_ALIAS_SELECT, KID_ALIAS_EMIT, KID_ALIAS_INV, KID_SKIP_DECIDE, KID_MSD_HIST, KID_MSD_SCAN, KID_MSD_SCATTER, KID_BUCKET_SORT, KID_BUCKET_COUNT, KID_BUCKET_COUNT_S, KID_TR_HIST16, KID_TR_ASSIGN, KID_TR_COUNT, KID_TR_SCATTER, KID_TR_SORT, KID_TEXT_INV, KID_UTF_INV, KID_TEXT_FWD, KID_TEXT_WALK, KID_UTF_FWD, KID_ANS1_HIST, KID_ANS1_NORM, KID_ANS1_HDR, KID_ANS1_ENC, KID_ANS1_DEC_INDEX, KID_ANS1_DEC_TABLE, KID_ANS1_DEC_CHUNK, KID_ANS1_DEC_FIN, KID_RANGE_ENC_CHUNK, KID_RANGE_ENC_FIN, KID_RANGE_DEC, KID_CM_ENC, KID_CM_DEC, KID_LZP_FWD, KID_LZP_INV, KID_EXE_SETUP, KID_EXE_MAP, KID_EXE_SCAN, KID_EXE_HIST, KID_EXE_DECIDE, KID_EXE_SIZE, KID_EXE_VERDICT, KID_EXE_EMIT, KID_COUNT };
+#define KZ_KERNEL_NAMES { "k_ans_enc_chunk", "k_ans_enc_scan", "k_ans_enc_concat", "k_ans_dec_index", "k_ans_dec_chunk", "k_ans_dec_fin", "k_mask_len", "k_passthrough", "k_frame_prepare", "k_copy_bytes", "k_frame_decide", "k_frame_header", "k_frame_parse", "k_copy_payload", "k_bwt_init", "k_radix_hist", "k_radix_scan", "k_radix_scatter", "k_seg_reduce", "k_seg_scan", "k_seg_apply", "k_live_emit", "k_bwt_emit", "k_bwti_parse", "k_bwti_hist", "k_bwti_scan", "k_bwti_scatter", "k_bwti_walk1", "k_bwti_resolve", "k_bwti_copy", "k_bwti_literal", "k_bwti_fin", "k_sbrt_last2", "k_sbrt_scan", "k_sbrt_replay", "k_copy_len", "k_sbrt_inverse", "k_zrlt_f1", "k_zrlt_f2", "k_zrlt_f3", "k_zrlt_ffin", "k_zrlt_i1", "k_zrlt_i2", "k_zrlt_i3", "k_zrlt_ifin", "k_rlt_f0", "k_rlt_fscan", "k_rlt_f1", "k_rlt_fsum", "k_rlt_f3", "k_rlt_ftail", "k_rlt_i1", "k_rlt_iscan", "k_rlt_i2", "k_rlt_isum", "k_rlt_i3", "k_rlt_ifin", "k_huf_enc_chunk", "k_huf_dec_index", "k_huf_dec_chunk", "k_huf_dec_fin", "k_fpaq_enc", "k_fpaq_pack", "k_fpaq_dec", "k_srt_hist", "k_srt_prep", "k_srt_scatter", "k_srt_inv", "k_lz_fwd", "k_lz_inv", "k_xxhash", "k_block_magic", "k_mm_analyze", "k_mm_emit", "k_mm_check", "k_mm_inv", "k_alias_analyze", "k_alias_hist1", "k_alias_select", "k_alias_emit", "k_alias_inv", "k_skip_decide", "k_msd_hist", "k_msd_scan", "k_msd_scatter", "k_bucket_sort", "k_bucket_count", "k_bucket_count_s", "k_tr_hist16", "k_tr_assign", "k_tr_count", "k_tr_scatter", "k_tr_sort", "k_text_inv", "k_utf_inv", "k_text_fwd", "k_text_walk", "k_utf_fwd", "k_ans1_hist", "k_ans1_norm", "k_ans1_hdr", "k_ans1_enc", "k_ans1_dec_index", "k_ans1_dec_table", "k_ans1_dec_chunk", "k_ans1_dec_fin", "k_range_enc_chunk", "k_range_enc_fin", "k_range_dec", "k_cm_enc", "k_cm_dec", "k_lzp_fwd", "k_lzp_inv", "k_exe_setup", "k_exe_map", "k_exe_scan", "k_exe_hist", "k_exe_decide", "k_exe_size", "k_exe_verdict", "k_exe_emit" }
 // Environment switches (diagnostics, A/B runs, the tests' forced schedules; none is needed for normal use).  Read ONCE, when the
 // context is created (kz_switches_read, kz_api.hip); kz_ctx_reload_switches re-reads them for a live context (tests, A/B tools).
 // Nothing on a call's path calls getenv.
@@ -44,6 +44,7 @@ struct kz_switches {
   int bwtTrace = 0;              // KZ_BWT_TRACE
   int bwtTestTrieOverflow = -1;  // KZ_BWT_TEST_TRIE_OVERFLOW=<round> (tests)
   int fpaqForce = 0;             // KZ_FPAQ_FORCE: 0 unset, 1 wave, 2 lane
+  int cmTestRowBytes = 0;        // KZ_CM_TEST_ROW_BYTES=<bytes> (tests): the CM encoder takes its output rows to be this short
   int sbrtForm = -1;             // KZ_SBRT_FORM: -1 default, 0 = the 32-bit list forms of rounds 2-5 (A/B)
 };
 void kz_switches_read(kz_switches& s);   // kz_api.hip
@@ -212,6 +213,12 @@ int kz_stage_range_encode(kz_ctx*, kz_batch&, uint8_t* out, int64_t outStride, c
 int kz_stage_range_decode(kz_ctx*, kz_batch&, const uint8_t* in, int64_t inStride, const int64_t* d_bitOff, const int64_t* d_bitEnd);
 size_t kz_range_scratch(int B, int maxN, bool decode);
 int64_t kz_range_max_stream_bytes(int n);  // a single block's RANGE stream at the encoder's payload buffer bound (12.5 bits per byte and the headers)
+// CM, the context-model binary coder (kz_cm.hip): the same contract, one chunk per block, blocks below KZ_CM_MAX_BLOCK (kz_cm_host.h).  The encoder
+// also writes d_flag[b]: 0 for a block whose stream does not fit its output row or its payload buffer (d_bits[b] = 0 then), the
+// caller fails that block
+int kz_stage_cm_encode(kz_ctx*, kz_batch&, uint8_t* out, int64_t outStride, const int32_t* d_hdrBytes, int64_t* d_bits);
+int kz_stage_cm_decode(kz_ctx*, kz_batch&, const uint8_t* in, int64_t inStride, const int64_t* d_bitOff, const int64_t* d_bitEnd);
+size_t kz_cm_scratch(int B, int maxN, bool decode);
 int kz_stage_huffman_encode(kz_ctx*, kz_batch&, uint8_t* out, int64_t outStride, const int32_t* d_hdrBytes, int64_t* d_bits);
 int kz_stage_huffman_decode(kz_ctx*, kz_batch&, const uint8_t* in, int64_t inStride, const int64_t* d_bitOff, const int64_t* d_bitEnd);
 
