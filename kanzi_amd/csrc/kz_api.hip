@@ -1009,6 +1009,15 @@ static void overlap_plan(kz_ctx* ctx, Overlap& O, const std::vector<int32_t>& zl
     for (int g = n - 1; g >= 0; g--) O.launchOrder.push_back(g);
     for (int g = 0; g < n; g++) O.bwtOrder.push_back(g);
     O.mainGroup = 0;
+    // The main stream runs the cheapest class's RANK inverse itself, behind the last preparation, and the BWT inverses behind that:
+    // its chain is what everything else waits for.  With the classes' own priorities (most expensive = highest) that chain ran
+    // under the two long ones at their pace and no BWT inverse could begin before all chains had ended (bulk batch, 2048 x 4 MiB,
+    // profiles/rankprio_parent_decode_timeline.txt: chains 270 / 282 / 275 ms, all over at 395 ms, then 283 ms of BWT inverses
+    // alone, 680 ms).  As in the wide schedule the class whose BWT inverse comes first now issues first and the long chains end
+    // under the BWT inverses (profiles/rankprio_new_decode_timeline.txt: cheap class 110 ms, over at 234 ms; skewed bytes 211,
+    // incompressible 464 ms, over at 468 ms = 6 ms before the last BWT inverse could start; 533 ms).
+    if ((int)zlen.size() > 4 * ctx->numCUs)
+      for (size_t i = 0; i < O.bwtOrder.size(); i++) O.groups[O.bwtOrder[i]].prio = i == 0 ? 2 : (i == 1 ? 1 : 0);
     return;
   }
   for (auto& G : O.groups) {
