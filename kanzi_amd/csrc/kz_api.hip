@@ -274,20 +274,79 @@ void kz_stage_end(kz_ctx* ctx, hipEvent_t e0, int stageId, int64_t algBytes) {
 
 // =================================================================================================
 // ids / sizes
-extern "C" int32_t kz_transform_max_encoded_len(uint32_t type, int32_t n) {
-  switch (type) {
-    case KZ_T_BWT: return n + 33;                                    // BWTBlockCodec.java:40,222
-    case KZ_T_SRT: return n + 1024;                                  // SRT.java:30,365
-    case KZ_T_LZ: case KZ_T_LZX: return ((n <= 1024) ? n + 16 : n + (n / 64)) + 2;   // LZCodec.java:961-964
-    case KZ_T_LZP: return (n <= 1024) ? n + 16 : n + (n / 64);       // LZCodec.java:1284-1286
-    case KZ_T_EXE: return (n <= 256) ? n + 32 : n + n / 8;           // EXECodec.java:655
-    case KZ_T_MM: return n + std::max(64, n >> 4);                   // FSDCodec.java:320-323
-    case KZ_T_PACK: case KZ_T_DNA: return n + 1024;                  // AliasCodec.java:472-475
-    case KZ_T_UTF: return n + 8192;                                  // UTFCodec.java:308-310
-    case KZ_T_RLT: return (n <= 512) ? n + 32 : n;                   // RLT.java:419-421
-    default: return n;                                               // ZRLT.java:243, SBRT.java:224
-  }
-}
+// The codec tables: what this file knows about a transform or an entropy coder is ONE row here; a new stage adds a row.
+static int bwt_group_blocks(int B, int maxLen);
+static int bwt_forward_grouped(kz_ctx* ctx, kz_batch& bt);
+#define LEN(expr) [](int n) -> int { return expr; }
+#define SCRATCH(expr) [](int B, int maxN, bool decode) -> size_t { return expr; }
+#define STAGE(fn, ...) [](kz_ctx* ctx, kz_batch& bt, int dstCap, int entropy) -> int { return fn(ctx, bt, ##__VA_ARGS__); }   // fn(ctx, bt, the mode arguments)
+#define TIMERS(X) KZ_STAGE_##X##_FWD, KZ_STAGE_##X##_INV
+struct TransformRow {
+  int id;                                             // KZ_T_*
+  int (*maxLen)(int n);                               // ByteTransform.getMaxEncodedLength
+  size_t (*scratch)(int B, int maxN, bool decode);    // arena bytes of the stage (null: none)
+  int (*forward)(kz_ctx*, kz_batch&, int dstCap, int entropy);   // null: no device entry point (NONE, the host stages)
+  int (*inverse)(kz_ctx*, kz_batch&, int dstCap, int entropy);
+  int timerFwd, timerInv;                             // KZ_STAGE_*; a stage without a timer of its own is counted under ZRLT's
+  bool host;                                          // TEXT, UTF: host stages; kz_is_host_transform (kz_text.hip, for the context-free kz_host_stage_* calls) names the same ids
+};
+static const TransformRow kTransforms[] = {
+  {KZ_T_NONE, LEN(n), nullptr, nullptr, nullptr, TIMERS(ZRLT)},   // NullTransform.java:107-109
+  {KZ_T_TEXT, LEN(n), nullptr, nullptr, nullptr, TIMERS(ZRLT), true},   // TextCodec.java:1033-1037
+  {KZ_T_UTF, LEN(n + 8192), nullptr, nullptr, nullptr, TIMERS(ZRLT), true},   // UTFCodec.java:308-310
+  {KZ_T_BWT, LEN(n + 33), SCRATCH(decode ? kz_bwt_inverse_scratch(B, maxN) : kz_bwt_forward_scratch(bwt_group_blocks(B, maxN), maxN)),
+   STAGE(bwt_forward_grouped), STAGE(kz_stage_bwt_inverse), TIMERS(BWT)},   // BWTBlockCodec.java:40,222
+  {KZ_T_RANK, LEN(n), SCRATCH(kz_sbrt_scratch(B, maxN)), STAGE(kz_stage_sbrt_forward, 2), STAGE(kz_stage_sbrt_inverse, 2), TIMERS(SBRT)},   // SBRT.java:224
+  {KZ_T_MTFT, LEN(n), SCRATCH(kz_sbrt_scratch(B, maxN)), STAGE(kz_stage_sbrt_forward, 1), STAGE(kz_stage_sbrt_inverse, 1), TIMERS(SBRT)},
+  {KZ_T_ZRLT, LEN(n), SCRATCH(kz_zrlt_scratch(B, maxN)), STAGE(kz_stage_zrlt_forward), STAGE(kz_stage_zrlt_inverse, dstCap), TIMERS(ZRLT)},   // ZRLT.java:243
+  {KZ_T_RLT, LEN((n <= 512) ? n + 32 : n), SCRATCH(kz_rlt_scratch(B, maxN) + (size_t)B * 4 + 256),   // RLT.java:419-421; + the per-block dst.length of the batched forward
+   STAGE(kz_stage_rlt_forward, entropy), STAGE(kz_stage_rlt_inverse, dstCap), TIMERS(ZRLT)},
+  {KZ_T_SRT, LEN(n + 1024), SCRATCH(decode ? 4096 : kz_srt_scratch(B, maxN)), STAGE(kz_stage_srt_forward), STAGE(kz_stage_srt_inverse), TIMERS(SRT)},   // SRT.java:30,365
+  {KZ_T_LZ, LEN(((n <= 1024) ? n + 16 : n + (n / 64)) + 2), SCRATCH(decode ? 4096 : kz_lz_scratch(B, maxN)),   // LZCodec.java:961-964
+   STAGE(kz_stage_lz_forward, 0), STAGE(kz_stage_lz_inverse, 0, dstCap), TIMERS(LZ)},
+  {KZ_T_LZX, LEN(((n <= 1024) ? n + 16 : n + (n / 64)) + 2), SCRATCH(decode ? 4096 : kz_lz_scratch(B, maxN)),
+   STAGE(kz_stage_lz_forward, 1), STAGE(kz_stage_lz_inverse, 1, dstCap), TIMERS(LZ)},
+  {KZ_T_LZP, LEN((n <= 1024) ? n + 16 : n + (n / 64)), SCRATCH(kz_lzp_scratch(B, maxN)),   // LZCodec.java:1284-1286; the hash table, in both directions
+   STAGE(kz_stage_lzp_forward), STAGE(kz_stage_lzp_inverse, dstCap), TIMERS(LZ)},
+  {KZ_T_EXE, LEN((n <= 256) ? n + 32 : n + n / 8), SCRATCH(kz_exe_scratch(B, maxN, decode)),   // EXECodec.java:653-656
+   STAGE(kz_stage_exe_forward), STAGE(kz_stage_exe_inverse, dstCap), TIMERS(ZRLT)},
+  {KZ_T_MM, LEN(n + std::max(64, n >> 4)), SCRATCH(kz_mm_scratch(B, maxN)), STAGE(kz_stage_mm_forward), STAGE(kz_stage_mm_inverse, dstCap), TIMERS(ZRLT)},   // FSDCodec.java:323-325
+  {KZ_T_PACK, LEN(n + 1024), SCRATCH(kz_alias_scratch(B, maxN, decode)),   // AliasCodec.java:445-447
+   STAGE(kz_stage_alias_forward, 0), STAGE(kz_stage_alias_inverse, dstCap), TIMERS(ZRLT)},
+  {KZ_T_DNA, LEN(n + 1024), SCRATCH(kz_alias_scratch(B, maxN, decode)),   // PACK with onlyDNA, TransformFactory.java:341-343
+   STAGE(kz_stage_alias_forward, 1), STAGE(kz_stage_alias_inverse, dstCap), TIMERS(ZRLT)},
+};
+static const TransformRow* transform_row(int t) { for (const TransformRow& r : kTransforms) if (r.id == t) return &r; return nullptr; }
+static bool host_stage(int t) { const TransformRow* r = transform_row(t); return r && r->host; }
+extern "C" int32_t kz_transform_max_encoded_len(uint32_t type, int32_t n) { const TransformRow* r = transform_row((int)type); return r ? r->maxLen(n) : n; }
+static int64_t ans1_max_stream_bytes(int n) { return (int64_t)kz_align((size_t)n + (size_t)(n >> 3) + 1024 + 102400 * ((size_t)n / (1 << 22) + 1), 256); }
+struct EntropyRow {
+  int id;                                             // KZ_E_*
+  int (*encode)(kz_ctx*, kz_batch&, uint8_t* out, int64_t outStride, const int32_t* d_hdrBytes, int64_t* d_bits);   // null: NONE, the bytes as they are
+  int (*decode)(kz_ctx*, kz_batch&, const uint8_t* in, int64_t inStride, const int64_t* d_bitOff, const int64_t* d_bitEnd);
+  size_t (*scratch)(int B, int maxN, bool decode);    // arena bytes of the stage (null: none)
+  int64_t (*streamBytes)(int n);                      // bound of a single block's stream (kz_entropy_encode's buffer)
+  const char* overflow;                               // set: the encoder writes d_flag[b] = 0 for a block that outgrew its buffer, which fails; the text is kz_entropy_encode's
+  bool flushEmpty;                                    // encode + dispose of an empty input still writes the 56-bit flush
+  int blockLimit;                                     // blocks of this many bytes and more are refused (0: no limit; CM alone has one, and the two error texts beside the checks are CM's)
+  bool fast;                                          // the reference's fast coders: TextCodec2, no escape search in RLT (TransformFactory.java:275-286, RLT.java:101-108)
+};
+static size_t ans0_scratch(int B, int maxN, bool decode) { return decode ? (size_t)B * ((size_t)(maxN / 16384 + 4) * 8 + 64) + 65536 : kz_ans_scratch(B, maxN); }   // and HUFFMAN: 16 KiB chunks
+static const EntropyRow kEntropies[] = {
+  {KZ_E_NONE, nullptr, nullptr, nullptr, kz_max_block_stream_bytes, nullptr, false, 0, true},
+  {KZ_E_HUFFMAN, kz_stage_huffman_encode, kz_stage_huffman_decode, ans0_scratch, kz_max_block_stream_bytes, nullptr, false, 0, true},
+  {KZ_E_FPAQ, kz_stage_fpaq_encode, kz_stage_fpaq_decode, SCRATCH(decode ? 4096 : kz_fpaq_scratch(B, maxN)), kz_max_block_stream_bytes, nullptr, true, 0, false},
+  {KZ_E_RANGE, kz_stage_range_encode, kz_stage_range_decode, kz_range_scratch, kz_range_max_stream_bytes, "range encode: a chunk's payload does not fit its buffer", false, 0, true},
+  {KZ_E_ANS0, kz_stage_ans0_encode, kz_stage_ans0_decode, ans0_scratch, kz_max_block_stream_bytes, nullptr, false, 0, true},
+  {KZ_E_CM, kz_stage_cm_encode, kz_stage_cm_decode, kz_cm_scratch, kz_max_block_stream_bytes, "cm encode: the block's stream does not fit its buffer", true, KZ_CM_MAX_BLOCK, false},
+  {KZ_E_ANS1, kz_stage_ans1_encode, kz_stage_ans1_decode, kz_ans1_scratch, ans1_max_stream_bytes, nullptr, false, 0, false},
+};
+static const EntropyRow* entropy_row(uint32_t e) { for (const EntropyRow& r : kEntropies) if ((uint32_t)r.id == e) return &r; return nullptr; }
+#undef LEN
+#undef SCRATCH
+#undef STAGE
+#undef TIMERS
+bool kz_fast_coder(int entropyType) { const EntropyRow* r = entropy_row((uint32_t)entropyType); return r && r->fast; }
 extern "C" uint64_t kz_transform_type(const int32_t* types, int32_t nb) {   // TransformFactory.java:132-158
   uint64_t t = 0;
   for (int i = 0; i < 8; i++) t = (t << 6) | (uint64_t)((i < nb) ? (types[i] & 0x3F) : 0);
@@ -301,11 +360,6 @@ static int split_types(uint64_t tt, int* types) {                    // Transfor
   for (int i = 0; i < nbtr; i++) { int t = (int)((tt >> (42 - 6 * i)) & 0x3F); if (t != KZ_T_NONE || i == 0) types[k++] = t; }
   return k;
 }
-static bool transform_supported(int t) { return t == KZ_T_NONE || t == KZ_T_TEXT || t == KZ_T_UTF || t == KZ_T_BWT || t == KZ_T_RANK || t == KZ_T_MTFT || t == KZ_T_ZRLT || t == KZ_T_RLT || t == KZ_T_SRT || t == KZ_T_LZ || t == KZ_T_LZX || t == KZ_T_LZP || t == KZ_T_EXE || t == KZ_T_MM || t == KZ_T_PACK || t == KZ_T_DNA; }
-static bool entropy_supported(int e) { return e == KZ_E_NONE || e == KZ_E_ANS0 || e == KZ_E_ANS1 || e == KZ_E_HUFFMAN || e == KZ_E_FPAQ || e == KZ_E_RANGE || e == KZ_E_CM; }
-// TEXT is TextCodec2 under NONE / ANS0 / HUFFMAN / RANGE and TextCodec1 under every other coder (TransformFactory.java:275-286)
-static bool text_codec1(int e) { return !(e == KZ_E_NONE || e == KZ_E_ANS0 || e == KZ_E_HUFFMAN || e == KZ_E_RANGE); }
-int64_t kz_ans1_max_stream_bytes(int n) { return (int64_t)kz_align((size_t)n + (size_t)(n >> 3) + 1024 + 102400 * ((size_t)n / (1 << 22) + 1), 256); }
 static int seq_max_len(const int* types, int nb, int n) {             // Sequence.java:215-226
   int req = n;
   for (int i = 0; i < nb; i++) req = std::max(req, kz_transform_max_encoded_len((uint32_t)types[i], req));
@@ -514,32 +568,9 @@ static int bwt_group_blocks(int B, int maxLen) {
   return (B + groups - 1) / groups;                                  // seventh group of TWO blocks paying every round's launches
 }
 static size_t pipeline_scratch(int B, int maxLen, bool decode, const ChainSpec& C) {
-  size_t s = 65536;
-  for (int i = 0; i < C.nb; i++) {
-    switch (C.types[i]) {
-      case KZ_T_BWT: s += decode ? kz_bwt_inverse_scratch(B, maxLen) : kz_bwt_forward_scratch(bwt_group_blocks(B, maxLen), maxLen); break;
-      case KZ_T_RANK: case KZ_T_MTFT: s += kz_sbrt_scratch(B, maxLen); break;
-      case KZ_T_ZRLT: s += kz_zrlt_scratch(B, maxLen); break;
-      case KZ_T_RLT: s += kz_rlt_scratch(B, maxLen) + (size_t)B * 4 + 256; break;     // + the per-block dst.length of the batched forward
-      case KZ_T_SRT: s += decode ? 4096 : kz_srt_scratch(B, maxLen); break;
-      case KZ_T_LZ: case KZ_T_LZX: s += decode ? 4096 : kz_lz_scratch(B, maxLen); break;
-      case KZ_T_LZP: s += kz_lzp_scratch(B, maxLen); break;                          // the hash table, in both directions
-      case KZ_T_EXE: s += kz_exe_scratch(B, maxLen, decode); break;
-      case KZ_T_MM: s += kz_mm_scratch(B, maxLen); break;
-      case KZ_T_PACK: case KZ_T_DNA: s += kz_alias_scratch(B, maxLen, decode); break;
-      default: break;
-    }
-  }
-  if (C.entropy == KZ_E_ANS0 || C.entropy == KZ_E_HUFFMAN)
-    s += decode ? (size_t)B * ((size_t)(maxLen / 16384 + 4) * 8 + 64) + 65536 : kz_ans_scratch(B, maxLen);
-  else if (C.entropy == KZ_E_ANS1)
-    s += kz_ans1_scratch(B, maxLen, decode);
-  else if (C.entropy == KZ_E_FPAQ)
-    s += decode ? 4096 : kz_fpaq_scratch(B, maxLen);
-  else if (C.entropy == KZ_E_RANGE)
-    s += kz_range_scratch(B, maxLen, decode);
-  else if (C.entropy == KZ_E_CM)
-    s += kz_cm_scratch(B, maxLen, decode);
+  const EntropyRow* E = entropy_row((uint32_t)C.entropy);
+  size_t s = 65536 + (E && E->scratch ? E->scratch(B, maxLen, decode) : 0);
+  for (int i = 0; i < C.nb; i++) if (const TransformRow* r = transform_row(C.types[i])) if (r->scratch) s += r->scratch(B, maxLen, decode);
   return s;
 }
 
@@ -590,32 +621,12 @@ static int bwt_forward_grouped(kz_ctx* ctx, kz_batch& bt) {
 }
 
 static int run_transform_stage(kz_ctx* ctx, kz_batch& bt, int type, bool forward, int dstCap, int entropy) {
-  switch (type) {
-    case KZ_T_BWT: return forward ? bwt_forward_grouped(ctx, bt) : kz_stage_bwt_inverse(ctx, bt);
-    case KZ_T_RANK: return forward ? kz_stage_sbrt_forward(ctx, bt, 2) : kz_stage_sbrt_inverse(ctx, bt, 2);
-    case KZ_T_MTFT: return forward ? kz_stage_sbrt_forward(ctx, bt, 1) : kz_stage_sbrt_inverse(ctx, bt, 1);
-    case KZ_T_ZRLT: return forward ? kz_stage_zrlt_forward(ctx, bt) : kz_stage_zrlt_inverse(ctx, bt, dstCap);
-    case KZ_T_RLT: return forward ? kz_stage_rlt_forward(ctx, bt, entropy) : kz_stage_rlt_inverse(ctx, bt, dstCap);
-    case KZ_T_SRT: return forward ? kz_stage_srt_forward(ctx, bt) : kz_stage_srt_inverse(ctx, bt);
-    case KZ_T_LZ: return forward ? kz_stage_lz_forward(ctx, bt, 0) : kz_stage_lz_inverse(ctx, bt, 0, dstCap);
-    case KZ_T_LZX: return forward ? kz_stage_lz_forward(ctx, bt, 1) : kz_stage_lz_inverse(ctx, bt, 1, dstCap);
-    case KZ_T_LZP: return forward ? kz_stage_lzp_forward(ctx, bt) : kz_stage_lzp_inverse(ctx, bt, dstCap);
-    case KZ_T_EXE: return forward ? kz_stage_exe_forward(ctx, bt) : kz_stage_exe_inverse(ctx, bt, dstCap);
-    case KZ_T_MM: return forward ? kz_stage_mm_forward(ctx, bt) : kz_stage_mm_inverse(ctx, bt, dstCap);
-    case KZ_T_PACK: return forward ? kz_stage_alias_forward(ctx, bt, 0) : kz_stage_alias_inverse(ctx, bt, dstCap);
-    case KZ_T_DNA: return forward ? kz_stage_alias_forward(ctx, bt, 1) : kz_stage_alias_inverse(ctx, bt, dstCap);   // TransformFactory.java:341-343
-    default: snprintf(ctx->err, sizeof(ctx->err), "transform %d has no HIP stage", type); return -KZ_ERR_INVALID_CODEC;
-  }
+  const TransformRow* r = transform_row(type);
+  if (!r || !r->forward) { snprintf(ctx->err, sizeof(ctx->err), "transform %d has no HIP stage", type); return -KZ_ERR_INVALID_CODEC; }
+  return (forward ? r->forward : r->inverse)(ctx, bt, dstCap, entropy);
 }
-static int stage_id(int type, bool forward) {
-  switch (type) {
-    case KZ_T_BWT: return forward ? KZ_STAGE_BWT_FWD : KZ_STAGE_BWT_INV;
-    case KZ_T_RANK: case KZ_T_MTFT: return forward ? KZ_STAGE_SBRT_FWD : KZ_STAGE_SBRT_INV;
-    case KZ_T_SRT: return forward ? KZ_STAGE_SRT_FWD : KZ_STAGE_SRT_INV;
-    case KZ_T_LZ: case KZ_T_LZX: case KZ_T_LZP: return forward ? KZ_STAGE_LZ_FWD : KZ_STAGE_LZ_INV;
-    default: return forward ? KZ_STAGE_ZRLT_FWD : KZ_STAGE_ZRLT_INV;
-  }
-}
+static int stage_id(int type, bool forward) {                       // an id without a row: NONE's timers
+  const TransformRow* r = transform_row(type) ? transform_row(type) : kTransforms; return forward ? r->timerFwd : r->timerInv; }
 
 // =================================================================================================
 // host (CPU) stages: TEXT and UTF lead the chains of the reference's levels 3, 5 and 6.  They are sequential dictionary coders
@@ -623,9 +634,9 @@ static int stage_id(int type, bool forward) {
 // them when decoding, and carry their skip flags and the block's "dataType" entry through like Sequence does.
 static int host_prefix(kz_ctx* ctx, const int* types, int nb) {          // number of leading host stages, or <0
   int hp = 0;
-  while (hp < nb && kz_is_host_transform(types[hp])) hp++;
+  while (hp < nb && host_stage(types[hp])) hp++;
   for (int i = hp; i < nb; i++)
-    if (kz_is_host_transform(types[i])) {
+    if (host_stage(types[i])) {
       snprintf(ctx->err, sizeof(ctx->err), "TEXT / UTF are built as host stages in front of the GPU stages only (as in the reference's levels)");
       return -KZ_ERR_INVALID_CODEC;
     }
@@ -729,7 +740,7 @@ HostPre* kz_host_prestage(kz_ctx* ctx, uint64_t transformType, uint32_t entropyT
   int types[8];
   const int nb = split_types(transformType, types);
   int hp = 0;
-  while (hp < nb && kz_is_host_transform(types[hp])) hp++;
+  while (hp < nb && host_stage(types[hp])) hp++;
   if (hp == 0 || ctx->skipBlocks || nBlocks <= 0) return nullptr;   // ("skipBlocks": the copy decision comes from the device first)
   int maxN = 0;
   for (int b = 0; b < nBlocks; b++) maxN = std::max(maxN, lengths[b]);
@@ -856,16 +867,15 @@ __global__ void k_gather_group(const int32_t* __restrict__ in, const int32_t* __
 // 0 = host stage only; 1 = row form, three waves; 2 = serial token walk (both codecs); 3 = row form, one wave (1-3: any batch).
 static int text_gpu_form(const kz_ctx* ctx, uint32_t entropyType, int nBlocks) {
   if (ctx->sw.textGpu >= 0) return ctx->sw.textGpu;
-  return (text_codec1((int)entropyType) || nBlocks < ctx->sw.textGpuMin) ? 0 : 1;
+  return (!kz_fast_coder((int)entropyType) || nBlocks < ctx->sw.textGpuMin) ? 0 : 1;
 }
 static bool text_gpu_on(const kz_ctx* ctx, uint32_t entropyType, int nBlocks) { return text_gpu_form(ctx, entropyType, nBlocks) != 0; }
-// TEXT forward on the device (kz_text_fwd_gpu.hip): TextCodec2 streams (every entropy coder but FPAQ) in batches of KZ_TEXT_FWD_GPU_MIN
+// TEXT forward on the device (kz_text_fwd_gpu.hip): TextCodec2 streams under NONE / ANS0 / HUFFMAN (not RANGE) in batches of KZ_TEXT_FWD_GPU_MIN
 // blocks (256) or more -- a block's dictionary walk takes the kernel ~0.1 s however few there are, so small batches stay on the host's
 // chunk pipeline (measured with 16 host CPUs, level-exact -l 5 encode of 64 / 128 / 256 / 512 blocks: host 102 / 159 / 293 / 529 ms,
 // device 157 / 188 / 247 / 379 ms).  KZ_TEXT_FWD_GPU=0: host stage, =1: any batch size.  (Read per call: the tests force both.)
 static bool text_fwd_gpu_on(const kz_ctx* ctx, uint32_t entropyType, int nBlocks) {
-  const bool type2 = entropyType == KZ_E_NONE || entropyType == KZ_E_ANS0 || entropyType == KZ_E_HUFFMAN;
-  if (!type2) return false;
+  if (!kz_fast_coder((int)entropyType) || entropyType == KZ_E_RANGE) return false;   // RANGE chains: never measured there
   if (ctx->sw.textFwdGpu >= 0) return ctx->sw.textFwdGpu == 1;
   return nBlocks >= ctx->sw.textFwdGpuMin;
 }
@@ -1180,7 +1190,7 @@ bool kz_text_fwd_gpu_applies(kz_ctx* ctx, uint64_t transformType, uint32_t entro
   int types[8];
   const int nb = split_types(transformType, types);
   int hp = 0;
-  while (hp < nb && kz_is_host_transform(types[hp])) hp++;
+  while (hp < nb && host_stage(types[hp])) hp++;
   return hp > 0 && !ctx->skipBlocks && types[0] == KZ_T_TEXT && (hp == 1 || types[1] == KZ_T_UTF) && text_fwd_gpu_on(ctx, entropyType, nBlocks);
 }
 
@@ -1212,8 +1222,8 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
   KZ_HIP(hipSetDevice(ctx->device));
   int types[8];
   const int nb = split_types(transformType, types);
-  for (int i = 0; i < nb; i++) if (!transform_supported(types[i])) { snprintf(ctx->err, sizeof(ctx->err), "unsupported transform id %d", types[i]); return -KZ_ERR_INVALID_CODEC; }
-  if (!entropy_supported((int)entropyType)) { snprintf(ctx->err, sizeof(ctx->err), "unsupported entropy id %u", entropyType); return -KZ_ERR_INVALID_CODEC; }
+  for (int i = 0; i < nb; i++) if (!transform_row(types[i])) { snprintf(ctx->err, sizeof(ctx->err), "unsupported transform id %d", types[i]); return -KZ_ERR_INVALID_CODEC; }
+  const EntropyRow* E = entropy_row(entropyType); if (!E) { snprintf(ctx->err, sizeof(ctx->err), "unsupported entropy id %u", entropyType); return -KZ_ERR_INVALID_CODEC; }
   const int B = nBlocks;
   const int hp = host_prefix(ctx, types, nb);
   if (hp < 0) return hp;
@@ -1534,7 +1544,7 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
     hipEvent_t e0; kz_stage_begin(ctx, &e0);
     int64_t inBytes = 0; for (int b = 0; b < B; b++) inBytes += bt.h_len[b];
     // copy blocks and NONE entropy: raw bytes (NullEntropyEncoder.java:66-81)
-    if (entropyType == KZ_E_ANS0 || entropyType == KZ_E_ANS1 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_FPAQ || entropyType == KZ_E_RANGE || entropyType == KZ_E_CM) {
+    if (E->encode) {
       // small copy blocks use NONE: mask them out of the ANS stage by zero length, then copy raw
       for (int b = 0; b < B; b++) h_mask[b] = h_copy[b] ? 0 : 1;
       KZ_HIP(hipMemcpyAsync(P.d_mask, h_mask.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
@@ -1542,14 +1552,9 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
       KZ_LAUNCH(ctx, KID_MASK_LEN, k_mask_len, dim3((B + 255) / 256), dim3(256), P.d_lenSave, P.d_mask, bt.d_len, B);
       std::vector<int32_t> saved = bt.h_len;
       for (int b = 0; b < B; b++) if (h_copy[b]) bt.h_len[b] = 0;
-      rc = (entropyType == KZ_E_ANS0) ? kz_stage_ans0_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
-         : (entropyType == KZ_E_ANS1) ? kz_stage_ans1_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
-         : (entropyType == KZ_E_HUFFMAN) ? kz_stage_huffman_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
-         : (entropyType == KZ_E_RANGE) ? kz_stage_range_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
-         : (entropyType == KZ_E_CM) ? kz_stage_cm_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits)
-                                         : kz_stage_fpaq_encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits);
+      rc = E->encode(ctx, bt, d_out, outStride, F.hdrBytes, F.bits);
       if (rc) return rc;
-      if (entropyType == KZ_E_RANGE || entropyType == KZ_E_CM) {        // a chunk that outgrew its payload buffer (kz_range.hip), a stream that outgrew its row (kz_cm.hip): the block fails
+      if (E->overflow) {                                            // a block that outgrew its buffer fails
         std::vector<int32_t> ok(B);
         KZ_HIP(hipMemcpyAsync(ok.data(), bt.d_flag, (size_t)B * 4, hipMemcpyDeviceToHost, st));
         KZ_HIP(kz_stream_sync(ctx, st));
@@ -1693,8 +1698,8 @@ static int32_t decode_blocks_impl(kz_ctx* ctx, uint64_t transformType, uint32_t 
   KZ_HIP(hipSetDevice(ctx->device));
   int types[8];
   const int nb = split_types(transformType, types);
-  for (int i = 0; i < nb; i++) if (!transform_supported(types[i])) { snprintf(ctx->err, sizeof(ctx->err), "unsupported transform id %d", types[i]); return -KZ_ERR_INVALID_CODEC; }
-  if (!entropy_supported((int)entropyType)) { snprintf(ctx->err, sizeof(ctx->err), "unsupported entropy id %u", entropyType); return -KZ_ERR_INVALID_CODEC; }
+  for (int i = 0; i < nb; i++) if (!transform_row(types[i])) { snprintf(ctx->err, sizeof(ctx->err), "unsupported transform id %d", types[i]); return -KZ_ERR_INVALID_CODEC; }
+  const EntropyRow* E = entropy_row(entropyType); if (!E) { snprintf(ctx->err, sizeof(ctx->err), "unsupported entropy id %u", entropyType); return -KZ_ERR_INVALID_CODEC; }
   const int B = nBlocks;
   const int hp = host_prefix(ctx, types, nb);
   if (hp < 0) return hp;
@@ -1792,15 +1797,9 @@ static int32_t decode_blocks_impl(kz_ctx* ctx, uint64_t transformType, uint32_t 
       if (in) outBytes += bt.h_len[b];
       h_rawp[b] = (in && (entropyType == KZ_E_NONE || h_raw[b] || h_tc[b])) ? 1 : 0;
     }
-    if (entropyType == KZ_E_ANS0 || entropyType == KZ_E_ANS1 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_FPAQ || entropyType == KZ_E_RANGE || entropyType == KZ_E_CM) {
+    if (E->decode) {
       for (int b = 0; b < B; b++) h_mask[b] = ((!part || (*part)[b]) && !(h_raw[b] || h_tc[b])) ? 1 : 0;
-      int r = run_stage(ctx, P, h_mask, h_applied, [&](kz_batch& x) {
-        return (entropyType == KZ_E_ANS0) ? kz_stage_ans0_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
-             : (entropyType == KZ_E_ANS1) ? kz_stage_ans1_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
-             : (entropyType == KZ_E_HUFFMAN) ? kz_stage_huffman_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
-             : (entropyType == KZ_E_RANGE) ? kz_stage_range_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
-             : (entropyType == KZ_E_CM) ? kz_stage_cm_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd)
-                                             : kz_stage_fpaq_decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd); }, d_part);
+      int r = run_stage(ctx, P, h_mask, h_applied, [&](kz_batch& x) { return E->decode(ctx, x, d_in, inS, F.bitOff, F.bitEnd); }, d_part);
       if (r) return r;
       for (int b = 0; b < B; b++) if (h_mask[b] && !h_applied[b] && !h_status[b]) h_status[b] = -KZ_ERR_PROCESS_BLOCK;
     } else {
@@ -1928,7 +1927,7 @@ static int32_t decode_blocks_impl(kz_ctx* ctx, uint64_t transformType, uint32_t 
       take[b] = t ? 1 : 0;
     }
     hipEvent_t e0; kz_stage_begin(ctx, &e0);
-    rc = kz_stage_text_inverse_gpu(ctx, bt, blockSize, dataCap, text_codec1(entropyType), take, done, text_gpu_form(ctx, (uint32_t)entropyType, B));
+    rc = kz_stage_text_inverse_gpu(ctx, bt, blockSize, dataCap, !kz_fast_coder((int)entropyType), take, done, text_gpu_form(ctx, (uint32_t)entropyType, B));
     if (rc) return rc;
     kz_stage_end(ctx, e0, KZ_STAGE_HOST_INV, 0);
     for (int b = 0; b < B; b++) if (done[b]) h_skipHost[b] |= 0x80;
@@ -2005,7 +2004,7 @@ extern "C" int32_t kz_decode_blocks(kz_ctx* ctx, uint64_t transformType, uint32_
   int types[8];
   const int nb = split_types(transformType, types);
   int hp = 0;
-  while (hp < nb && kz_is_host_transform(types[hp])) hp++;
+  while (hp < nb && host_stage(types[hp])) hp++;
   const int CH = ctx->sw.hostChunkDec;
   // ---- chains led by TEXT / UTF on large batches: the host inverse stages of chunk k run on a helper thread (and the host pool)
   //      while the GPU decodes chunk k+1.  (Block checksums are verified on the device AFTER the host stages: that case takes the
@@ -2147,9 +2146,9 @@ static int32_t transform_one(kz_ctx* ctx, uint32_t type, bool forward, const uin
   if (!ctx || !src || !dst || !produced || n < 0) return -KZ_ERR_INVALID_PARAM;
   *produced = 0;
   if (n == 0) return 1;                                             // every reference codec: length 0 -> true
-  if (!transform_supported((int)type) || type == KZ_T_NONE) { snprintf(ctx->err, sizeof(ctx->err), "transform %u has no HIP stage", type); return -KZ_ERR_INVALID_CODEC; }
+  if (!transform_row((int)type) || type == KZ_T_NONE) { snprintf(ctx->err, sizeof(ctx->err), "transform %u has no HIP stage", type); return -KZ_ERR_INVALID_CODEC; }
   if (forward && dstCap < kz_transform_max_encoded_len(type, n)) return 0;   // e.g. ZRLT.java:68, BWTBlockCodec.java:84-86
-  if (kz_is_host_transform((int)type)) {                                     // TEXT, UTF: host stages, no GPU involved
+  if (host_stage((int)type)) {                                     // TEXT, UTF: host stages, no GPU involved
     int dt = ctx->dataType;
     const int r = forward ? kz_host_transform_forward((int)type, ctx->entropy, ctx->blockSize, &dt, src, n, dst, dstCap, produced)
                           : kz_host_transform_inverse((int)type, ctx->blockSize, src, n, dst, dstCap, produced);
@@ -2198,12 +2197,12 @@ extern "C" int32_t kz_transform_inverse(kz_ctx* ctx, uint32_t type, const uint8_
 
 extern "C" int64_t kz_entropy_encode(kz_ctx* ctx, uint32_t type, const uint8_t* src, int32_t n, uint8_t* out, int64_t outCapBytes) {
   if (!ctx || !src || !out || n < 0) return -KZ_ERR_INVALID_PARAM;
-  if (!entropy_supported((int)type)) return -KZ_ERR_INVALID_CODEC;
-  if (type == KZ_E_CM && n >= KZ_CM_MAX_BLOCK) { snprintf(ctx->err, sizeof(ctx->err), "cm encode: block of %d bytes: CM blocks go up to (1 << 26) - 1 bytes", n); return -KZ_ERR_INVALID_CODEC; }
+  const EntropyRow* E = entropy_row(type); if (!E) return -KZ_ERR_INVALID_CODEC;
+  if (E->blockLimit && n >= E->blockLimit) { snprintf(ctx->err, sizeof(ctx->err), "cm encode: block of %d bytes: CM blocks go up to (1 << 26) - 1 bytes", n); return -KZ_ERR_INVALID_CODEC; }
   if (n == 0) {
     // encode() of nothing writes nothing; FPAQ's dispose() still flushes its 56-bit low register, all zero but the
     // 24 padding ones (FPAQEncoder.java:232-238): the call stands for encode + dispose
-    if (type != KZ_E_FPAQ && type != KZ_E_CM) return 0;                  // (BinaryEntropyEncoder.java:250-255 for CM: the same tail)
+    if (!E->flushEmpty) return 0;                                        // (BinaryEntropyEncoder.java:250-255 for CM: the same tail)
     if (outCapBytes < 7) return -KZ_ERR_INVALID_PARAM;
     const uint8_t flush[7] = {0, 0, 0, 0, 0xFF, 0xFF, 0xFF};
     memcpy(out, flush, 7);
@@ -2211,7 +2210,7 @@ extern "C" int64_t kz_entropy_encode(kz_ctx* ctx, uint32_t type, const uint8_t* 
   }
   KZ_HIP(hipSetDevice(ctx->device));
   Pipe P;
-  const int64_t oS = (type == KZ_E_ANS1) ? kz_ans1_max_stream_bytes(n) : (type == KZ_E_RANGE) ? kz_range_max_stream_bytes(n) : kz_max_block_stream_bytes(n);
+  const int64_t oS = E->streamBytes(n);
   ChainSpec CS; CS.nb = 0; CS.entropy = (int)type;
   int rc = pipe_setup(ctx, P, 1, n, oS + 256, false, CS);
   if (rc) return rc;
@@ -2227,14 +2226,14 @@ extern "C" int64_t kz_entropy_encode(kz_ctx* ctx, uint32_t type, const uint8_t* 
   KZ_HIP(hipMemsetAsync(d_out, 0, (size_t)oS, st));
   KZ_HIP(hipMemsetAsync(d_hdr, 0, 64, st));
   int64_t bits = 0;
-  if (type == KZ_E_ANS0 || type == KZ_E_ANS1 || type == KZ_E_HUFFMAN || type == KZ_E_FPAQ || type == KZ_E_RANGE || type == KZ_E_CM) {
-    rc = (type == KZ_E_ANS0) ? kz_stage_ans0_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_ANS1) ? kz_stage_ans1_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_HUFFMAN) ? kz_stage_huffman_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_RANGE) ? kz_stage_range_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : (type == KZ_E_CM) ? kz_stage_cm_encode(ctx, bt, d_out, oS, d_hdr, d_bits) : kz_stage_fpaq_encode(ctx, bt, d_out, oS, d_hdr, d_bits);
+  if (E->encode) {
+    rc = E->encode(ctx, bt, d_out, oS, d_hdr, d_bits);
     if (rc) return rc;
-    if (type == KZ_E_RANGE || type == KZ_E_CM) {                        // the chunk outgrew its payload buffer (kz_range.hip), the stream its row (kz_cm.hip)
+    if (E->overflow) {
       int32_t ok = 1;
       KZ_HIP(hipMemcpyAsync(&ok, bt.d_flag, 4, hipMemcpyDeviceToHost, st));
       KZ_HIP(kz_stream_sync(ctx, st));
-      if (!ok) { snprintf(ctx->err, sizeof(ctx->err), type == KZ_E_CM ? "cm encode: the block's stream does not fit its buffer" : "range encode: a chunk's payload does not fit its buffer"); return -KZ_ERR_PROCESS_BLOCK; }
+      if (!ok) { snprintf(ctx->err, sizeof(ctx->err), "%s", E->overflow); return -KZ_ERR_PROCESS_BLOCK; }
     }
     KZ_HIP(hipMemcpyAsync(&bits, d_bits, 8, hipMemcpyDeviceToHost, st));
     KZ_HIP(kz_stream_sync(ctx, st));
@@ -2251,8 +2250,8 @@ extern "C" int64_t kz_entropy_encode(kz_ctx* ctx, uint32_t type, const uint8_t* 
 
 extern "C" int32_t kz_entropy_decode(kz_ctx* ctx, uint32_t type, const uint8_t* in, int64_t inBits, uint8_t* dst, int32_t count, int64_t* bitsConsumed) {
   if (!ctx || !in || !dst || count < 0) return -KZ_ERR_INVALID_PARAM;
-  if (!entropy_supported((int)type)) return -KZ_ERR_INVALID_CODEC;
-  if (type == KZ_E_CM && count >= KZ_CM_MAX_BLOCK) { snprintf(ctx->err, sizeof(ctx->err), "cm decode: block of %d bytes: CM blocks go up to (1 << 26) - 1 bytes", count); return -KZ_ERR_INVALID_CODEC; }
+  const EntropyRow* E = entropy_row(type); if (!E) return -KZ_ERR_INVALID_CODEC;
+  if (E->blockLimit && count >= E->blockLimit) { snprintf(ctx->err, sizeof(ctx->err), "cm decode: block of %d bytes: CM blocks go up to (1 << 26) - 1 bytes", count); return -KZ_ERR_INVALID_CODEC; }
   if (bitsConsumed) *bitsConsumed = 0;
   if (count == 0) return 0;
   KZ_HIP(hipSetDevice(ctx->device));
@@ -2273,9 +2272,9 @@ extern "C" int32_t kz_entropy_decode(kz_ctx* ctx, uint32_t type, const uint8_t* 
   KZ_HIP(hipMemcpyAsync(d_off, h, 16, hipMemcpyHostToDevice, st));
   bt.h_len[0] = count;
   KZ_HIP(hipMemcpyAsync(bt.d_len, &count, 4, hipMemcpyHostToDevice, st));
-  if (type == KZ_E_ANS0 || type == KZ_E_ANS1 || type == KZ_E_HUFFMAN || type == KZ_E_FPAQ || type == KZ_E_RANGE || type == KZ_E_CM) {
+  if (E->decode) {
     ctx->d_endBits = (long long*)(d_off + 2);
-    rc = (type == KZ_E_ANS0) ? kz_stage_ans0_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_ANS1) ? kz_stage_ans1_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_HUFFMAN) ? kz_stage_huffman_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_RANGE) ? kz_stage_range_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : (type == KZ_E_CM) ? kz_stage_cm_decode(ctx, bt, d_in, inS, d_off, d_off + 1) : kz_stage_fpaq_decode(ctx, bt, d_in, inS, d_off, d_off + 1);
+    rc = E->decode(ctx, bt, d_in, inS, d_off, d_off + 1);
     ctx->d_endBits = nullptr;
     if (rc) return rc;
     int32_t flag = 0;

@@ -14,8 +14,43 @@
 #include <thread>
 #include "../../include/kanzi_hip.h"
 
-enum KzKernelId { KID_ANS_ENC_CHUNK, KID_ANS_ENC_SCAN, KID_ANS_ENC_CONCAT, KID_ANS_DEC_INDEX, KID_ANS_DEC_CHUNK, KID_ANS_DEC_FIN, KID_MASK_LEN, KID_PASSTHROUGH, KID_FRAME_PREPARE, KID_COPY_BYTES, KID_FRAME_DECIDE, KID_FRAME_HEADER, KID_FRAME_PARSE, KID_COPY_PAYLOAD, KID_BWT_INIT, KID_RADIX_HIST, KID_RADIX_SCAN, KID_RADIX_SCATTER, KID_SEG_REDUCE, KID_SEG_SCAN, KID_SEG_APPLY, KID_LIVE_EMIT, KID_BWT_EMIT, KID_BWTI_PARSE, KID_BWTI_HIST, KID_BWTI_SCAN, KID_BWTI_SCATTER, KID_BWTI_WALK1, KID_BWTI_RESOLVE, KID_BWTI_COPY, KID_BWTI_LITERAL, KID_BWTI_FIN, KID_SBRT_LAST2, KID_SBRT_SCAN, KID_SBRT_REPLAY, KID_COPY_LEN, KID_SBRT_INVERSE, KID_ZRLT_F1, KID_ZRLT_F2, KID_ZRLT_F3, KID_ZRLT_FFIN, KID_ZRLT_I1, KID_ZRLT_I2, KID_ZRLT_I3, KID_ZRLT_IFIN, KID_RLT_F0, KID_RLT_FSCAN, KID_RLT_F1, KID_RLT_FSUM, KID_RLT_F3, KID_RLT_FTAIL, KID_RLT_I1, KID_RLT_ISCAN, KID_RLT_I2, KID_RLT_ISUM, KID_RLT_I3, KID_RLT_IFIN, KID_HUF_ENC_CHUNK, KID_HUF_DEC_INDEX, KID_HUF_DEC_CHUNK, KID_HUF_DEC_FIN, KID_FPAQ_ENC, KID_FPAQ_PACK, KID_FPAQ_DEC, KID_SRT_HIST, KID_SRT_PREP, KID_SRT_SCATTER, KID_SRT_INV, KID_LZ_FWD, KID_LZ_INV, KID_XXHASH, KID_BLOCK_MAGIC, KID_MM_ANALYZE, KID_MM_EMIT, KID_MM_CHECK, KID_MM_INV, KID_ALIAS_ANALYZE, KID_ALIAS_HIST1, KID_ALIAS_SELECT, KID_ALIAS_EMIT, KID_ALIAS_INV, KID_SKIP_DECIDE, KID_MSD_HIST, KID_MSD_SCAN, KID_MSD_SCATTER, KID_BUCKET_SORT, KID_BUCKET_COUNT, KID_BUCKET_COUNT_S, KID_TR_HIST16, KID_TR_ASSIGN, KID_TR_COUNT, KID_TR_SCATTER, KID_TR_SORT, KID_TEXT_INV, KID_UTF_INV, KID_TEXT_FWD, KID_TEXT_WALK, KID_UTF_FWD, KID_ANS1_HIST, KID_ANS1_NORM, KID_ANS1_HDR, KID_ANS1_ENC, KID_ANS1_DEC_INDEX, KID_ANS1_DEC_TABLE, KID_ANS1_DEC_CHUNK, KID_ANS1_DEC_FIN, KID_RANGE_ENC_CHUNK, KID_RANGE_ENC_FIN, KID_RANGE_DEC, KID_CM_ENC, KID_CM_DEC, KID_LZP_FWD, KID_LZP_INV, KID_EXE_SETUP, KID_EXE_MAP, KID_EXE_SCAN, KID_EXE_HIST, KID_EXE_DECIDE, KID_EXE_SIZE, KID_EXE_VERDICT, KID_EXE_EMIT, KID_COUNT };
-#define KZ_KERNEL_NAMES { "k_ans_enc_chunk", "k_ans_enc_scan", "k_ans_enc_concat", "k_ans_dec_index", "k_ans_dec_chunk", "k_ans_dec_fin", "k_mask_len", "k_passthrough", "k_frame_prepare", "k_copy_bytes", "k_frame_decide", "k_frame_header", "k_frame_parse", "k_copy_payload", "k_bwt_init", "k_radix_hist", "k_radix_scan", "k_radix_scatter", "k_seg_reduce", "k_seg_scan", "k_seg_apply", "k_live_emit", "k_bwt_emit", "k_bwti_parse", "k_bwti_hist", "k_bwti_scan", "k_bwti_scatter", "k_bwti_walk1", "k_bwti_resolve", "k_bwti_copy", "k_bwti_literal", "k_bwti_fin", "k_sbrt_last2", "k_sbrt_scan", "k_sbrt_replay", "k_copy_len", "k_sbrt_inverse", "k_zrlt_f1", "k_zrlt_f2", "k_zrlt_f3", "k_zrlt_ffin", "k_zrlt_i1", "k_zrlt_i2", "k_zrlt_i3", "k_zrlt_ifin", "k_rlt_f0", "k_rlt_fscan", "k_rlt_f1", "k_rlt_fsum", "k_rlt_f3", "k_rlt_ftail", "k_rlt_i1", "k_rlt_iscan", "k_rlt_i2", "k_rlt_isum", "k_rlt_i3", "k_rlt_ifin", "k_huf_enc_chunk", "k_huf_dec_index", "k_huf_dec_chunk", "k_huf_dec_fin", "k_fpaq_enc", "k_fpaq_pack", "k_fpaq_dec", "k_srt_hist", "k_srt_prep", "k_srt_scatter", "k_srt_inv", "k_lz_fwd", "k_lz_inv", "k_xxhash", "k_block_magic", "k_mm_analyze", "k_mm_emit", "k_mm_check", "k_mm_inv", "k_alias_analyze", "k_alias_hist1", "k_alias_select", "k_alias_emit", "k_alias_inv", "k_skip_decide", "k_msd_hist", "k_msd_scan", "k_msd_scatter", "k_bucket_sort", "k_bucket_count", "k_bucket_count_s", "k_tr_hist16", "k_tr_assign", "k_tr_count", "k_tr_scatter", "k_tr_sort", "k_text_inv", "k_utf_inv", "k_text_fwd", "k_text_walk", "k_utf_fwd", "k_ans1_hist", "k_ans1_norm", "k_ans1_hdr", "k_ans1_enc", "k_ans1_dec_index", "k_ans1_dec_table", "k_ans1_dec_chunk", "k_ans1_dec_fin", "k_range_enc_chunk", "k_range_enc_fin", "k_range_dec", "k_cm_enc", "k_cm_dec", "k_lzp_fwd", "k_lzp_inv", "k_exe_setup", "k_exe_map", "k_exe_scan", "k_exe_hist", "k_exe_decide", "k_exe_size", "k_exe_verdict", "k_exe_emit" }
+// every kernel once, in the order of its id: KzKernelId and the names that bench.py and tools/pmc_traffic.py key on come from this list
+#define KZ_KERNELS(X) \
+  X(KID_ANS_ENC_CHUNK, "k_ans_enc_chunk") X(KID_ANS_ENC_SCAN, "k_ans_enc_scan") X(KID_ANS_ENC_CONCAT, "k_ans_enc_concat") X(KID_ANS_DEC_INDEX, "k_ans_dec_index") \
+  X(KID_ANS_DEC_CHUNK, "k_ans_dec_chunk") X(KID_ANS_DEC_FIN, "k_ans_dec_fin") X(KID_MASK_LEN, "k_mask_len") X(KID_PASSTHROUGH, "k_passthrough") \
+  X(KID_FRAME_PREPARE, "k_frame_prepare") X(KID_COPY_BYTES, "k_copy_bytes") X(KID_FRAME_DECIDE, "k_frame_decide") X(KID_FRAME_HEADER, "k_frame_header") \
+  X(KID_FRAME_PARSE, "k_frame_parse") X(KID_COPY_PAYLOAD, "k_copy_payload") X(KID_BWT_INIT, "k_bwt_init") X(KID_RADIX_HIST, "k_radix_hist") \
+  X(KID_RADIX_SCAN, "k_radix_scan") X(KID_RADIX_SCATTER, "k_radix_scatter") X(KID_SEG_REDUCE, "k_seg_reduce") X(KID_SEG_SCAN, "k_seg_scan") \
+  X(KID_SEG_APPLY, "k_seg_apply") X(KID_LIVE_EMIT, "k_live_emit") X(KID_BWT_EMIT, "k_bwt_emit") X(KID_BWTI_PARSE, "k_bwti_parse") \
+  X(KID_BWTI_HIST, "k_bwti_hist") X(KID_BWTI_SCAN, "k_bwti_scan") X(KID_BWTI_SCATTER, "k_bwti_scatter") X(KID_BWTI_WALK1, "k_bwti_walk1") \
+  X(KID_BWTI_RESOLVE, "k_bwti_resolve") X(KID_BWTI_COPY, "k_bwti_copy") X(KID_BWTI_LITERAL, "k_bwti_literal") X(KID_BWTI_FIN, "k_bwti_fin") \
+  X(KID_SBRT_LAST2, "k_sbrt_last2") X(KID_SBRT_SCAN, "k_sbrt_scan") X(KID_SBRT_REPLAY, "k_sbrt_replay") X(KID_COPY_LEN, "k_copy_len") \
+  X(KID_SBRT_INVERSE, "k_sbrt_inverse") X(KID_ZRLT_F1, "k_zrlt_f1") X(KID_ZRLT_F2, "k_zrlt_f2") X(KID_ZRLT_F3, "k_zrlt_f3") \
+  X(KID_ZRLT_FFIN, "k_zrlt_ffin") X(KID_ZRLT_I1, "k_zrlt_i1") X(KID_ZRLT_I2, "k_zrlt_i2") X(KID_ZRLT_I3, "k_zrlt_i3") \
+  X(KID_ZRLT_IFIN, "k_zrlt_ifin") X(KID_RLT_F0, "k_rlt_f0") X(KID_RLT_FSCAN, "k_rlt_fscan") X(KID_RLT_F1, "k_rlt_f1") \
+  X(KID_RLT_FSUM, "k_rlt_fsum") X(KID_RLT_F3, "k_rlt_f3") X(KID_RLT_FTAIL, "k_rlt_ftail") X(KID_RLT_I1, "k_rlt_i1") \
+  X(KID_RLT_ISCAN, "k_rlt_iscan") X(KID_RLT_I2, "k_rlt_i2") X(KID_RLT_ISUM, "k_rlt_isum") X(KID_RLT_I3, "k_rlt_i3") \
+  X(KID_RLT_IFIN, "k_rlt_ifin") X(KID_HUF_ENC_CHUNK, "k_huf_enc_chunk") X(KID_HUF_DEC_INDEX, "k_huf_dec_index") X(KID_HUF_DEC_CHUNK, "k_huf_dec_chunk") \
+  X(KID_HUF_DEC_FIN, "k_huf_dec_fin") X(KID_FPAQ_ENC, "k_fpaq_enc") X(KID_FPAQ_PACK, "k_fpaq_pack") X(KID_FPAQ_DEC, "k_fpaq_dec") \
+  X(KID_SRT_HIST, "k_srt_hist") X(KID_SRT_PREP, "k_srt_prep") X(KID_SRT_SCATTER, "k_srt_scatter") X(KID_SRT_INV, "k_srt_inv") \
+  X(KID_LZ_FWD, "k_lz_fwd") X(KID_LZ_INV, "k_lz_inv") X(KID_XXHASH, "k_xxhash") X(KID_BLOCK_MAGIC, "k_block_magic") \
+  X(KID_MM_ANALYZE, "k_mm_analyze") X(KID_MM_EMIT, "k_mm_emit") X(KID_MM_CHECK, "k_mm_check") X(KID_MM_INV, "k_mm_inv") \
+  X(KID_ALIAS_ANALYZE, "k_alias_analyze") X(KID_ALIAS_HIST1, "k_alias_hist1") X(KID_ALIAS_SELECT, "k_alias_select") X(KID_ALIAS_EMIT, "k_alias_emit") \
+  X(KID_ALIAS_INV, "k_alias_inv") X(KID_SKIP_DECIDE, "k_skip_decide") X(KID_MSD_HIST, "k_msd_hist") X(KID_MSD_SCAN, "k_msd_scan") \
+  X(KID_MSD_SCATTER, "k_msd_scatter") X(KID_BUCKET_SORT, "k_bucket_sort") X(KID_BUCKET_COUNT, "k_bucket_count") X(KID_BUCKET_COUNT_S, "k_bucket_count_s") \
+  X(KID_TR_HIST16, "k_tr_hist16") X(KID_TR_ASSIGN, "k_tr_assign") X(KID_TR_COUNT, "k_tr_count") X(KID_TR_SCATTER, "k_tr_scatter") \
+  X(KID_TR_SORT, "k_tr_sort") X(KID_TEXT_INV, "k_text_inv") X(KID_UTF_INV, "k_utf_inv") X(KID_TEXT_FWD, "k_text_fwd") \
+  X(KID_TEXT_WALK, "k_text_walk") X(KID_UTF_FWD, "k_utf_fwd") X(KID_ANS1_HIST, "k_ans1_hist") X(KID_ANS1_NORM, "k_ans1_norm") \
+  X(KID_ANS1_HDR, "k_ans1_hdr") X(KID_ANS1_ENC, "k_ans1_enc") X(KID_ANS1_DEC_INDEX, "k_ans1_dec_index") X(KID_ANS1_DEC_TABLE, "k_ans1_dec_table") \
+  X(KID_ANS1_DEC_CHUNK, "k_ans1_dec_chunk") X(KID_ANS1_DEC_FIN, "k_ans1_dec_fin") X(KID_RANGE_ENC_CHUNK, "k_range_enc_chunk") X(KID_RANGE_ENC_FIN, "k_range_enc_fin") \
+  X(KID_RANGE_DEC, "k_range_dec") X(KID_CM_ENC, "k_cm_enc") X(KID_CM_DEC, "k_cm_dec") X(KID_LZP_FWD, "k_lzp_fwd") \
+  X(KID_LZP_INV, "k_lzp_inv") X(KID_EXE_SETUP, "k_exe_setup") X(KID_EXE_MAP, "k_exe_map") X(KID_EXE_SCAN, "k_exe_scan") \
+  X(KID_EXE_HIST, "k_exe_hist") X(KID_EXE_DECIDE, "k_exe_decide") X(KID_EXE_SIZE, "k_exe_size") X(KID_EXE_VERDICT, "k_exe_verdict") \
+  X(KID_EXE_EMIT, "k_exe_emit")
+#define KZ_KERNEL_ENUM(id, name) id,
+#define KZ_KERNEL_NAME(id, name) name,
+enum KzKernelId { KZ_KERNELS(KZ_KERNEL_ENUM) KID_COUNT };
+#define KZ_KERNEL_NAMES { KZ_KERNELS(KZ_KERNEL_NAME) }
 // Environment switches (diagnostics, A/B runs, the tests' forced schedules; none is needed for normal use).  Read ONCE, when the
 // context is created (kz_switches_read, kz_api.hip); kz_ctx_reload_switches re-reads them for a live context (tests, A/B tools).
 // Nothing on a call's path calls getenv.
@@ -206,7 +241,6 @@ int kz_stage_ans0_decode(kz_ctx*, kz_batch&, const uint8_t* in, int64_t inStride
 int kz_stage_ans1_encode(kz_ctx*, kz_batch&, uint8_t* out, int64_t outStride, const int32_t* d_hdrBytes, int64_t* d_bits);
 int kz_stage_ans1_decode(kz_ctx*, kz_batch&, const uint8_t* in, int64_t inStride, const int64_t* d_bitOff, const int64_t* d_bitEnd);
 size_t kz_ans1_scratch(int B, int maxN, bool decode);
-int64_t kz_ans1_max_stream_bytes(int n);   // a single block's ANS1 stream: headers of up to 256 contexts per chunk
 // order-0 range coder (kz_range.hip): the same contract, 32 KiB chunks.  The encoder also writes d_flag[b]: 0 for a block one of
 // whose chunks outgrew its payload buffer (d_bits[b] = 0 then), the caller fails that block
 int kz_stage_range_encode(kz_ctx*, kz_batch&, uint8_t* out, int64_t outStride, const int32_t* d_hdrBytes, int64_t* d_bits);
@@ -239,6 +273,7 @@ void kz_ktimer_flush(kz_ctx* ctx);     // call after the stream has been synchro
 
 // ---- host (CPU) stages in front of the GPU chain: TEXT and UTF (kz_text.hip) ----
 bool kz_is_host_transform(int type);
+bool kz_fast_coder(int entropyType);    // kz_api.hip: NONE / ANS0 / HUFFMAN / RANGE, the entropy table's flag
 int kz_host_block_data_type(const uint8_t* p, int n, int init);
 int kz_host_transform_forward(int type, int entropyType, int blockSize, int* dataType, const uint8_t* src, int n, uint8_t* dst, int dstCap, int* produced);
 int kz_host_transform_inverse(int type, int blockSize, const uint8_t* src, int n, uint8_t* dst, int dstCap, int* produced);

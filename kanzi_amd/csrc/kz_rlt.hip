@@ -716,7 +716,7 @@ int kz_stage_rlt_forward(kz_ctx* ctx, kz_batch& bt, int entropy) {
   int maxN = 0;
   for (int b = 0; b < B; b++) if (bt.h_len[b] > maxN) maxN = bt.h_len[b];
   // the escape is searched, and the block's type looked at, under every coder but these (:101-108)
-  const int findBest = !(entropy == KZ_E_NONE || entropy == KZ_E_ANS0 || entropy == KZ_E_HUFFMAN || entropy == KZ_E_RANGE);
+  const int findBest = !kz_fast_coder(entropy);
   RlScratch S;
   S.T = (maxN + RL_TILE - 1) / RL_TILE + 1;
   S.tLastB = (u32*)kz_arena_alloc(ctx, (size_t)B * S.T * 4);

@@ -771,7 +771,7 @@ int kz_host_transform_forward(int type, int entropyType, int blockSize, int* dat
   if (n == 0) return 1;
   if (type == KZ_T_TEXT) {
     if (n < kMinBlock || n > kMaxBlock) return 0;                                                     // TextCodec.forward :491-492
-    const bool type2 = entropyType == KZ_E_NONE || entropyType == KZ_E_ANS0 || entropyType == KZ_E_HUFFMAN || entropyType == KZ_E_RANGE;
+    const bool type2 = kz_fast_coder(entropyType);
     return text_forward(type2 ? 2 : 1, blockSize, dataType, src, n, dst, dstCap, produced);
   }
   if (type == KZ_T_UTF) return utf_forward(dataType, src, n, dst, dstCap, produced);

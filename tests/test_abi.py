@@ -30,12 +30,30 @@ def test_library_exports_every_declared_symbol(built):
 def test_max_encoded_len_matches_reference_values(built):
     L = kz.load_library()
     O = oracle.lib()
-    for n in (0, 1, 100, 1024, 1025, 65536, 4 * 1024 * 1024):
-        # BWT n+33 (BWTBlockCodec.java:40,222); SRT n+1024 (SRT.java:30,365); LZ/LZX (LZCodec.java:961-964); ZRLT/SBRT n
-        assert L.kz_transform_max_encoded_len(kz.BWT_TYPE, n) == n + 33
-        assert L.kz_transform_max_encoded_len(kz.SRT_TYPE, n) == n + 1024
-        assert L.kz_transform_max_encoded_len(kz.LZ_TYPE, n) == ((n + 16) if n <= 1024 else n + n // 64) + 2
-        assert L.kz_transform_max_encoded_len(kz.ZRLT_TYPE, n) == n
+    # getMaxEncodedLength of every transform the library accepts, as the reference writes it
+    want = {
+        "NONE": lambda n: n,                                              # NullTransform.java:107-109
+        "TEXT": lambda n: n,                                              # TextCodec.java:1033-1037, :1614-1618
+        "UTF": lambda n: n + 8192,                                        # UTFCodec.java:308-310
+        "BWT": lambda n: n + 33,                                          # BWTBlockCodec.java:40,222
+        "RANK": lambda n: n,                                              # SBRT.java:223-225
+        "MTFT": lambda n: n,
+        "ZRLT": lambda n: n,                                              # ZRLT.java:242-244
+        "RLT": lambda n: n + 32 if n <= 512 else n,                       # RLT.java:419-421
+        "SRT": lambda n: n + 1024,                                        # SRT.java:30,365
+        "LZ": lambda n: (n + 16 if n <= 1024 else n + n // 64) + 2,       # LZCodec.java:961-964
+        "LZX": lambda n: (n + 16 if n <= 1024 else n + n // 64) + 2,
+        "LZP": lambda n: n + 16 if n <= 1024 else n + n // 64,            # LZCodec.java:1284-1286
+        "EXE": lambda n: n + 32 if n <= 256 else n + n // 8,              # EXECodec.java:653-656
+        "MM": lambda n: n + max(64, n >> 4),                              # FSDCodec.java:323-325
+        "PACK": lambda n: n + 1024,                                       # AliasCodec.java:445-447
+        "DNA": lambda n: n + 1024,
+    }
+    assert sorted(want) == sorted(kz.TRANSFORM_IDS) and len(want) == 16
+    for n in (0, 1, 100, 256, 257, 512, 513, 1024, 1025, 65536, 4 * 1024 * 1024):
+        for name, f in want.items():
+            assert L.kz_transform_max_encoded_len(kz.TRANSFORM_IDS[name], n) == f(n), (name, n)
+        assert L.kz_transform_max_encoded_len(4, n) == n                  # an id the library does not accept
         for t in (kz.BWT_TYPE, kz.SRT_TYPE, kz.LZ_TYPE, kz.LZX_TYPE, kz.ZRLT_TYPE, kz.RANK_TYPE, kz.MTFT_TYPE):
             assert L.kz_transform_max_encoded_len(t, n) == O.kzo_transform_max_encoded_len(t, n)
 
