@@ -34,7 +34,8 @@ struct UtfFwd {
   u8* tileIn;               // [A][maxTiles] entry state of each tile
   int32_t* tileSum;         // [A][maxTiles] alias bytes of each tile, then their exclusive sums
   u32* table;               // [A][UF_TABLE] counters, then aliases
-  int32_t* info;            // [A][8]: 0 start, 1 adjust, 2 error / unsupported, 3 symbols, 4 verdict (1 go on, 2 declined, 0 host), 5 output length
+  int32_t* info;            // [A][8]: 0 start, 1 adjust, 2 error / unsupported, 3 symbols, 4 verdict (1 go on, 2 declined, 0 host), 5 output length,
+                            //         6 what word 2 held when k_uf_tiles ended (k_uf_pass<0> adds to word 2, so it tests this copy)
   int maxTiles;
 };
 
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(64) void k_uf_init(const u8* __restrict__ src, int6
     if (s[0] == 0xEF && s[1] == 0xBB && s[2] == 0xBF) start = 3;                                        // byte order mark (:106-110)
     else while (start < 4) { const u32 c = s[start]; const int ok = c < 0x80 ? 1 : (c < 0xC2 ? 0 : (c < 0xF5 ? 1 : 0)); if (ok) break; start++; }   // LEN_SEQ == 0 (:111-114)
   }
-  info[0] = start; info[1] = 0; info[2] = n < UF_MIN_BLOCK ? 2 : 0; info[3] = 0; info[4] = 0; info[5] = 0;
+  info[0] = start; info[1] = 0; info[2] = info[6] = n < UF_MIN_BLOCK ? 2 : 0; info[3] = 0; info[4] = 0; info[5] = 0;
 }
 
 __global__ __launch_bounds__(256) void k_uf_map(const u8* __restrict__ src, int64_t stride, const int32_t* __restrict__ d_len, UtfFwd G, int B) {
@@ -105,7 +106,7 @@ __global__ __launch_bounds__(256) void k_uf_map(const u8* __restrict__ src, int6
   const int n = d_len[b], t = blockIdx.x;
   if (t * UF_TILE >= n) return;
   const int32_t* info = G.info + (int64_t)a * 8;
-  if (info[2]) return;
+  if (info[2]) return;                                              // (written by k_uf_init, the launch before: one answer for the workgroup)
   const int start = info[0], body = n - 4;
   __shared__ u32 lds[8];
   const int pos0 = t * UF_TILE + (int)threadIdx.x * 16;
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(64) void k_uf_tiles(const int32_t* __restrict__ d_l
   const int a = G.ord[b];
   if (a < 0) return;
   int32_t* info = G.info + (int64_t)a * 8;
-  if (info[2]) return;
+  if (info[2]) return;                                              // (written by k_uf_init; this thread alone owns the block's words here)
   const int n = d_len[b], nt = (n + UF_TILE - 1) / UF_TILE;
   u32 s = 0, err = 0;
   for (int t = 0; t < nt; t++) {
@@ -131,7 +132,7 @@ __global__ __launch_bounds__(64) void k_uf_tiles(const int32_t* __restrict__ d_l
     err |= (f >> (8 + s)) & 1u;
     s = (f >> (2 * s)) & 3u;
   }
-  if (err) info[2] = 1;                                             // a byte that cannot start a code point where one must start: UTF declines
+  if (err) info[2] = info[6] = 1;                                   // a byte that cannot start a code point where one must start: UTF declines
 }
 
 // the table slot of the code point at p (u units): size tag << 16 | its 16 payload bits (= the low 16 bits of the reference's key, :436-455)
@@ -149,7 +150,10 @@ __global__ __launch_bounds__(256) void k_uf_pass(const u8* __restrict__ src, u8*
   const int n = d_len[b], t = blockIdx.x;
   if (t * UF_TILE >= n) return;
   int32_t* info = G.info + (int64_t)a * 8;
-  if (info[2] || (PASS > 0 && info[4] != 1)) return;
+  // One answer for the workgroup, from words an earlier launch finished: PASS 0 adds bits to info[2] itself (other tiles of the block,
+  // same launch), so it tests info[6], the copy k_uf_init / k_uf_tiles left; PASS 1 and 2 read info[2] after k_uf_pass<0> ended and
+  // info[4] after k_uf_syms (PASS 1) resp. k_uf_scan (PASS 2) ended.
+  if (PASS == 0 ? info[6] != 0 : (info[2] || info[4] != 1)) return;
   const int start = info[0], body = n - 4;
   __shared__ u32 lds[8];
   __shared__ u32 bins[256 + 2048];                                  // PASS 0: ASCII counters, two-unit counters (32 first units x 64 second units)
@@ -199,7 +203,7 @@ __global__ __launch_bounds__(256) void k_uf_pass(const u8* __restrict__ src, u8*
     }
   }
   if (PASS == 0) {
-    if (bad) info[2] = 1;
+    if (bad) atomicOr((int*)&info[2], 1);                           // (never a plain store: it would erase the four-unit bit)
     if (four) atomicOr((int*)&info[2], 2);
     __syncthreads();
     for (int i = threadIdx.x; i < 256 + 2048; i += 256) {
@@ -226,6 +230,7 @@ __global__ __launch_bounds__(1024) void k_uf_syms(u8* __restrict__ dst, int64_t 
   const int b = blockIdx.x, a = G.ord[b];
   if (a < 0) return;
   int32_t* info = G.info + (int64_t)a * 8;
+  // (info[2]: complete when k_uf_pass<0> ended; this workgroup alone writes the block's info[4])
   if (info[2]) { if (threadIdx.x == 0) info[4] = (info[2] & 1) ? 2 : 0; return; }       // error: UTF declines; four-unit code points: host stage
   const int n = d_len[b];
   __shared__ u64 key[UF_MAXSYM];
@@ -288,6 +293,8 @@ __global__ __launch_bounds__(256) void k_uf_scan(const u8* __restrict__ src, u8*
   const int b = blockIdx.x, a = G.ord[b];
   if (a < 0) return;
   int32_t* info = G.info + (int64_t)a * 8;
+  // written by k_uf_syms, the launch before last; thread 0 of this one workgroup per block changes it below, behind the barriers of
+  // kz_wg_excl_sum that every thread reaches after this read
   if (info[4] != 1) return;
   const int n = d_len[b];
   const int nt = (n + UF_TILE - 1) / UF_TILE;
