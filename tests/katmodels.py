@@ -566,11 +566,17 @@ def huffman_encode_exact(data):
     return bs.bytes(), bs.n
 
 
-def lz_decode(src, out_cap):
+def lz_decode(src, out_cap, events=None):
     """K/transform/LZCodec.java inverseV6 :617-756 + readLength :241-258, as a pure-Python reader of the LZ / LZX frame: three little-
     endian lengths (offset of the token stream = 13 + literal bytes, token bytes, match-index bytes; the match lengths fill the rest), a flag byte (bit 0: the 2^24 window, bits 1..3:
-    minMatch - 2), the literals, then the token, match-index and match-length streams.  Returns the decoded bytes or None."""
+    minMatch - 2), the literals, then the token, match-index and match-length streams.  Returns the decoded bytes or None.
+    events: a collections.Counter for the decoder-side trace (names in tests/lzcases.py); counting changes nothing else."""
     count = len(src)
+
+    def ev(name):
+        if events is not None:
+            events[name] += 1
+
     if count == 0:
         return b""
     if count < 13:
@@ -590,19 +596,24 @@ def lz_decode(src, out_cap):
     dst = bytearray()
     repd0 = repd1 = count
 
-    def read_length(p):
+    def read_length(p, stream):
         r = src[p]; p += 1
         if r < 254:
             return r, p
         if r == 254:
+            ev("inv_%s_code_3byte" % stream)
             return r + (src[p] << 8) + src[p + 1], p + 2
+        ev("inv_%s_code_4byte" % stream)
         return r + (src[p] << 16) + (src[p + 1] << 8) + src[p + 2], p + 3
 
+    tk0, mi0 = tk, mi
     while True:
+        if tk > tk0 and (tk - tk0) % 64 == 0:
+            ev("inv_token_idx_mult64")
         token = src[tk]; tk += 1
         if token >= 32:
             if token >= 0xE0:
-                n, pos = read_length(pos)
+                n, pos = read_length(pos, "lit")
                 lit = 7 + n
             else:
                 lit = token >> 5
@@ -616,7 +627,7 @@ def lz_decode(src, out_cap):
         if f == 0:
             mlen = token & 3
             if mlen == 3:
-                n, ml = read_length(ml)
+                n, ml = read_length(ml, "mlen")
                 mlen += min_match + n
             else:
                 mlen += min_match
@@ -624,10 +635,13 @@ def lz_decode(src, out_cap):
         else:
             mlen = token & 7
             if mlen == 7:
-                n, ml = read_length(ml)
+                n, ml = read_length(ml, "mlen")
                 mlen += min_match + n
             else:
                 mlen += min_match
+            nb = 3 if f == 0x18 else 2 if f == 0x10 else 1
+            if nb > 1 and (mi - mi0) // 64 != (mi - mi0 + nb - 1) // 64:
+                ev("inv_dist%d_straddle64" % nb)
             dist = src[mi]; mi += 1
             if f == 0x18:
                 dist = (dist << 16) | (src[mi] << 8) | src[mi + 1]; mi += 2
@@ -637,6 +651,7 @@ def lz_decode(src, out_cap):
         ref = len(dst) - dist
         if ref < 0 or dist > max_dist or len(dst) + mlen > out_cap:
             return None
+        ev("inv_copy_%s_%s" % ("near" if dist < 64 else "far", "short" if mlen <= 64 else "long"))
         for i in range(mlen):
             dst.append(dst[ref + i])
     return bytes(dst) if pos == tk_len else None
@@ -678,16 +693,30 @@ class _JavaBytes(list):
         list.__setitem__(self, i, v & 0xFF)
 
 
-def lz_forward(data, extra=False, data_type="UNDEFINED"):
+LZ_MUTANTS = ("bwd_cap7", "bwd_ignore_anchor", "minref_ge", "no_clamp", "stale_lit_store", "lazy_early_read", "fill_lowest_wins", "fm_round_up")
+
+
+def lz_forward(data, extra=False, data_type="UNDEFINED", events=None, mutate=None):
     """K/transform/LZCodec.java LZXCodec.forward :299-597 (LZ: extra = false, 2^16 hash entries; LZX: extra = true, 2^19 entries and the
     second lazy probe), hash :904-911, findMatch :271-287, emitLength :211-231, differentInts :134-137.  data_type = the context's
-    "dataType" entry (:343-352).  Returns (applied, bytes); raises JavaException where the reference's fixed tkBuf / mLenBuf overflow."""
+    "dataType" entry (:343-352).  Returns (applied, bytes); raises JavaException where the reference's fixed tkBuf / mLenBuf overflow.
+
+    events: a collections.Counter that receives the trace of the parse (tests/lzcases.py lists the names and what each one means);
+    counting changes nothing else.  mutate: one of LZ_MUTANTS, a one-line departure from the reference that mirrors a shortcut of
+    kanzi_amd/csrc/kz_lz.hip going wrong; tests/test_lz_cases.py asserts that the case set tells each of them from the reference."""
+    assert mutate is None or mutate in LZ_MUTANTS, mutate
     src = bytes(data)
     count = len(src)
+
+    def ev(name):
+        if events is not None:
+            events[name] += 1
+
     if count == 0:
         return True, b""
     max_enc = (count + 16 if count <= 1024 else count + count // 64) + 2          # getMaxEncodedLength :961-964 (the caller provides it)
     if count < 24:                                                                # MIN_BLOCK_LENGTH :312
+        ev("count_lt_24")
         return False, b""
     SEED, MAXD1, MAXD2, MAX_MATCH = 0x1E35A7BD, (1 << 16) - 2, (1 << 24) - 2, 65535 + 254 + 4
     log = 19 if extra else 16
@@ -706,17 +735,26 @@ def lz_forward(data, extra=False, data_type="UNDEFINED"):
 
     def find_match(s, r, max_match):                                              # :271-287 (8 bytes at a time, stops below max_match - 7)
         best = 0
-        while best + 8 <= max_match:
+        cut = True
+        while (best < max_match) if mutate == "fm_round_up" else (best + 8 <= max_match):
             x = int.from_bytes(pad[s + best:s + best + 8], "little") ^ int.from_bytes(pad[r + best:r + best + 8], "little")
             if x:
                 best += ((x & -x).bit_length() - 1) >> 3
+                cut = False
                 break
             best += 8
+        if events is not None:
+            for lo, hi, name in ((0, 3, "fm_0_3"), (4, 7, "fm_4_7"), (8, 8, "fm_8"), (504, 519, "fm_504_519"), (1016, 1031, "fm_1016_1031")):
+                if lo <= best <= hi:
+                    ev(name)
+            if cut and best >= 8:
+                ev("fm_cut_mod%d" % (max_match % 8))
         return best
 
     src_end = count - 16 - 2
     max_dist = MAXD1 if src_end < 4 * MAXD1 else MAXD2
     dst[12] = 0 if max_dist == MAXD1 else 1
+    ev("win_flag_%d" % dst[12])
     mm = 4
     if data_type == "DNA":
         mm = 6
@@ -729,62 +767,120 @@ def lz_forward(data, extra=False, data_type="UNDEFINED"):
     repd = [count, count]
     rep_idx = 0
     src_inc = 0
+    run_store = {}                                                                # position -> (srcInc of the literal step that stored it, entry it replaced)
+
+    def above(ref, min_ref):                                                      # the strict ref > minRef of every candidate test
+        return ref > min_ref or (mutate == "minref_ge" and ref == min_ref and min_ref > 0)
+
     while src_idx < src_end:
         best = 0
         h0 = h(src_idx)
-        ref0 = hashes[h0]
+        ref0 = ref0_old = hashes[h0]
         hashes[h0] = src_idx
+        if src_inc >= 2 and ref0 in run_store and 2 <= run_store[ref0][0] and src_inc - run_store[ref0][0] < 64:
+            ev("lit_peer_differs" if differ(ref0, src_idx) else "lit_peer_equal")
+            if mutate == "stale_lit_store":
+                ref0 = run_store[ref0][1]
+        run_store[src_idx] = (src_inc, ref0_old)
         s1 = src_idx + 1
         ref = s1 - repd[rep_idx]
         min_ref = max(src_idx - max_dist, 0)
-        if ref > min_ref and not differ(ref, s1):                                # repd first :378-387
+        via = "rep0"
+        if above(ref, min_ref) and not differ(ref, s1):                           # repd first :378-387
             best = find_match(s1, ref, min(src_end - s1, MAX_MATCH))
         else:
             ref = s1 - repd[rep_idx ^ 1]
-            if ref > min_ref and not differ(ref, s1):
+            via = "rep1"
+            if above(ref, min_ref) and not differ(ref, s1):
                 best = find_match(s1, ref, min(src_end - s1, MAX_MATCH))
         if best < mm:
             ref = ref0                                                            # :391-395
-            if ref > min_ref and not differ(ref, src_idx):
+            via = "table"
+            if above(ref, min_ref) and not differ(ref, src_idx):
                 best = find_match(src_idx, ref, min(src_end - src_idx, MAX_MATCH))
+            elif events is not None and ref == min_ref and min_ref > 0 and not differ(ref, src_idx):
+                ev("reject_minref")
             if best < mm:                                                         # :398-403
+                step = 1 + (src_inc >> 6)
+                ev("lit_step_1" if step == 1 else "lit_step_2" if step == 2 else "lit_step_3plus")
                 src_idx = s1 + (src_inc >> 6)
                 src_inc += 1
+                if src_inc in (64, 128):
+                    ev("lit_run_cross_%d" % src_inc)
                 rep_idx = 0
                 continue
+            if src_inc >= 2:
+                ev("lit_end_table")
             if ref != src_idx - repd[0] and ref != src_idx - repd[1]:             # :405-443 lazy probes
+                s0 = src_idx
                 h1 = h(s1)
-                ref1 = hashes[h1]
+                ref1 = ref1_old = hashes[h1]
+                if mutate == "lazy_early_read" and h1 == h0:
+                    ref1 = ref1_old = ref0_old
                 hashes[h1] = s1
+                if h1 == h0:
+                    ev("lazy_h1_eq_h0")
                 if ref1 > min_ref + 1 and not differ(ref1 + best - 3, s1 + best - 3):
                     b1 = find_match(s1, ref1, min(src_end - s1, MAX_MATCH))
                     if b1 >= best:
+                        ev("lazy_h1_eq_h0_win" if (h1 == h0 and ref1 == s0) else "lazy_p1_win")
                         ref, best, src_idx = ref1, b1, s1
                 if extra:
                     s2 = s1 + 1
                     h2 = h(s2)
                     ref2 = hashes[h2]
+                    if mutate == "lazy_early_read":
+                        ref2 = ref0_old if h2 == h0 else ref1_old if h2 == h1 else ref2
                     hashes[h2] = s2
+                    if h2 == h1:
+                        ev("lazy_h2_eq_h1")
+                    elif h2 == h0:
+                        ev("lazy_h2_eq_h0")
                     if ref2 > min_ref + 2 and not differ(ref2 + best - 3, s2 + best - 3):
                         b2 = find_match(s2, ref2, min(src_end - s2, MAX_MATCH))
                         if b2 >= best:
+                            ev("lazy_h2_eq_h1_win" if (h2 == h1 and ref2 == s1) else "lazy_h2_eq_h0_win" if (h2 == h0 and h2 != h1 and ref2 == s0) else "lazy_p2_win")
                             ref, best, src_idx = ref2, b2, s2
-            while src_idx > anchor and ref > min_ref and src[src_idx - 1] == src[ref - 1]:   # :446-450 extend backwards
+            back = 0
+            while (src_idx > anchor or mutate == "bwd_ignore_anchor") and ref > min_ref and src[src_idx - 1] == src[ref - 1] \
+                    and not (mutate == "bwd_cap7" and back >= 7):                 # :446-450 extend backwards
                 best += 1
                 ref -= 1
                 src_idx -= 1
-            if best > MAX_MATCH:                                                  # :452-456
+                back += 1
+            if events is not None:
+                ev("bwd_len_" + ("0" if back == 0 else "1_7" if back < 8 else "8" if back == 8 else "9_15" if back < 16 else "16" if back == 16 else "17plus"))
+                # what stopped it: the one bound that holds while the other two would have let it go on
+                if src_idx > anchor and ref > min_ref:
+                    ev("bwd_stop_byte")
+                elif src_idx == anchor and ref > min_ref and src[src_idx - 1] == src[ref - 1]:
+                    ev("bwd_stop_anchor")
+                elif ref == min_ref and src_idx > anchor and (ref == 0 or src[src_idx - 1] == src[ref - 1]):
+                    ev("bwd_stop_minref" if min_ref > 0 else "bwd_stop_block_start")
+                if ref < 8:
+                    ev("bwd_end_ref_lt8")
+                    if back >= 9:
+                        ev("bwd_end_ref_lt8_after_8")
+            if best > MAX_MATCH and mutate != "no_clamp":                         # :452-456
+                ev("bwd_clamp")
                 ref += best - MAX_MATCH
                 src_idx += best - MAX_MATCH
                 best = MAX_MATCH
         else:                                                                     # :457-466 repeat match found at srcIdx + 1
+            if src_inc >= 2:
+                ev("lit_end_" + via)
+            if best >= MAX_MATCH:
+                ev("rep_max_match")
             if best >= MAX_MATCH or src[src_idx] != src[ref - 1]:
+                ev("rep_found_no_ext")
                 src_idx += 1
                 hashes[h(src_idx)] = src_idx
             else:
+                ev("rep_found_ext_back")
                 best += 1
                 ref -= 1
         src_inc = 0
+        run_store = {}
         dist = src_idx - ref
         if dist == repd[0]:
             token, th = 0x00, 3
@@ -800,9 +896,16 @@ def lz_forward(data, extra=False, data_type="UNDEFINED"):
             mbuf[m_idx] = dist
             m_idx += 1
             token, th = (inc1 + inc2 + 1) << 3, 7
+            if events is not None:
+                for lo, hi, name in ((1, 1, "1"), (2, 63, "2_63"), (64, 64, "64"), (65, 255, "65_255"), (255, 255, "255"), (256, 256, "256"),
+                                     (65533, 65533, "65533"), (65535, 65535, "65535"), (65536, 65536, "65536"), (65537, MAXD2, "gt_65536")):
+                    if lo <= dist <= hi:
+                        ev("dist_" + name)
         mlen = best - mm
         if mlen >= th:
             token += th
+            if mlen - th in (252, 253, 254, 65789, 65790):
+                ev("mlen_%s_%d" % ("rep" if th == 3 else "new", mlen - th))
             mlen_idx = _emit_length(mlenbuf, mlen_idx, mlen - th)
         else:
             token += mlen
@@ -810,6 +913,8 @@ def lz_forward(data, extra=False, data_type="UNDEFINED"):
         repd[0] = dist
         rep_idx = 1
         lit = src_idx - anchor
+        if lit in (6, 7, 260, 261, 65796, 65797):
+            ev("lit_loop_%d" % lit)
         if lit == 0:
             tkbuf[tk_idx] = token
             tk_idx += 1
@@ -831,6 +936,24 @@ def lz_forward(data, extra=False, data_type="UNDEFINED"):
             if mlen_idx >= len(mlenbuf) - 4:
                 mlenbuf.extend([0] * ((len(mlenbuf) * 3) // 2 - len(mlenbuf)))
         anchor = src_idx + best                                                   # :552-564 hash fill
+        if events is not None or mutate == "fill_lowest_wins":
+            nfill = anchor - (src_idx + 1)
+            ev("nfill_" + (str(nfill) if nfill in (0, 1, 16, 17, 63, 64, 65) else "129plus" if nfill >= 129 else "other"))
+            if nfill > 16:                                                        # the rounds of 64 positions kz_lz.hip fills in
+                for p0 in range(src_idx + 1, anchor, 64):
+                    hs = [h(p) for p in range(p0, min(p0 + 64, anchor))]
+                    if len(set(hs)) < len(hs):
+                        ev("fill_dup_hash")
+                        if mutate == "fill_lowest_wins":
+                            for k in range(len(hs) - 1, -1, -1):
+                                hashes[hs[k]] = p0 + k
+                            continue
+                    if mutate == "fill_lowest_wins":
+                        for k, hk in enumerate(hs):
+                            hashes[hk] = p0 + k
+        if mutate == "fill_lowest_wins" and anchor - (src_idx + 1) > 16:
+            src_idx = anchor
+            continue
         while src_idx + 4 < anchor:
             src_idx += 4
             for k in (3, 2, 1, 0):
@@ -839,9 +962,14 @@ def lz_forward(data, extra=False, data_type="UNDEFINED"):
         while src_idx < anchor:
             hashes[h(src_idx)] = src_idx
             src_idx += 1
+    if src_inc >= 2:
+        ev("lit_end_srcend")
     lit = count - anchor                                                          # :567-596
     if dst_idx + lit + tk_idx + m_idx + mlen_idx >= count:
+        ev("declined_ge_count")
         return False, b""
+    if lit in (6, 7, 260, 261, 65796, 65797):
+        ev("lit_final_%d" % lit)
     if lit >= 7:
         tkbuf[tk_idx] = 7 << 5
         tk_idx += 1
@@ -857,6 +985,7 @@ def lz_forward(data, extra=False, data_type="UNDEFINED"):
     out[4:8] = tk_idx.to_bytes(4, "little")
     out[8:12] = m_idx.to_bytes(4, "little")
     out += bytes(tkbuf[:tk_idx]) + bytes(mbuf[:m_idx]) + bytes(mlenbuf[:mlen_idx])
+    ev("applied" if len(out) <= count - count // 100 else "declined_1pct")
     return len(out) <= count - count // 100, bytes(out)
 
 
