@@ -284,6 +284,46 @@ int32_t kz_knz_index(const uint8_t* src, int64_t n, uint64_t* transformType, uin
                      int32_t* blockSize, int64_t* inputSize, int32_t* checksumBits,
                      int64_t* blockBitOff, int64_t* blockBits, int32_t cap);
 
+/* ---- whole .knz stream on device memory ---------------------------------------------------------
+ * The same container as above, written and read with source and destination both in HBM: the stream is byte-identical to
+ * kz_compress's, and kz_decompress_device accepts everything kz_decompress accepts.  No payload byte crosses PCIe, except inside
+ * kz_encode_blocks / kz_decode_blocks for the blocks their TEXT / UTF host stages take.  What stays on the host: the stream header
+ * (at most 26 bytes, one small copy), the bit-offset arithmetic over results[] (5 + lw bit length prefix per block, :1024-1035), and
+ * the block-header prechecks (:1025-1095, :1145-1164) on 8 bytes per block that the walk of the length prefixes (:1127-1129, one
+ * lane on the device) brings back.
+ *
+ *   addresses   d_src, d_dst and d_streams may have any address and any alignment; they must not overlap.
+ *   read        nothing outside d_src[0 .. n) (kz_knz_assemble_device: of row i only the (bits[i] + 7) / 8 bytes of its stream).  When n
+ *               is not a multiple of blockSize, the last, short block is coded in a call of its own with its length as the longest
+ *               block (kz_encode_blocks's device contract may read a row up to the call's longest block).
+ *   written     nothing outside d_dst[0 .. dstCap).  On success dst[0 .. size) is the stream, the spare bits of its last byte zero;
+ *               dst[size .. dstCap) is unspecified; dst need not be zeroed by the caller.  kz_decompress_device: blocks whose whole
+ *               blockSize row fits in what is left of dst are decoded straight into it, the others (as a rule the last block of a
+ *               destination of the exact size) through staging and a device copy of their bytes; on a fault the blocks in front of
+ *               the first failing one are delivered.
+ *   returns     kz_compress_device: what kz_compress returns for the same arguments and context settings (checksum, skip blocks,
+ *               data type): the size, the first failing block's status, or -KZ_ERR_WRITE_FILE when dstCap is too small;
+ *               kz_compress_bound is the bound for both.  kz_decompress_device: what kz_decompress returns for the same bytes and
+ *               dstCap, fault or not (a stream is cut at the same block when dst is too small, although the two calls work in
+ *               chunks of different sizes).  kz_knz_assemble_device / kz_knz_index_device: as kz_knz_assemble / kz_knz_index
+ *               (entries with bits[i] <= 0 are skipped; `bits`, blockBitOff and blockBits are host arrays).
+ *   chunks      work proceeds in chunks, one after the other, so staging (the context's grow-only buffers) never exceeds a chunk's rows
+ *               whatever n is: kz_compress_device in kz_compress's chunks (about 1 GiB of blocks, 2048 at the most),
+ *               kz_decompress_device in kz_decompress's batches (8 GiB of blocks, 2048 at the most: the decoder's serial per-block
+ *               chains want many blocks in flight); KZ_STREAM_CHUNK=<blocks> overrides both.  A chunk's first bit is wherever the
+ *               previous chunk's last bit ended.
+ *   stream      the calls are synchronous and run on the context's stream.
+ */
+int64_t kz_compress_device(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int32_t blockSize,
+                           const uint8_t* d_src, int64_t n, uint8_t* d_dst, int64_t dstCap);
+int64_t kz_decompress_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, uint8_t* d_dst, int64_t dstCap);
+int64_t kz_knz_assemble_device(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int32_t blockSize, int64_t inputSize,
+                               int32_t checksumBits, const uint8_t* d_streams, int64_t stride, const int64_t* bits /* host */,
+                               int32_t nBlocks, uint8_t* d_dst, int64_t dstCap);
+int32_t kz_knz_index_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, uint64_t* transformType, uint32_t* entropyType,
+                            int32_t* blockSize, int64_t* inputSize, int32_t* checksumBits,
+                            int64_t* blockBitOff /* host */, int64_t* blockBits /* host */, int32_t cap);
+
 /* ---- instrumentation (bench.py / roofline) ----------------------------------------------------- */
 /* blocks that went through a TEXT / UTF stage on a HOST thread since the last reset (process-wide counter; inverse = 0: forward,
  * 1: inverse).  The stage timers KZ_STAGE_HOST_FWD / _INV measure the TEXT / UTF stage's wall time INCLUDING its device forms

@@ -110,6 +110,10 @@ def load_library():
         "kz_knz_writer_add": (c.c_int32, [vp, u8p, c.c_int64]),
         "kz_knz_writer_close": (c.c_int64, [vp]),
         "kz_knz_index": (c.c_int32, [u8p, c.c_int64, vp, vp, vp, vp, vp, i64p, i64p, c.c_int32]),
+        "kz_compress_device": (c.c_int64, [vp, c.c_uint64, c.c_uint32, c.c_int32, u8p, c.c_int64, u8p, c.c_int64]),
+        "kz_decompress_device": (c.c_int64, [vp, u8p, c.c_int64, u8p, c.c_int64]),
+        "kz_knz_assemble_device": (c.c_int64, [vp, c.c_uint64, c.c_uint32, c.c_int32, c.c_int64, c.c_int32, u8p, c.c_int64, i64p, c.c_int32, u8p, c.c_int64]),
+        "kz_knz_index_device": (c.c_int32, [vp, u8p, c.c_int64, vp, vp, vp, vp, vp, i64p, i64p, c.c_int32]),
         "kz_set_timing": (None, [vp, c.c_int32]),
         "kz_get_stage_count": (c.c_int32, [vp]),
         "kz_get_stage_ms": (c.c_float, [vp, c.c_int32]),
@@ -137,6 +141,7 @@ ABI_SYMBOLS = ["kz_abi_version", "kz_ctx_create", "kz_ctx_destroy", "kz_last_err
                "kz_entropy_encode", "kz_entropy_decode", "kz_encode_blocks", "kz_decode_blocks",
                "kz_max_block_stream_bytes", "kz_submit_encode_blocks", "kz_submit_decode_blocks", "kz_wait", "kz_poll", "kz_compress", "kz_decompress", "kz_compress_bound", "kz_transform_type",
                "kz_knz_assemble", "kz_knz_index", "kz_knz_writer_open", "kz_knz_writer_add", "kz_knz_writer_close",
+               "kz_compress_device", "kz_decompress_device", "kz_knz_assemble_device", "kz_knz_index_device",
                "kz_set_timing", "kz_get_stage_count", "kz_get_stage_ms", "kz_get_stage_alg_bytes", "kz_reset_timing",
                "kz_set_kernel_timing", "kz_get_kernel_count", "kz_get_kernel_name", "kz_get_kernel_ms", "kz_get_kernel_max_ms",
                "kz_get_kernel_launches", "kz_reset_kernel_timing"]
@@ -769,7 +774,7 @@ def knz_index(data):
     L = load_library()
     src = np.frombuffer(bytes(data) + b"\0" * 16, dtype=np.uint8)
     tt, et, bs, isz, chk = ctypes.c_uint64(0), ctypes.c_uint32(0), ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
-    cap = max(16, len(data) // 8 + 16)
+    cap = len(data) * 8 // 9 + 16                 # a block takes 9 bits of the stream at the least (5 + 3 bit prefix, W >= 1)
     off = np.zeros(cap, dtype=np.int64)
     bits = np.zeros(cap, dtype=np.int64)
     nb = L.kz_knz_index(src.ctypes.data, len(data), ctypes.addressof(tt), ctypes.addressof(et), ctypes.addressof(bs),
@@ -778,6 +783,93 @@ def knz_index(data):
         raise KanziError(-nb, "knz_index")
     return {"transform": tt.value, "entropy": et.value, "blockSize": bs.value, "inputSize": isz.value, "checksum": chk.value,
             "blocks": [(int(off[i]), int(bits[i])) for i in range(nb)]}
+
+
+# ---- whole .knz stream on device memory (kz_compress_device and its kin: source and destination in HBM) ----
+def compress_device(ctx, transform, entropy, block_size, src, n, dst, cap, checksum=0, skip_blocks=False):
+    """kz_compress_device: the .knz stream of the n bytes at device address `src`, written at device address `dst` (capacity `cap`;
+    compress_bound(n, block_size) always suffices) -> its size.  `src` / `dst`: integer device pointers, any alignment."""
+    tt = transform if isinstance(transform, int) else transform_type(transform)
+    et = entropy if isinstance(entropy, int) else ENTROPY_IDS[entropy.upper()]
+    ctx.set_checksum(checksum)
+    ctx.set_skip_blocks(skip_blocks)
+    try:
+        rc = ctx.lib.kz_compress_device(ctx.h, tt, et, int(block_size), _ptr(src), int(n), _ptr(dst), int(cap))
+    finally:
+        ctx.set_checksum(0)
+        ctx.set_skip_blocks(False)
+    return int(ctx.check(rc))
+
+
+def decompress_device(ctx, src, n, dst, cap):
+    """kz_decompress_device: decode the n-byte .knz stream at device address `src` into device address `dst` -> decoded size."""
+    return int(ctx.check(ctx.lib.kz_decompress_device(ctx.h, _ptr(src), int(n), _ptr(dst), int(cap))))
+
+
+def compress_bound(n, block_size):
+    return int(load_library().kz_compress_bound(int(n), int(block_size)))
+
+
+def knz_assemble_device(ctx, transform, entropy, block_size, input_size, streams, stride, bits, dst, cap, checksum=0):
+    """kz_knz_assemble_device: knz_assemble with the rows (device address `streams`, `stride` bytes apart) and the destination on the
+    device; `bits` is a host sequence, entries <= 0 are skipped -> the stream's size."""
+    tt = transform if isinstance(transform, int) else transform_type(transform)
+    et = entropy if isinstance(entropy, int) else ENTROPY_IDS[entropy.upper()]
+    b = np.ascontiguousarray(bits, dtype=np.int64)
+    rc = ctx.lib.kz_knz_assemble_device(ctx.h, tt, et, int(block_size), int(input_size), int(checksum), _ptr(streams), int(stride),
+                                        b.ctypes.data if len(b) else None, len(b), _ptr(dst), int(cap))
+    return int(ctx.check(rc))
+
+
+def knz_index_device(ctx, src, n):
+    """kz_knz_index_device: knz_index of the n-byte stream at device address `src` -> the same dict."""
+    tt, et, bs, isz, chk = ctypes.c_uint64(0), ctypes.c_uint32(0), ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
+    cap = int(n) * 8 // 9 + 16                    # a block takes 9 bits of the stream at the least (5 + 3 bit prefix, W >= 1)
+    off = np.zeros(cap, dtype=np.int64)
+    bits = np.zeros(cap, dtype=np.int64)
+    nb = ctx.lib.kz_knz_index_device(ctx.h, _ptr(src), int(n), ctypes.addressof(tt), ctypes.addressof(et), ctypes.addressof(bs),
+                                     ctypes.addressof(isz), ctypes.addressof(chk), off.ctypes.data, bits.ctypes.data, cap)
+    if nb < 0:
+        raise KanziError(-nb, "knz_index_device")
+    return {"transform": tt.value, "entropy": et.value, "blockSize": bs.value, "inputSize": isz.value, "checksum": chk.value,
+            "blocks": [(int(off[i]), int(bits[i])) for i in range(nb)]}
+
+
+def _byte_view(t):
+    import torch
+    if not t.is_cuda or not t.is_contiguous():
+        raise ValueError("a contiguous device tensor is needed")
+    return t.reshape(-1).view(torch.uint8)
+
+
+def compress_tensor(ctx, t, transform="BWT+RANK+ZRLT", entropy="ANS0", block_size=4 << 20, checksum=0):
+    """The .knz stream of a contiguous device tensor's bytes, as a torch.uint8 device tensor of exactly the stream's size.  The result
+    is a VIEW of a buffer of compress_bound(nbytes, block_size) bytes, which stays allocated as long as the view lives: clone() it to
+    keep only the stream."""
+    import torch
+    src = _byte_view(t)
+    n = src.numel()
+    cap = compress_bound(n, block_size)
+    dst = torch.empty(cap, dtype=torch.uint8, device=t.device)
+    torch.cuda.current_stream(t.device).synchronize()            # the call runs on the context's own stream
+    size = compress_device(ctx, transform, entropy, block_size, src.data_ptr() if n else dst.data_ptr(), n, dst.data_ptr(), cap, checksum=checksum)
+    return dst[:size]
+
+
+def decompress_tensor(ctx, knz, out=None):
+    """Decode a .knz stream held in a torch.uint8 device tensor -> a torch.uint8 device tensor of the decoded bytes (a view of `out`
+    when given).  Without `out` the result is sized from the stream's own block walk (blocks x blockSize), not from the header's
+    size field, which is informative and untrusted (CompressedInputStream._declared_size)."""
+    import torch
+    src = _byte_view(knz)
+    n = src.numel()
+    torch.cuda.current_stream(knz.device).synchronize()
+    if out is None:
+        idx = knz_index_device(ctx, src.data_ptr(), n)
+        out = torch.empty(max(len(idx["blocks"]) * idx["blockSize"], 1), dtype=torch.uint8, device=knz.device)
+    dst = _byte_view(out)
+    size = decompress_device(ctx, src.data_ptr(), n, dst.data_ptr(), dst.numel())
+    return dst[:size]
 
 
 def usable_cpus():

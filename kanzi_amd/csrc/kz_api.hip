@@ -104,6 +104,8 @@ extern "C" void kz_ctx_destroy(kz_ctx* ctx) {
     if (ctx->devOut[i].p) hipFree(ctx->devOut[i].p);
   }
   if (ctx->tfIn.p) hipHostFree(ctx->tfIn.p);
+  if (ctx->knzPin.p) hipHostFree(ctx->knzPin.p);
+  if (ctx->knzAux.p) hipFree(ctx->knzAux.p);
   if (ctx->tfCopy) hipStreamDestroy(ctx->tfCopy);
   if (ctx->evBlock) hipEventDestroy(ctx->evBlock);
   if (ctx->copyUp) hipStreamDestroy(ctx->copyUp);

@@ -46,7 +46,7 @@
   X(KID_RANGE_DEC, "k_range_dec") X(KID_CM_ENC, "k_cm_enc") X(KID_CM_DEC, "k_cm_dec") X(KID_LZP_FWD, "k_lzp_fwd") \
   X(KID_LZP_INV, "k_lzp_inv") X(KID_EXE_SETUP, "k_exe_setup") X(KID_EXE_MAP, "k_exe_map") X(KID_EXE_SCAN, "k_exe_scan") \
   X(KID_EXE_HIST, "k_exe_hist") X(KID_EXE_DECIDE, "k_exe_decide") X(KID_EXE_SIZE, "k_exe_size") X(KID_EXE_VERDICT, "k_exe_verdict") \
-  X(KID_EXE_EMIT, "k_exe_emit")
+  X(KID_EXE_EMIT, "k_exe_emit") X(KID_KNZ_PACK, "k_knz_pack") X(KID_KNZ_WALK, "k_knz_walk") X(KID_KNZ_UNPACK, "k_knz_unpack")
 #define KZ_KERNEL_ENUM(id, name) id,
 #define KZ_KERNEL_NAME(id, name) name,
 enum KzKernelId { KZ_KERNELS(KZ_KERNEL_ENUM) KID_COUNT };
@@ -141,6 +141,7 @@ struct kz_ctx {
   hipStream_t copyUp = nullptr, copyDown = nullptr;
   Stage hiAux[2];                  // HBM: per-block lengths / masks of the decoder's host-inverse chunks (kz_api.hip)
   hipStream_t hiStream[2] = {nullptr, nullptr};   // their gather / scatter kernels run beside the main stream's next chunk
+  Stage knzPin, knzAux;            // pinned / HBM: the device stream calls' per-chunk tables (bit offsets, lengths, header bytes; kz_stream.hip)
   // waits of the context's own thread: 1 = block on an event (hipEventBlockingSync) instead of hipStreamSynchronize's spin loop.
   // Chosen at creation: on when the process is CPU-quota limited (a spinning waiter burns a whole CPU of the quota that the
   // host stages -- or the other ranks of the node -- could use), KZ_BLOCKING_WAITS=0/1 overrides.
@@ -306,6 +307,13 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
 HostPre* kz_host_prestage(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int32_t blockSize, const uint8_t* hsrc, int64_t hstride,
                           const int32_t* lengths, int32_t nBlocks, int slotId);   // slotId 0/1: the outputs go to the context's pinned hsOut[slotId]
 void kz_host_pre_free(HostPre* p);
+
+// ---- the .knz container on device memory (kz_knz_gpu.hip); the callers are in kz_stream.hip ----
+struct KnzBlk { int64_t pay, bits, src; };   // a block in the container: bit offset of its payload in dst, its W, byte offset of its row
+enum { KNZ_WALK_COUNT = 0, KNZ_WALK_END = 1, KNZ_WALK_PREFIX = 2, KNZ_WALK_PAYLOAD = 3 };
+int kz_knz_pack(kz_ctx*, const uint8_t* d_rows, const KnzBlk* d_blk, int nb, uint8_t* d_dst, int64_t startBit, int64_t endBit);
+int kz_knz_walk(kz_ctx*, const uint8_t* d_src, int64_t n, int64_t startBit, int maxCount, int64_t* d_off, int64_t* d_bits, uint64_t* d_hdr, int64_t* d_res);
+int kz_knz_unpack(kz_ctx*, const uint8_t* d_src, int64_t n, const int64_t* d_off, const int64_t* d_bits, int nb, int64_t maxBytes, uint8_t* d_rows, int64_t stride);
 
 // timing helpers
 void kz_stage_begin(kz_ctx*, hipEvent_t* e0);

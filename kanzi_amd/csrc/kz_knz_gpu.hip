@@ -1,0 +1,214 @@
+// kz_knz_gpu.hip -- the .knz container on device memory: the bit-granular concatenation of block streams
+// (K/io/CompressedOutputStream.java:1024-1035) as a copy kernel, its inverse, and the serial walk of the block length
+// prefixes (K/io/CompressedInputStream.java:1127-1129).  The callers (kz_compress_device / kz_decompress_device /
+// kz_knz_assemble_device / kz_knz_index_device, kz_stream.hip) do the bit-offset arithmetic, the stream header and the
+// block-header prechecks on the host; no payload byte leaves the device.
+#include "kz_device.h"
+#include "kz_internal.h"
+#include <algorithm>
+
+typedef uint8_t u8;
+typedef uint32_t u32;
+typedef unsigned long long u64;
+
+namespace {
+// 16 bytes of the bit string that starts `sh` bits (0..7) into *p, from aligned 32-bit loads: reads the aligned words that cover
+// p[0 .. 16] (p[0 .. 15] when the total shift is 0), so the caller makes sure that [p & ~3, (p & ~3) + knz_window(p, sh)) is readable
+__device__ __forceinline__ int knz_window(const u8* p, int sh) { return ((((uintptr_t)p & 3) << 3) + sh) ? 20 : 16; }
+__device__ __forceinline__ uint4 knz_load128(const u8* p, int sh) {
+  const int s = (int)(((uintptr_t)p & 3) << 3) + sh;                    // 0 .. 31
+  const u32* a = (const u32*)((uintptr_t)p & ~(uintptr_t)3);
+  u32 w[5];
+#pragma unroll
+  for (int i = 0; i < 4; i++) w[i] = __builtin_bswap32(a[i]);
+  w[4] = s ? __builtin_bswap32(a[4]) : 0u;
+  u32 o[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) o[i] = s ? ((w[i] << s) | (w[i + 1] >> (32 - s))) : w[i];
+  return make_uint4(__builtin_bswap32(o[0]), __builtin_bswap32(o[1]), __builtin_bswap32(o[2]), __builtin_bswap32(o[3]));
+}
+__device__ __forceinline__ int knz_lw(int64_t W) { return W < 8 ? 3 : kz_ilog2((u32)(W >> 3)) + 4; }   // write_block, kz_stream.hip
+}  // namespace
+
+// ---- pack: blocks -> container --------------------------------------------------------------------------------------------
+// The launch owns the bits [startBit, endBit) of dst: the fields of blk[0 .. nb) back to back from startBit (5 bits lw - 3, lw bits
+// W, W payload bits from rows + blk[i].src), then zeros up to endBit (the end marker, :491-492) and to the end of the last byte.
+// Output-centric: a lane owns the (at most) 16 bytes of one 16-byte aligned unit of dst and composes them from whatever fields
+// they hold, so every byte has one writer and nothing depends on what dst held -- with one exception: when startBit is not on a
+// byte boundary, the high bits of the first byte are the previous launch's (same stream), which wrote that byte whole with its
+// spare bits zero; they are read back and kept.  From a row only the bytes of its W bits are read.
+__global__ void __launch_bounds__(256) k_knz_pack(const u8* __restrict__ rows, const KnzBlk* __restrict__ blk, int nb, u8* dst, int64_t startBit, int64_t endBit) {
+  const int64_t firstByte = startBit >> 3, lastByte = (endBit + 7) >> 3;           // [firstByte, lastByte) is written
+  const uintptr_t A0 = (uintptr_t)(dst + firstByte) & ~(uintptr_t)15;
+  const int64_t units = (int64_t)(((uintptr_t)(dst + lastByte) - A0 + 15) >> 4);
+  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t ub = (int64_t)(A0 - (uintptr_t)dst) + (u << 4);                   // the unit's first byte as an index into dst (may be < firstByte)
+    const int64_t lo = ub < firstByte ? firstByte : ub, hi = ub + 16 > lastByte ? lastByte : ub + 16;
+    if (lo >= hi) continue;
+    const int64_t pos0 = (lo == firstByte) ? startBit : (lo << 3);
+    // the last block whose prefix starts at or before pos0 (prefix starts grow with i)
+    int j = 0;
+    {
+      int a = 0, b = nb;                                                            // invariant: prefix start of blocks < a is <= pos0
+      while (a < b) {
+        const int m = (a + b) >> 1;
+        const int64_t W = blk[m].bits;
+        if (blk[m].pay - 5 - knz_lw(W) <= pos0) a = m + 1; else b = m;
+      }
+      j = a > 0 ? a - 1 : 0;
+    }
+    if (j < nb && hi - lo == 16) {                                                  // the whole unit inside one payload: wide load, wide store
+      const int64_t pay = blk[j].pay, W = blk[j].bits;
+      if (pos0 >= pay && (hi << 3) <= pay + W) {
+        const int64_t k = pos0 - pay;
+        const u8* row = rows + blk[j].src;
+        const u8* p = row + (k >> 3);
+        const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
+        if (al >= row && al + knz_window(p, (int)(k & 7)) <= row + ((W + 7) >> 3)) {
+          *(uint4*)(dst + lo) = knz_load128(p, (int)(k & 7));
+          continue;
+        }
+      }
+    }
+    int64_t pos = pos0;
+    for (int64_t b = lo; b < hi; b++) {
+      const int64_t bend = (b + 1) << 3;
+      u32 acc = 0;
+      if (pos & 7) acc = dst[b] & (0xFFu << (8 - (int)(pos & 7)));                  // only the launch's first byte: see above
+      while (pos < bend) {
+        while (j < nb && pos >= blk[j].pay + blk[j].bits) j++;
+        if (j >= nb) break;                                                         // behind the last field: zeros
+        const int64_t pay = blk[j].pay, W = blk[j].bits;
+        const int room = (int)(bend - pos);
+        u32 v; int take;
+        if (pos < pay) {                                                            // length prefix: 5 + lw bits
+          const int lw = knz_lw(W), pw = 5 + lw;
+          const u64 field = ((u64)(lw - 3) << lw) | (u64)W;
+          const int k = (int)(pos - (pay - pw));
+          take = (int)(pay - pos) < room ? (int)(pay - pos) : room;
+          v = (u32)(field >> (pw - k - take)) & ((1u << take) - 1);
+        } else {
+          const int64_t k = pos - pay;
+          const int so = (int)(k & 7);
+          take = (W - k) < room ? (int)(W - k) : room;
+          const u8* s = rows + blk[j].src + (k >> 3);
+          const u32 two = ((u32)s[0] << 8) | (so + take > 8 ? (u32)s[1] : 0u);
+          v = (two >> (16 - so - take)) & ((1u << take) - 1);
+        }
+        acc |= v << (room - take);
+        pos += take;
+      }
+      dst[b] = (u8)acc;
+      pos = bend;
+    }
+  }
+}
+
+// ---- walk: the length prefixes, one after the other ---------------------------------------------------------------------------
+// One lane (the chain is serial by the format).  From bit `startBit` of src[0 .. n): per block the payload's bit offset, its W, and
+// the first 8 bytes of the payload, left aligned (zeros where the stream ends): the block-header bytes the host prechecks.
+// res[0] = blocks recorded whole, res[1] = bit position of the next prefix, res[2] = why it stopped: KNZ_WALK_COUNT, _END (the end
+// marker, W = 0; res[1] is behind it), _PREFIX (a prefix does not fit in 8 n bits; res[1] is that prefix) or _PAYLOAD (a payload
+// does not fit: its entry is recorded at index res[0] all the same, res[1] is its payload).  Nothing outside src[0 .. n) is read.
+__device__ __forceinline__ u64 knz_peek64(const u8* __restrict__ src, int64_t n, int64_t pos) {   // 57 bits or more from bit pos, left aligned
+  const int64_t by = pos >> 3;
+  u64 hi = 0; u32 lo = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) hi = (hi << 8) | (by + i < n ? (u64)src[by + i] : 0ull);
+  lo = by + 8 < n ? (u32)src[by + 8] : 0u;
+  const int sh = (int)(pos & 7);
+  return sh ? ((hi << sh) | (lo >> (8 - sh))) : hi;
+}
+__global__ void k_knz_walk(const u8* __restrict__ src, int64_t n, int64_t startBit, int maxCount,
+                           int64_t* __restrict__ off, int64_t* __restrict__ bits, u64* __restrict__ hdr, int64_t* __restrict__ res) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int64_t nbits = n << 3;
+  int64_t pos = startBit;
+  int cnt = 0, why = KNZ_WALK_COUNT;
+  while (cnt < maxCount) {
+    if (pos + 5 > nbits) { why = KNZ_WALK_PREFIX; break; }
+    const u64 w = knz_peek64(src, n, pos);                                          // 5 + 34 bits at the most
+    const int lr = (int)(w >> 59) + 3;
+    if (pos + 5 + lr > nbits) { why = KNZ_WALK_PREFIX; break; }
+    const int64_t W = (int64_t)((w << 5) >> (64 - lr));
+    const int64_t pay = pos + 5 + lr;
+    if (W == 0) { why = KNZ_WALK_END; pos = pay; break; }
+    off[cnt] = pay; bits[cnt] = W; hdr[cnt] = knz_peek64(src, n, pay);               // (bytes at and behind src[n] read as zero)
+    pos = pay;
+    if (W > nbits - pay) { why = KNZ_WALK_PAYLOAD; break; }
+    pos = pay + W;
+    cnt++;
+  }
+  res[0] = cnt; res[1] = pos; res[2] = why;
+}
+
+// ---- unpack: container -> byte-aligned rows ------------------------------------------------------------------------------------
+// Row i (rows + i * stride, 16-byte aligned) gets the bits[i] bits from bit off[i] of src, in 16-byte units; the bits behind them in
+// the last unit are zero (rows carry KZ_STREAM_SLACK bytes behind their streams).  Nothing outside src[0 .. n) is read: units
+// near either end of src load bytewise.
+__global__ void __launch_bounds__(256) k_knz_unpack(const u8* __restrict__ src, int64_t n, const int64_t* __restrict__ off, const int64_t* __restrict__ bits, int nb,
+                                                    u8* __restrict__ rows, int64_t stride) {
+  for (int i = blockIdx.y; i < nb; i += gridDim.y) {
+    const int64_t W = bits[i], o = off[i];
+    const int64_t units = (((W + 7) >> 3) + 15) >> 4;
+    u8* row = rows + (int64_t)i * stride;
+    for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
+      const int64_t sb = o + (u << 7);
+      const int sh = (int)(sb & 7);
+      const u8* p = src + (sb >> 3);
+      const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
+      uint4 v;
+      if (al >= src && al + knz_window(p, sh) <= src + n) v = knz_load128(p, sh);
+      else {
+        u32 o4[4];
+        const int64_t by = sb >> 3;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          u32 x = 0;
+#pragma unroll
+          for (int t = 0; t < 4; t++) {
+            const int64_t c = by + q * 4 + t;
+            const u32 b0 = c < n ? src[c] : 0u, b1 = (sh && c + 1 < n) ? src[c + 1] : 0u;
+            x |= (((b0 << sh) | (b1 >> (8 - sh))) & 0xFFu) << (8 * t);
+          }
+          o4[q] = x;
+        }
+        v = make_uint4(o4[0], o4[1], o4[2], o4[3]);
+      }
+      const int64_t left = W - (u << 7);                                             // bits of this unit that belong to the block
+      if (left < 128) {
+        u32* c = (u32*)&v;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int64_t l = left - 32 * q;
+          const u32 keepBE = l >= 32 ? ~0u : (l <= 0 ? 0u : ~0u << (32 - (int)l));   // mask on the big-endian view
+          c[q] &= __builtin_bswap32(keepBE);
+        }
+      }
+      *(uint4*)(row + (u << 4)) = v;
+    }
+  }
+}
+
+// ---- launchers -------------------------------------------------------------------------------------------------------------------
+int kz_knz_pack(kz_ctx* ctx, const uint8_t* d_rows, const KnzBlk* d_blk, int nb, uint8_t* d_dst, int64_t startBit, int64_t endBit) {
+  if (endBit <= startBit) return 0;
+  const int64_t units = (((endBit + 7) >> 3) - (startBit >> 3) + 15 + 15) >> 4;
+  const int grid = (int)std::min<int64_t>((units + 255) / 256, 1 << 20);
+  KZ_LAUNCH(ctx, KID_KNZ_PACK, k_knz_pack, dim3(grid), dim3(256), d_rows, d_blk, nb, d_dst, startBit, endBit);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_walk(kz_ctx* ctx, const uint8_t* d_src, int64_t n, int64_t startBit, int maxCount, int64_t* d_off, int64_t* d_bits, uint64_t* d_hdr, int64_t* d_res) {
+  KZ_LAUNCH(ctx, KID_KNZ_WALK, k_knz_walk, dim3(1), dim3(64), d_src, n, startBit, maxCount, d_off, d_bits, (u64*)d_hdr, d_res);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_unpack(kz_ctx* ctx, const uint8_t* d_src, int64_t n, const int64_t* d_off, const int64_t* d_bits, int nb, int64_t maxBytes, uint8_t* d_rows, int64_t stride) {
+  if (nb <= 0) return 0;
+  const int64_t units = (maxBytes + 15) >> 4;
+  const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((units + 255) / 256, 1 << 16));
+  KZ_LAUNCH(ctx, KID_KNZ_UNPACK, k_knz_unpack, dim3(gx, std::min(nb, KZ_MAX_BATCH)), dim3(256), d_src, n, d_off, d_bits, nb, d_rows, stride);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}

@@ -583,3 +583,291 @@ extern "C" int64_t kz_decompress(kz_ctx* ctx, const uint8_t* src, int64_t n, uin
   }
   return pending ? pending : produced;
 }
+
+
+// =================================================================================================
+// whole .knz stream on device memory: the same container, written and read with source and destination in HBM.  The kernels are in
+// kz_knz_gpu.hip; what stays here is what kz_compress / kz_decompress do on the host as well and costs nothing: the stream header
+// (write_stream_header / read_stream_header on a copy of at most 26 bytes), the bit-offset arithmetic over results[] (host arrays
+// anyway), and precheck_block_header on the 8 header bytes per block that the walk kernel brings back.
+namespace {
+// per-chunk tables, pinned and their HBM mirror: 64 bytes (the stream header resp. the walk's result), then the entries
+int knz_tables(kz_ctx* ctx, size_t entries, size_t entryBytes) {
+  const size_t need = 64 + entries * entryBytes;
+  int rc = stage_reserve(ctx, ctx->knzPin, need, true);
+  if (!rc) rc = stage_reserve(ctx, ctx->knzAux, need, false);
+  return rc;
+}
+// The rows' streams (W[i] bits each, rows `stride` apart, W[i] <= 0: no block) go behind bit `pos` of d_dst, then tailBits zero bits;
+// pos moves behind them.  -KZ_ERR_WRITE_FILE, nothing launched, when that does not fit in dstCap bytes.
+int knz_pack_rows(kz_ctx* ctx, const uint8_t* d_rows, int64_t stride, const int64_t* W, int cnt, uint8_t* d_dst, int64_t dstCap, int64_t& pos, int tailBits) {
+  KnzBlk* t = (KnzBlk*)(ctx->knzPin.p + 64);
+  int m = 0;
+  int64_t p = pos;
+  for (int i = 0; i < cnt; i++) {
+    if (W[i] <= 0) continue;
+    const int lw = ((uint64_t)W[i] < 8) ? 3 : ilog2((uint32_t)((uint64_t)W[i] >> 3)) + 4;    // write_block
+    p += 5 + lw;
+    t[m++] = KnzBlk{p, W[i], (int64_t)i * stride};
+    p += W[i];
+  }
+  const int64_t end = p + tailBits;
+  if (((end + 7) >> 3) > dstCap) return -KZ_ERR_WRITE_FILE;
+  if (m) KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + 64, t, (size_t)m * sizeof(KnzBlk), hipMemcpyHostToDevice, ctx->stream));
+  const int rc = kz_knz_pack(ctx, d_rows, (const KnzBlk*)(ctx->knzAux.p + 64), m, d_dst, pos, end);
+  pos = end;
+  return rc;
+}
+// the stream header goes up from the front of the pinned table; the caller waits for the stream before it returns
+int knz_put_header(kz_ctx* ctx, const uint8_t* hdr, int64_t hdrBytes, uint8_t* d_dst) {
+  memcpy(ctx->knzPin.p, hdr, (size_t)hdrBytes);
+  KZ_HIP(hipMemcpyAsync(d_dst, ctx->knzPin.p, (size_t)hdrBytes, hipMemcpyHostToDevice, ctx->stream));
+  return 0;
+}
+int knz_get_header(kz_ctx* ctx, const uint8_t* d_src, int64_t n, uint8_t* hdr /*32*/, int64_t& hn) {
+  memset(hdr, 0, 32);
+  hn = std::min<int64_t>(n, 26);                                 // the longest header: 160 + 48 bits
+  if (hn > 0) {
+    KZ_HIP(hipMemcpyAsync(hdr, d_src, (size_t)hn, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  }
+  return 0;
+}
+int knz_chunk_blocks(const kz_ctx* ctx, int blockSize) { return std::min(stream_chunk_blocks(ctx, blockSize), KZ_MAX_BATCH); }
+}  // namespace
+
+extern "C" int64_t kz_knz_assemble_device(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int32_t blockSize, int64_t inputSize,
+                                          int32_t checksumBits, const uint8_t* d_streams, int64_t stride, const int64_t* bits, int32_t nBlocks,
+                                          uint8_t* d_dst, int64_t dstCap) {
+  if (!ctx || !d_dst || nBlocks < 0 || (nBlocks > 0 && (!d_streams || !bits))) return -KZ_ERR_INVALID_PARAM;
+  if (checksumBits != 0 && checksumBits != 32 && checksumBits != 64) return -KZ_ERR_INVALID_PARAM;
+  KZ_HIP(hipSetDevice(ctx->device));
+  uint8_t hdr[32];
+  HostBits hb{hdr, 32, 0, false};
+  write_stream_header(hb, transformType, entropyType, blockSize, inputSize, checksumBits == 32 ? 1 : (checksumBits == 64 ? 2 : 0));
+  { const int rc = knz_tables(ctx, (size_t)std::max(nBlocks, 1), sizeof(KnzBlk)); if (rc) return rc; }
+  int64_t pos = (int64_t)hb.pos;                                // (a whole number of bytes: 160 + 16 k bits)
+  const int rc = knz_pack_rows(ctx, d_streams, stride, bits, nBlocks, d_dst, dstCap, pos, 8);   // end marker (:491-492)
+  if (rc) return rc;
+  { const int hrc = knz_put_header(ctx, hdr, (int64_t)(hb.pos >> 3), d_dst); if (hrc) return hrc; }
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  return (pos + 7) >> 3;
+}
+
+extern "C" int64_t kz_compress_device(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int32_t blockSize,
+                                      const uint8_t* d_src, int64_t n, uint8_t* d_dst, int64_t dstCap) {
+  if (!ctx || !d_src || !d_dst || n < 0) return -KZ_ERR_INVALID_PARAM;
+  if (blockSize < 1024 || blockSize > (1 << 30) || (blockSize & 15)) return -KZ_ERR_BLOCK_SIZE;   // :165-174
+  KZ_HIP(hipSetDevice(ctx->device));
+  uint8_t hdr[32];
+  HostBits hb{hdr, 32, 0, false};
+  write_stream_header(hb, transformType, entropyType, blockSize, n, ctx->checksum);
+  const int64_t nblocks = (n + blockSize - 1) / blockSize;
+  BlockSizeScope scope(ctx, blockSize);
+  const int CH = (int)std::min<int64_t>(knz_chunk_blocks(ctx, blockSize), std::max<int64_t>(nblocks, 1));
+  const int64_t oS = kz_max_block_stream_bytes(blockSize);
+  {
+    int rc = stage_reserve(ctx, ctx->devOut[0], (size_t)CH * oS, false);
+    if (!rc) rc = knz_tables(ctx, (size_t)CH, sizeof(KnzBlk));
+    if (rc) return rc;
+  }
+  auto tooSmall = [&]() { snprintf(ctx->err, sizeof(ctx->err), "kz_compress_device: destination too small"); return (int64_t)-KZ_ERR_WRITE_FILE; };
+  uint8_t* rows = ctx->devOut[0].p;
+  std::vector<int32_t> lens(CH);
+  std::vector<kz_block_result> res(CH);
+  std::vector<int64_t> W(CH);
+  int64_t pos = (int64_t)hb.pos;
+  // ---- chunks, one after the other: encode HBM -> HBM rows, pack the rows behind the previous chunk's last bit ----
+  for (int64_t b0 = 0; b0 < nblocks; b0 += CH) {
+    const int cnt = (int)std::min<int64_t>(CH, nblocks - b0);
+    for (int i = 0; i < cnt; i++) lens[i] = (int32_t)std::min<int64_t>(blockSize, n - (b0 + i) * blockSize);
+    // a device row may be read up to the call's longest block whatever its own length is (kz_encode_blocks's contract), and behind
+    // the stream's last, short block lies memory that is not the caller's: that block goes in a call of its own
+    const int full = lens[cnt - 1] < blockSize ? cnt - 1 : cnt;
+    int rc = 0;
+    if (full) rc = kz_encode_blocks_pre(ctx, transformType, entropyType, blockSize, d_src + b0 * blockSize, blockSize, lens.data(), full,
+                                        rows, oS, res.data(), KZ_MEM_DEVICE, nullptr);
+    if (!rc && full < cnt) rc = kz_encode_blocks_pre(ctx, transformType, entropyType, blockSize, d_src + (b0 + full) * blockSize, blockSize, lens.data() + full, 1,
+                                                     rows + (int64_t)full * oS, oS, res.data() + full, KZ_MEM_DEVICE, nullptr);
+    if (rc) return rc;
+    for (int i = 0; i < cnt; i++) { if (res[i].status) return res[i].status; W[i] = res[i].bits; }
+    rc = knz_pack_rows(ctx, rows, oS, W.data(), cnt, d_dst, dstCap, pos, b0 + cnt >= nblocks ? 8 : 0);   // the last chunk: end marker (:491-492)
+    if (rc == -KZ_ERR_WRITE_FILE) return tooSmall();
+    if (rc) return rc;
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));                    // the rows and the pinned table are the next chunk's
+    kz_ktimer_flush(ctx);
+  }
+  if (nblocks == 0) {
+    const int rc = knz_pack_rows(ctx, rows, oS, W.data(), 0, d_dst, dstCap, pos, 8);
+    if (rc == -KZ_ERR_WRITE_FILE) return tooSmall();
+    if (rc) return rc;
+  }
+  { const int hrc = knz_put_header(ctx, hdr, (int64_t)(hb.pos >> 3), d_dst); if (hrc) return hrc; }
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  return (pos + 7) >> 3;
+}
+
+// the walk's tables: result at the front, then off[CH], bits[CH], hdr[CH]
+namespace {
+struct KnzWalk {
+  int64_t* res; int64_t* off; int64_t* bits; uint64_t* hdr;         // host (pinned) views
+  int64_t* d_res; int64_t* d_off; int64_t* d_bits; uint64_t* d_hdr;
+  int cap;
+  void bind(kz_ctx* ctx, int CH) {
+    cap = CH;
+    res = (int64_t*)ctx->knzPin.p; off = (int64_t*)(ctx->knzPin.p + 64); bits = off + CH; hdr = (uint64_t*)(bits + CH);
+    d_res = (int64_t*)ctx->knzAux.p; d_off = (int64_t*)(ctx->knzAux.p + 64); d_bits = d_off + CH; d_hdr = (uint64_t*)(d_bits + CH);
+  }
+};
+// walk up to maxCount (<= T.cap) prefixes from bit pos and bring the tables back (arrays = 2: offsets and lengths, 3: the header bytes as well)
+int knz_walk_chunk(kz_ctx* ctx, KnzWalk& T, const uint8_t* d_src, int64_t n, int64_t pos, int maxCount, int arrays) {
+  const int CH = maxCount;
+  { const int rc = kz_knz_walk(ctx, d_src, n, pos, maxCount, T.d_off, T.d_bits, T.d_hdr, T.d_res); if (rc) return rc; }
+  KZ_HIP(hipMemcpyAsync(ctx->knzPin.p, ctx->knzAux.p, 64 + (size_t)arrays * T.cap * 8, hipMemcpyDeviceToHost, ctx->stream));
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  if (T.res[0] < 0 || T.res[0] > CH) { snprintf(ctx->err, sizeof(ctx->err), "knz walk: bad count"); return -KZ_ERR_DEVICE; }
+  return 0;
+}
+}  // namespace
+
+extern "C" int32_t kz_knz_index_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, uint64_t* transformType, uint32_t* entropyType,
+                                       int32_t* blockSize, int64_t* inputSize, int32_t* checksumBits, int64_t* blockBitOff, int64_t* blockBits, int32_t cap) {
+  if (!ctx) return -KZ_ERR_INVALID_PARAM;
+  if (!d_src || n < 20) return -KZ_ERR_INVALID_FILE;
+  KZ_HIP(hipSetDevice(ctx->device));
+  uint8_t hdr[32]; int64_t hn = 0;
+  { const int rc = knz_get_header(ctx, d_src, n, hdr, hn); if (rc) return rc; }
+  HostBitsIn bs{hdr, (uint64_t)hn * 8, 0, false};
+  KnzHeader h;
+  { const int hrc = read_stream_header(bs, h, nullptr, 0); if (hrc) return hrc; }
+  if (transformType) *transformType = h.transformType;
+  if (entropyType) *entropyType = (uint32_t)h.entropyType;
+  if (blockSize) *blockSize = h.blockSize;
+  if (inputSize) *inputSize = h.inputSize;
+  if (checksumBits) *checksumBits = h.chkKind == 1 ? 32 : (h.chkKind == 2 ? 64 : 0);
+  const int CH = (int)std::min<int64_t>(16384, n / 8 + 16);
+  { const int rc = knz_tables(ctx, (size_t)CH, 24); if (rc) return rc; }
+  KnzWalk T; T.bind(ctx, CH);
+  int64_t pos = (int64_t)bs.pos, nb = 0;
+  for (;;) {
+    { const int rc = knz_walk_chunk(ctx, T, d_src, n, pos, CH, 2); if (rc) return rc; }
+    const int got = (int)T.res[0], why = (int)T.res[2];
+    const int have = got + (why == KNZ_WALK_PAYLOAD ? 1 : 0);       // kz_knz_index records a block before it looks at its end
+    for (int i = 0; i < have; i++, nb++)
+      if (nb < cap) { if (blockBitOff) blockBitOff[nb] = T.off[i]; if (blockBits) blockBits[nb] = T.bits[i]; }
+    if (why == KNZ_WALK_PREFIX || why == KNZ_WALK_PAYLOAD) return -KZ_ERR_READ_FILE;
+    if (why == KNZ_WALK_END) break;
+    pos = T.res[1];
+    if (nb > 0x7FFFFFFF - CH) return -KZ_ERR_INVALID_FILE;
+  }
+  return (int32_t)nb;
+}
+
+extern "C" int64_t kz_decompress_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, uint8_t* d_dst, int64_t dstCap) {
+  if (!ctx || !d_src || !d_dst || n < 0) return -KZ_ERR_INVALID_PARAM;
+  KZ_HIP(hipSetDevice(ctx->device));
+  uint8_t hdr[32]; int64_t hn = 0;
+  { const int rc = knz_get_header(ctx, d_src, n, hdr, hn); if (rc) return rc; }
+  HostBitsIn bs{hdr, (uint64_t)hn * 8, 0, false};
+  KnzHeader h;
+  { const int hrc = read_stream_header(bs, h, ctx->err, sizeof(ctx->err)); if (hrc) return hrc; }
+  const int chkKind = h.chkKind, entropyType = h.entropyType, blockSize = h.blockSize;
+  const uint64_t tt = h.transformType;
+  const int savedChk = ctx->checksum;
+  ctx->checksum = chkKind;
+  struct Restore { kz_ctx* c; int v; ~Restore() { c->checksum = v; } } restore_{ctx, savedChk};
+  int nbFunctions = 0;
+  for (int i = 0; i < 8; i++) if (((tt >> (42 - 6 * i)) & 0x3F) != 0) nbFunctions++;         // Sequence length (TransformFactory.java:240-266)
+  if (nbFunctions == 0) nbFunctions = 1;
+  const uint64_t nbits = (uint64_t)n * 8;
+  // kz_decompress's own batch: 8 GiB of blocks, 2048 at the most, and no more than the stream can need (declared size if present,
+  // else >= 8 bytes of stream per block).  The decoder's serial per-block chains want that many blocks in flight: in chunks of the
+  // writer's size (about 1 GiB) a 2048 x 4 MiB stream decodes at a quarter of the speed.  KZ_STREAM_CHUNK makes the
+  // chunks smaller (the tests' seams); kz_decompress looks at the room left in dst once per batch of ITS size, so chunks never
+  // straddle those batches and carry the batch's count of blocks that may still start inside dst: both calls cut a stream at the
+  // same block.
+  int64_t NB = batch_blocks(blockSize);
+  if (h.szMask && h.inputSize > 0) NB = std::min<int64_t>(NB, (h.inputSize + blockSize - 1) / blockSize);
+  else NB = std::min<int64_t>(NB, n / 8 + 1);
+  const int CH = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->sw.streamChunk > 0 ? ctx->sw.streamChunk : NB, std::min<int64_t>(NB, KZ_MAX_BATCH)));
+  const int64_t iS = (int64_t)kz_align((size_t)blockSize + (size_t)(blockSize >> 3) + 1024 + 64, 256);
+  { const int rc = knz_tables(ctx, (size_t)CH, 24); if (rc) return rc; }
+  KnzWalk T; T.bind(ctx, CH);
+  std::vector<kz_block_result> res(CH);
+  int64_t pos = (int64_t)bs.pos, produced = 0;
+  bool done = false;
+  int pending = 0;
+  int64_t batchLeft = 0, fitLeft = 0;
+  while (!done) {
+    if (batchLeft == 0) {
+      batchLeft = NB;
+      const int64_t room = dstCap - produced;
+      fitLeft = (room <= 0) ? 0 : (room + blockSize - 1) / blockSize;
+    }
+    const int want = (int)std::min<int64_t>(CH, batchLeft);
+    // ---- the walk on the device, then kz_decompress's checks in kz_decompress's order on what it recorded.  A fault met here is
+    //      held back until the blocks before it have been decoded: the reference reports the FIRST failing block in stream order ----
+    { const int rc = knz_walk_chunk(ctx, T, d_src, n, pos, want, 3); if (rc) return rc; }
+    const int why = (int)T.res[2];
+    const int have = (int)T.res[0] + (why == KNZ_WALK_PAYLOAD ? 1 : 0);
+    pos = T.res[1];
+    int cnt = 0;
+    for (; cnt < have; cnt++) {
+      const uint64_t rd = (uint64_t)T.bits[cnt], at = (uint64_t)T.off[cnt];
+      uint8_t hb8[8];
+      for (int k = 0; k < 8; k++) hb8[k] = (uint8_t)(T.hdr[cnt] >> (56 - 8 * k));
+      HostBitsIn t{hb8, std::min<uint64_t>(64, nbits - at), 0, false};         // the header is 7 bytes at the most
+      pending = precheck_block_header(t, rd, nbFunctions, blockSize, chkKind);
+      if (!pending && (int64_t)((rd + 7) >> 3) > iS - 64) pending = -KZ_ERR_BLOCK_SIZE;
+      if (!pending && at + rd > nbits) pending = -KZ_ERR_READ_FILE;
+      if (pending) break;
+    }
+    if (!pending) { if (why == KNZ_WALK_PREFIX) pending = -KZ_ERR_READ_FILE; else if (why == KNZ_WALK_END) done = true; }
+    if (pending) done = true;
+    if (cnt == 0) break;
+    // blocks that start past the end of the destination cannot be stored (kz_decompress)
+    if (fitLeft < cnt) { cnt = (int)fitLeft; pending = -KZ_ERR_WRITE_FILE; done = true; }
+    if (cnt == 0) break;
+    fitLeft -= cnt; batchLeft -= cnt;
+    int64_t maxBytes = 0;
+    for (int i = 0; i < cnt; i++) maxBytes = std::max<int64_t>(maxBytes, (T.bits[i] + 7) >> 3);
+    { const int rc = stage_reserve(ctx, ctx->devIn[0], (size_t)cnt * iS, false); if (rc) return rc; }   // (grow-only: the blocks walked, not the chunk's most)
+    { const int rc = kz_knz_unpack(ctx, d_src, n, T.d_off, T.d_bits, cnt, maxBytes, ctx->devIn[0].p, iS); if (rc) return rc; }
+    // ---- blocks whose whole blockSize row lies inside what is left of dst are decoded in place; the others (as a rule the last
+    //      block of a destination of the exact size) into staging rows ----
+    const int nd = (int)std::min<int64_t>(cnt, (dstCap - produced) / blockSize);
+    if (cnt > nd) { const int rc = stage_reserve(ctx, ctx->devOut[0], (size_t)(cnt - nd) * blockSize, false); if (rc) return rc; }
+    int rc = 0;
+    if (nd) rc = kz_decode_blocks(ctx, tt, (uint32_t)entropyType, blockSize, ctx->devIn[0].p, iS, T.bits, nd,
+                                  d_dst + produced, blockSize, res.data(), KZ_MEM_DEVICE);
+    if (!rc && cnt > nd) rc = kz_decode_blocks(ctx, tt, (uint32_t)entropyType, blockSize, ctx->devIn[0].p + (int64_t)nd * iS, iS, T.bits + nd, cnt - nd,
+                                               ctx->devOut[0].p, blockSize, res.data() + nd, KZ_MEM_DEVICE);
+    if (rc) return rc;
+    // ---- the reader appends whatever a block produced (:783-785): a block behind a short one moves left, in stream order; the
+    //      first failing block ends the stream, the blocks in front of it are delivered ----
+    const int64_t base = produced;
+    int code = 0;
+    for (int i = 0; i < cnt; i++) {
+      if (res[i].status) { code = res[i].status; break; }
+      if (res[i].length > blockSize) { code = -KZ_ERR_PROCESS_BLOCK; break; }                    // "incorrectly decompressed" (:756-759)
+      if (produced + res[i].length > dstCap) { code = -KZ_ERR_WRITE_FILE; break; }
+      const int64_t len = res[i].length;
+      const uint8_t* from = i < nd ? d_dst + base + (int64_t)i * blockSize : ctx->devOut[0].p + (int64_t)(i - nd) * blockSize;
+      uint8_t* to = d_dst + produced;
+      if (len > 0 && from != to) {
+        if (i < nd && from - to < len) {                          // overlapping move: through the staging rows, which are done with
+          KZ_HIP(hipMemcpyAsync(ctx->devIn[0].p, from, (size_t)len, hipMemcpyDeviceToDevice, ctx->stream));
+          from = ctx->devIn[0].p;
+        }
+        KZ_HIP(hipMemcpyAsync(to, from, (size_t)len, hipMemcpyDeviceToDevice, ctx->stream));
+      }
+      produced += len;
+    }
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+    if (code) return code;
+  }
+  return pending ? pending : produced;
+}
