@@ -324,6 +324,62 @@ int32_t kz_knz_index_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, uint64
                             int32_t* blockSize, int64_t* inputSize, int32_t* checksumBits,
                             int64_t* blockBitOff /* host */, int64_t* blockBits /* host */, int32_t cap);
 
+/* ---- seekable .knz streams: a block range, or blocks by an index ----------------------------------
+ * Two ways to read part of a stream, each on host memory and on device memory (the _device forms keep kz_decompress_device's
+ * memory contract).  Blocks are numbered from 0 in stream order.
+ *
+ * The RANGE form mirrors the reference reader's context entries "from" / "to" (CompressedInputStream.java:1193-1200, the CLI's
+ * --from / --to): from = firstBlock + 1, to = firstBlock + 1 + nBlocks.  It needs no index and walks the length prefixes from the
+ * front, so its cost grows with firstBlock (about 2 us per skipped block on the device: the walk is one lane).  Blocks in front of
+ * firstBlock are read and skipped as the reference does before it looks at "from" (:1126-1165): length prefix, block-header
+ * precheck, staging-row bound, end of stream, in kz_decompress's order; a fault there is returned and nothing is delivered; their
+ * payloads are neither unpacked nor decoded, so damage inside them goes unnoticed.  The blocks of the range are decoded and appended
+ * to dst from byte 0 exactly as kz_decompress appends (a short block is followed directly by the next; the first failing block
+ * ends the call with its status, the blocks of the range in front of it delivered; a block that would start past dstCap gives
+ * -KZ_ERR_WRITE_FILE).  At firstBlock + nBlocks the call stops and reads nothing behind the range (the reference still reads that
+ * block's bits before it drops it: INTEGRATION 4).  If the end marker comes first, the call returns what it produced, possibly 0.
+ *
+ * The INDEXED form takes (blockBitOff[i], blockBits[i]) pairs as kz_knz_index / kz_knz_index_device return them: any subset, in any
+ * order, with repeats.  Block i is decoded into row dst + i * dstStride; results[i] carries status and length as kz_decode_blocks
+ * fills them.  Nothing is walked: its cost does not depend on where the blocks lie in the stream.  The index is the caller's and is
+ * not trusted: before anything is unpacked every entry is checked against the stream, each on its own (the kernel k_knz_check on
+ * the device): W = blockBits[i] > 0; blockBitOff[i] at least 8 bits behind the stream header; blockBitOff[i] + W <= 8 n; and some
+ * lr in 3 .. 34 for which the 5 + lr bits in front of blockBitOff[i] lie behind the stream header and read (lr - 3, W), that is,
+ * the walk could have produced the entry at this place.  The check gives memory safety (nothing outside src is read, no row is
+ * written past dstStride); it does NOT prove that an entry lies on the true chain of prefixes: bits inside a payload that look like
+ * a prefix are accepted, and what follows them is decoded, as a rule into a per-block fault.
+ *
+ *   addresses   src / d_src and dst / d_dst: any address, any alignment; they must not overlap.  blockBitOff, blockBits and results
+ *               are host arrays in all four calls.
+ *   read        nothing outside src[0 .. n).
+ *   written     range: nothing outside dst[0 .. dstCap); dst[0 .. returned size) is specified, the rest is not.  indexed: nothing
+ *               outside dst[0 .. nBlocks * dstStride), and of row i nothing behind its first blockSize bytes; a row holds
+ *               results[i].length bytes, the rest of its first blockSize bytes is unspecified (kz_decode_blocks's contract); rows of
+ *               entries that were left out of the decode are untouched.
+ *   returns     range: bytes produced, or a negative code: the stream header's as from kz_decompress (same kz_last_error texts),
+ *               -KZ_ERR_INVALID_PARAM for firstBlock < 0 or nBlocks < 0; nBlocks == 0 returns 0 after the header checks.
+ *               indexed: 0, or a negative code for faults of the call: the stream header's, -KZ_ERR_INVALID_PARAM for
+ *               dstStride < the stream's block size, for bad arguments, and for the first entry that does not match the stream
+ *               (kz_last_error: "index entry %d does not match the stream"; dst untouched), -KZ_ERR_DEVICE.  A fault of one block
+ *               (its header precheck, the staging-row bound, its decode) goes to results[i].status; the other entries are decoded.
+ *               The transform word, entropy id, block size and checksum kind come from the stream header; the context's checksum
+ *               setting is the stream's for the call and restored after it.
+ *   chunks      range: kz_decompress_device's chunks from firstBlock on, so a destination that is too small cuts the range where
+ *               kz_decompress cuts a stream made of the range's blocks alone.  indexed: chunks of kz_compress_device's size; host
+ *               memory proportional to nBlocks (8 bytes per entry) is used besides.  KZ_STREAM_CHUNK=<blocks> overrides both.
+ *   stream      the calls are synchronous and run on the context's stream.
+ */
+int64_t kz_decompress_range(kz_ctx* ctx, const uint8_t* src, int64_t n, int64_t firstBlock, int64_t nBlocks,
+                            uint8_t* dst, int64_t dstCap);
+int64_t kz_decompress_range_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, int64_t firstBlock, int64_t nBlocks,
+                                   uint8_t* d_dst, int64_t dstCap);
+int32_t kz_decode_indexed(kz_ctx* ctx, const uint8_t* src, int64_t n,
+                          const int64_t* blockBitOff, const int64_t* blockBits, int32_t nBlocks,
+                          uint8_t* dst, int64_t dstStride, kz_block_result* results);
+int32_t kz_decode_indexed_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n,
+                                 const int64_t* blockBitOff /* host */, const int64_t* blockBits /* host */, int32_t nBlocks,
+                                 uint8_t* d_dst, int64_t dstStride, kz_block_result* results /* host */);
+
 /* ---- instrumentation (bench.py / roofline) ----------------------------------------------------- */
 /* blocks that went through a TEXT / UTF stage on a HOST thread since the last reset (process-wide counter; inverse = 0: forward,
  * 1: inverse).  The stage timers KZ_STAGE_HOST_FWD / _INV measure the TEXT / UTF stage's wall time INCLUDING its device forms

@@ -114,6 +114,10 @@ def load_library():
         "kz_decompress_device": (c.c_int64, [vp, u8p, c.c_int64, u8p, c.c_int64]),
         "kz_knz_assemble_device": (c.c_int64, [vp, c.c_uint64, c.c_uint32, c.c_int32, c.c_int64, c.c_int32, u8p, c.c_int64, i64p, c.c_int32, u8p, c.c_int64]),
         "kz_knz_index_device": (c.c_int32, [vp, u8p, c.c_int64, vp, vp, vp, vp, vp, i64p, i64p, c.c_int32]),
+        "kz_decompress_range": (c.c_int64, [vp, u8p, c.c_int64, c.c_int64, c.c_int64, u8p, c.c_int64]),
+        "kz_decompress_range_device": (c.c_int64, [vp, u8p, c.c_int64, c.c_int64, c.c_int64, u8p, c.c_int64]),
+        "kz_decode_indexed": (c.c_int32, [vp, u8p, c.c_int64, i64p, i64p, c.c_int32, u8p, c.c_int64, vp]),
+        "kz_decode_indexed_device": (c.c_int32, [vp, u8p, c.c_int64, i64p, i64p, c.c_int32, u8p, c.c_int64, vp]),
         "kz_set_timing": (None, [vp, c.c_int32]),
         "kz_get_stage_count": (c.c_int32, [vp]),
         "kz_get_stage_ms": (c.c_float, [vp, c.c_int32]),
@@ -142,6 +146,7 @@ ABI_SYMBOLS = ["kz_abi_version", "kz_ctx_create", "kz_ctx_destroy", "kz_last_err
                "kz_max_block_stream_bytes", "kz_submit_encode_blocks", "kz_submit_decode_blocks", "kz_wait", "kz_poll", "kz_compress", "kz_decompress", "kz_compress_bound", "kz_transform_type",
                "kz_knz_assemble", "kz_knz_index", "kz_knz_writer_open", "kz_knz_writer_add", "kz_knz_writer_close",
                "kz_compress_device", "kz_decompress_device", "kz_knz_assemble_device", "kz_knz_index_device",
+               "kz_decompress_range", "kz_decompress_range_device", "kz_decode_indexed", "kz_decode_indexed_device",
                "kz_set_timing", "kz_get_stage_count", "kz_get_stage_ms", "kz_get_stage_alg_bytes", "kz_reset_timing",
                "kz_set_kernel_timing", "kz_get_kernel_count", "kz_get_kernel_name", "kz_get_kernel_ms", "kz_get_kernel_max_ms",
                "kz_get_kernel_launches", "kz_reset_kernel_timing"]
@@ -678,16 +683,26 @@ class CompressedOutputStream:
 
 
 class CompressedInputStream:
-    """K/io/CompressedInputStream.java: read() the whole decoded stream."""
+    """K/io/CompressedInputStream.java: read() the whole decoded stream, or with from_block / to_block (the reference's context
+    entries "from" / "to", :1193-1200: block ids from 1, `to` excluded) the blocks from_block .. to_block - 1, through
+    kz_decompress_range."""
 
-    def __init__(self, ctx, data):
+    def __init__(self, ctx, data, from_block=None, to_block=None):
         self.ctx, self.data = ctx, bytes(data)
+        if (from_block is not None and from_block < 1) or (to_block is not None and to_block < (from_block or 1)):
+            raise ValueError("from_block >= 1 and to_block >= from_block are needed")
+        self.from_block, self.to_block = from_block, to_block
 
     def read(self, max_size=None):
         src = np.frombuffer(self.data + b"\0" * 16, dtype=np.uint8)
         cap = max_size if max_size is not None else self._declared_size()
         dst = np.empty(max(cap, 1), dtype=np.uint8)
-        rc = self.ctx.lib.kz_decompress(self.ctx.h, src.ctypes.data, len(self.data), dst.ctypes.data, cap)
+        if self.from_block is None and self.to_block is None:
+            rc = self.ctx.lib.kz_decompress(self.ctx.h, src.ctypes.data, len(self.data), dst.ctypes.data, cap)
+        else:
+            first = (self.from_block or 1) - 1
+            count = _ALL_BLOCKS if self.to_block is None else self.to_block - 1 - first
+            rc = self.ctx.lib.kz_decompress_range(self.ctx.h, src.ctypes.data, len(self.data), first, count, dst.ctypes.data, cap)
         self.ctx.check(rc)
         return dst[:rc].tobytes()
 
@@ -870,6 +885,131 @@ def decompress_tensor(ctx, knz, out=None):
     dst = _byte_view(out)
     size = decompress_device(ctx, src.data_ptr(), n, dst.data_ptr(), dst.numel())
     return dst[:size]
+
+
+# ---- seekable streams: a block range (the reference's from / to), or blocks by an index ----
+_ALL_BLOCKS = 1 << 62
+
+
+def decompress_range(ctx, data, first, count, cap=None):
+    """kz_decompress_range: blocks first .. first + count - 1 (numbered from 0) of the .knz bytes `data` -> their decoded bytes.  The
+    prefixes in front of `first` are walked, so the cost grows with `first`; cap defaults to count blocks of the stream's size."""
+    data = bytes(data)
+    if cap is None:
+        idx = knz_index(data)
+        cap = max(min(int(count), max(len(idx["blocks"]) - int(first), 0)), 0) * idx["blockSize"]
+    src = np.frombuffer(data + b"\0" * 16, dtype=np.uint8)
+    dst = np.empty(max(int(cap), 1), dtype=np.uint8)
+    rc = ctx.check(ctx.lib.kz_decompress_range(ctx.h, src.ctypes.data, len(data), int(first), int(count), dst.ctypes.data, int(cap)))
+    return dst[:rc].tobytes()
+
+
+def decompress_range_device(ctx, src, n, first, count, dst, cap):
+    """kz_decompress_range_device: the same with the stream at device address `src` (n bytes) and the destination at device address
+    `dst` (capacity cap) -> bytes produced."""
+    return int(ctx.check(ctx.lib.kz_decompress_range_device(ctx.h, _ptr(src), int(n), int(first), int(count), _ptr(dst), int(cap))))
+
+
+def _indexed(fn, ctx, src, n, offsets, bits, dst, stride):
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    w = np.ascontiguousarray(bits, dtype=np.int64)
+    if len(off) != len(w):
+        raise ValueError("offsets and bits differ in length")
+    res = (BlockResult * max(len(off), 1))()
+    ctx.check(fn(ctx.h, src, int(n), off.ctypes.data if len(off) else None, w.ctypes.data if len(w) else None, len(off),
+                 dst, int(stride), ctypes.addressof(res)))
+    return res
+
+
+def decode_indexed(ctx, data, offsets, bits, stride=None):
+    """kz_decode_indexed: the blocks of the .knz bytes `data` named by (bit offset, bit length) pairs as knz_index returns them, any
+    subset in any order -> (uint8 array [len(offsets), stride], BlockResult array).  A block's fault is in its result's status; an
+    entry that does not match the stream raises KanziError(18)."""
+    data = bytes(data)
+    if stride is None:
+        stride = knz_index(data)["blockSize"]
+    src = np.frombuffer(data + b"\0" * 16, dtype=np.uint8)
+    out = np.zeros((len(offsets), int(stride)), dtype=np.uint8)
+    res = _indexed(ctx.lib.kz_decode_indexed, ctx, src.ctypes.data, len(data), offsets, bits, out.ctypes.data if out.size else src.ctypes.data, stride)
+    return out, res
+
+
+def decode_indexed_device(ctx, src, n, offsets, bits, dst, stride):
+    """kz_decode_indexed_device: the same with the stream at device address `src` (n bytes); block i goes to device address
+    dst + i * stride -> BlockResult array (host)."""
+    return _indexed(ctx.lib.kz_decode_indexed_device, ctx, _ptr(src), n, offsets, bits, _ptr(dst), stride)
+
+
+class KnzReader:
+    """Random access to a .knz stream held as bytes or as a torch.uint8 device tensor: the index is built once (knz_index /
+    knz_index_device, the one serial walk), every read after that goes through the indexed call and costs the same wherever its
+    blocks lie.  Reads of a device stream return device tensors, reads of bytes return bytes."""
+
+    def __init__(self, ctx, knz):
+        self.ctx = ctx
+        self.device = not isinstance(knz, (bytes, bytearray, memoryview))
+        if self.device:
+            import torch
+            self.src = _byte_view(knz)
+            torch.cuda.current_stream(knz.device).synchronize()      # the calls run on the context's own stream
+            idx = knz_index_device(ctx, self.src.data_ptr(), self.src.numel())
+        else:
+            self.src = bytes(knz)
+            idx = knz_index(self.src)
+        self.index = idx
+        self.block_size = idx["blockSize"]
+        self.blocks = idx["blocks"]
+
+    def _decode(self, ids):
+        """-> (rows, results): rows[i] indexable by byte range, block_size apart"""
+        ids = [int(i) for i in ids]
+        for i in ids:
+            if not 0 <= i < len(self.blocks):
+                raise IndexError("block %d of %d" % (i, len(self.blocks)))
+        offs, bits = [self.blocks[i][0] for i in ids], [self.blocks[i][1] for i in ids]
+        if self.device:
+            import torch
+            out = torch.empty((max(len(ids), 1), self.block_size), dtype=torch.uint8, device=self.src.device)
+            res = decode_indexed_device(self.ctx, self.src.data_ptr(), self.src.numel(), offs, bits, out.data_ptr(), self.block_size)
+        else:
+            out, res = decode_indexed(self.ctx, self.src, offs, bits, self.block_size)
+        for k, i in enumerate(ids):
+            if res[k].status:
+                raise KanziError(-res[k].status, "block %d" % i)
+        return out, res
+
+    def read_blocks(self, ids):
+        """the decoded blocks `ids` (any order, repeats allowed) -> a list of bytes, or of device tensors"""
+        ids = list(ids)
+        if not ids:
+            return []
+        out, res = self._decode(ids)
+        return [out[k, :res[k].length] if self.device else out[k, :res[k].length].tobytes() for k in range(len(ids))]
+
+    def read_at(self, offset, size):
+        """bytes [offset, offset + size) of the original data (cut at its end, as a slice is).  Byte addresses are offset //
+        blockSize: a covering block other than the stream's last that decodes to fewer than blockSize bytes raises KanziError."""
+        offset, size = int(offset), int(size)
+        if offset < 0 or size < 0:
+            raise ValueError("offset and size must not be negative")
+        bs, nb = self.block_size, len(self.blocks)
+        b0, b1 = offset // bs, min((offset + size - 1) // bs, nb - 1)
+        if size == 0 or b0 > b1:
+            if self.device:
+                import torch
+                return torch.empty(0, dtype=torch.uint8, device=self.src.device)
+            return b""
+        out, res = self._decode(range(b0, b1 + 1))
+        for k in range(b1 - b0 + 1):
+            if res[k].length < bs and b0 + k != nb - 1:
+                raise KanziError(15, "block %d decodes to %d bytes, fewer than the block size %d: the stream has no byte addressing"
+                                 % (b0 + k, res[k].length, bs))
+        have = (b1 - b0) * bs + res[b1 - b0].length               # bytes of the covering blocks, back to back in `out`
+        lo, hi = offset - b0 * bs, min(offset - b0 * bs + size, have)
+        flat = out.reshape(-1)
+        if self.device:
+            return flat[lo:max(hi, lo)].clone()
+        return flat[lo:max(hi, lo)].tobytes()
 
 
 def usable_cpus():

@@ -46,7 +46,8 @@
   X(KID_RANGE_DEC, "k_range_dec") X(KID_CM_ENC, "k_cm_enc") X(KID_CM_DEC, "k_cm_dec") X(KID_LZP_FWD, "k_lzp_fwd") \
   X(KID_LZP_INV, "k_lzp_inv") X(KID_EXE_SETUP, "k_exe_setup") X(KID_EXE_MAP, "k_exe_map") X(KID_EXE_SCAN, "k_exe_scan") \
   X(KID_EXE_HIST, "k_exe_hist") X(KID_EXE_DECIDE, "k_exe_decide") X(KID_EXE_SIZE, "k_exe_size") X(KID_EXE_VERDICT, "k_exe_verdict") \
-  X(KID_EXE_EMIT, "k_exe_emit") X(KID_KNZ_PACK, "k_knz_pack") X(KID_KNZ_WALK, "k_knz_walk") X(KID_KNZ_UNPACK, "k_knz_unpack")
+  X(KID_EXE_EMIT, "k_exe_emit") X(KID_KNZ_PACK, "k_knz_pack") X(KID_KNZ_WALK, "k_knz_walk") X(KID_KNZ_UNPACK, "k_knz_unpack") \
+  X(KID_KNZ_CHECK, "k_knz_check")
 #define KZ_KERNEL_ENUM(id, name) id,
 #define KZ_KERNEL_NAME(id, name) name,
 enum KzKernelId { KZ_KERNELS(KZ_KERNEL_ENUM) KID_COUNT };
@@ -313,6 +314,7 @@ struct KnzBlk { int64_t pay, bits, src; };   // a block in the container: bit of
 enum { KNZ_WALK_COUNT = 0, KNZ_WALK_END = 1, KNZ_WALK_PREFIX = 2, KNZ_WALK_PAYLOAD = 3 };
 int kz_knz_pack(kz_ctx*, const uint8_t* d_rows, const KnzBlk* d_blk, int nb, uint8_t* d_dst, int64_t startBit, int64_t endBit);
 int kz_knz_walk(kz_ctx*, const uint8_t* d_src, int64_t n, int64_t startBit, int maxCount, int64_t* d_off, int64_t* d_bits, uint64_t* d_hdr, int64_t* d_res);
+int kz_knz_check(kz_ctx*, const uint8_t* d_src, int64_t n, int64_t hdrEnd, const int64_t* d_off, const int64_t* d_bits, int nb, uint64_t* d_hdr, int64_t* d_bad);
 int kz_knz_unpack(kz_ctx*, const uint8_t* d_src, int64_t n, const int64_t* d_off, const int64_t* d_bits, int nb, int64_t maxBytes, uint8_t* d_rows, int64_t stride);
 
 // timing helpers

@@ -1,8 +1,9 @@
 // kz_knz_gpu.hip -- the .knz container on device memory: the bit-granular concatenation of block streams
 // (K/io/CompressedOutputStream.java:1024-1035) as a copy kernel, its inverse, and the serial walk of the block length
-// prefixes (K/io/CompressedInputStream.java:1127-1129).  The callers (kz_compress_device / kz_decompress_device /
-// kz_knz_assemble_device / kz_knz_index_device, kz_stream.hip) do the bit-offset arithmetic, the stream header and the
-// block-header prechecks on the host; no payload byte leaves the device.
+// prefixes (K/io/CompressedInputStream.java:1127-1129), and the check of a caller's index entries that stands in for the walk in
+// the indexed reads.  The callers (kz_compress_device / kz_decompress_device / kz_decompress_range_device /
+// kz_decode_indexed_device / kz_knz_assemble_device / kz_knz_index_device, kz_stream.hip) do the bit-offset arithmetic, the stream
+// header and the block-header prechecks on the host; no payload byte leaves the device.
 #include "kz_device.h"
 #include "kz_internal.h"
 #include <algorithm>
@@ -142,6 +143,34 @@ __global__ void k_knz_walk(const u8* __restrict__ src, int64_t n, int64_t startB
   res[0] = cnt; res[1] = pos; res[2] = why;
 }
 
+// ---- check: index entries against the stream, each on its own ------------------------------------------------------------------
+// One lane per entry (off[i], bits[i]) of a caller's index.  bad[i] = 0 if the walk could have recorded the entry at this place:
+// W = bits[i] > 0, the payload [off, off + W) inside the 8 n bits of src, and for some lr in 3 .. 34 the 5 + lr bits in front of off
+// lie at or behind bit hdrEnd (the end of the stream header) and read (lr - 3, W); else 1.  hdr[i] = the payload's first 8 bytes,
+// left aligned, as the walk gives them (0 for a bad entry).  That makes k_knz_unpack and the decoders safe on the entry; it does
+// not prove that the entry lies on the chain of prefixes from hdrEnd.  Nothing outside src[0 .. n) is read: hdrEnd >= 160, so the
+// 39 bits in front of a good off start inside src, and knz_peek64 reads bytes at and behind src[n] as zero.
+__global__ void __launch_bounds__(256) k_knz_check(const u8* __restrict__ src, int64_t n, int64_t hdrEnd, const int64_t* __restrict__ off,
+                                                   const int64_t* __restrict__ bits, int nb, u64* __restrict__ hdr, int64_t* __restrict__ bad) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nb) return;
+  const int64_t nbits = n << 3, W = bits[i], o = off[i];
+  bool ok = W > 0 && W < (1ll << 34) && o >= hdrEnd + 8 && o >= 39 && o <= nbits && W <= nbits - o;
+  u64 h = 0;
+  if (ok) {
+    const u64 x = knz_peek64(src, n, o - 39) >> 25;                                   // the 39 bits in front of o
+    ok = false;
+    for (int lr = 64 - __clzll((long long)W) < 3 ? 3 : 64 - __clzll((long long)W); lr <= 34; lr++) {
+      if (o - 5 - lr < hdrEnd) break;
+      const u64 f = x & ((1ull << (5 + lr)) - 1);
+      if ((int)(f >> lr) + 3 == lr && (int64_t)(f & ((1ull << lr) - 1)) == W) { ok = true; break; }
+    }
+    if (ok) h = knz_peek64(src, n, o);
+  }
+  hdr[i] = h;
+  bad[i] = ok ? 0 : 1;
+}
+
 // ---- unpack: container -> byte-aligned rows ------------------------------------------------------------------------------------
 // Row i (rows + i * stride, 16-byte aligned) gets the bits[i] bits from bit off[i] of src, in 16-byte units; the bits behind them in
 // the last unit are zero (rows carry KZ_STREAM_SLACK bytes behind their streams).  Nothing outside src[0 .. n) is read: units
@@ -201,6 +230,12 @@ int kz_knz_pack(kz_ctx* ctx, const uint8_t* d_rows, const KnzBlk* d_blk, int nb,
 }
 int kz_knz_walk(kz_ctx* ctx, const uint8_t* d_src, int64_t n, int64_t startBit, int maxCount, int64_t* d_off, int64_t* d_bits, uint64_t* d_hdr, int64_t* d_res) {
   KZ_LAUNCH(ctx, KID_KNZ_WALK, k_knz_walk, dim3(1), dim3(64), d_src, n, startBit, maxCount, d_off, d_bits, (u64*)d_hdr, d_res);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_check(kz_ctx* ctx, const uint8_t* d_src, int64_t n, int64_t hdrEnd, const int64_t* d_off, const int64_t* d_bits, int nb, uint64_t* d_hdr, int64_t* d_bad) {
+  if (nb <= 0) return 0;
+  KZ_LAUNCH(ctx, KID_KNZ_CHECK, k_knz_check, dim3((nb + 255) / 256), dim3(256), d_src, n, hdrEnd, d_off, d_bits, nb, (u64*)d_hdr, d_bad);
   KZ_HIP(hipGetLastError());
   return 0;
 }

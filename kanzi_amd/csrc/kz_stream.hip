@@ -443,8 +443,10 @@ static int precheck_block_header(HostBitsIn bs /* by value: peek */, uint64_t W,
   return 0;
 }
 
-extern "C" int64_t kz_decompress(kz_ctx* ctx, const uint8_t* src, int64_t n, uint8_t* dst, int64_t dstCap) {
-  if (!ctx || !src || !dst || n < 0) return -KZ_ERR_INVALID_PARAM;
+// kz_decompress and kz_decompress_range: the blocks [firstBlock, firstBlock + nBlocks) of the stream, nBlocks < 0: from firstBlock
+// to the end marker.  Blocks in front of firstBlock get the walk's checks and nothing else; the batches, and with them the place
+// where a destination that is too small cuts the stream, start at firstBlock.
+static int64_t decompress_host(kz_ctx* ctx, const uint8_t* src, int64_t n, int64_t firstBlock, int64_t nBlocks, uint8_t* dst, int64_t dstCap) {
   KZ_HIP(hipSetDevice(ctx->device));
   HostBitsIn bs{src, (uint64_t)n * 8, 0, false};
   KnzHeader h;
@@ -462,6 +464,19 @@ extern "C" int64_t kz_decompress(kz_ctx* ctx, const uint8_t* src, int64_t n, uin
   if (szMask && inputSize > 0) NB = (int)std::min<int64_t>(NB, (inputSize + blockSize - 1) / blockSize);
   else NB = (int)std::min<int64_t>(NB, n / 8 + 1);
   const int64_t iS = (int64_t)kz_align((size_t)blockSize + (size_t)(blockSize >> 3) + 1024 + 64, 256);
+  if (nBlocks == 0) return 0;
+  for (int64_t k = 0; k < firstBlock; k++) {                      // read and skipped (:1126-1165 come before the reader looks at "from")
+    const int lr = (int)bs.get(5) + 3;
+    const uint64_t rd = bs.get(lr);
+    if (bs.error) return -KZ_ERR_READ_FILE;
+    if (rd == 0) return 0;                                        // the end marker in front of the range
+    int rc = precheck_block_header(bs, rd, nbFunctions, blockSize, chkKind);
+    if (!rc && (int64_t)((rd + 7) >> 3) > iS - 64) rc = -KZ_ERR_BLOCK_SIZE;
+    if (!rc && bs.pos + rd > bs.nbits) rc = -KZ_ERR_READ_FILE;
+    if (rc) return rc;
+    bs.pos += rd;
+  }
+  int64_t left = nBlocks < 0 ? INT64_MAX : nBlocks;               // blocks of the range not walked yet
   std::unique_ptr<uint8_t[]> inbuf;                                // (the unstaged path's strided copy of the payloads)
   std::vector<int64_t> bits(NB);
   std::vector<uint64_t> starts(NB);
@@ -474,6 +489,7 @@ extern "C" int64_t kz_decompress(kz_ctx* ctx, const uint8_t* src, int64_t n, uin
     // A fault met while walking the length prefixes is held back until the blocks before it have been decoded:
     // the reference reports the FIRST failing block in stream order (processedBlockId ordering, :1127-1170).
     while (cnt < NB) {                                          // serial walk of block length prefixes (:1127-1129)
+      if (left == 0) { done = true; break; }                    // the end of the range: nothing behind it is read
       const int lr = (int)bs.get(5) + 3;
       const uint64_t rd = bs.get(lr);
       if (bs.error) { pending = -KZ_ERR_READ_FILE; break; }
@@ -485,6 +501,7 @@ extern "C" int64_t kz_decompress(kz_ctx* ctx, const uint8_t* src, int64_t n, uin
       starts[cnt] = bs.pos;                                     // the payload is extracted below, by several threads
       bs.pos += rd;
       bits[cnt++] = (int64_t)rd;
+      left--;
     }
     if (pending) done = true;
     if (cnt == 0) break;
@@ -582,6 +599,15 @@ extern "C" int64_t kz_decompress(kz_ctx* ctx, const uint8_t* src, int64_t n, uin
     }
   }
   return pending ? pending : produced;
+}
+
+extern "C" int64_t kz_decompress(kz_ctx* ctx, const uint8_t* src, int64_t n, uint8_t* dst, int64_t dstCap) {
+  if (!ctx || !src || !dst || n < 0) return -KZ_ERR_INVALID_PARAM;
+  return decompress_host(ctx, src, n, 0, -1, dst, dstCap);
+}
+extern "C" int64_t kz_decompress_range(kz_ctx* ctx, const uint8_t* src, int64_t n, int64_t firstBlock, int64_t nBlocks, uint8_t* dst, int64_t dstCap) {
+  if (!ctx || !src || !dst || n < 0 || firstBlock < 0 || nBlocks < 0) return -KZ_ERR_INVALID_PARAM;
+  return decompress_host(ctx, src, n, firstBlock, nBlocks, dst, dstCap);
 }
 
 
@@ -766,8 +792,22 @@ extern "C" int32_t kz_knz_index_device(kz_ctx* ctx, const uint8_t* d_src, int64_
   return (int32_t)nb;
 }
 
-extern "C" int64_t kz_decompress_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, uint8_t* d_dst, int64_t dstCap) {
-  if (!ctx || !d_src || !d_dst || n < 0) return -KZ_ERR_INVALID_PARAM;
+namespace {
+// kz_decompress's checks on one walked block, in kz_decompress's order: the block header (from the 8 bytes the device brought back), the
+// staging-row bound, the end of the stream
+int knz_precheck_entry(uint64_t hdr, uint64_t rd, uint64_t at, uint64_t nbits, int nbFunctions, int blockSize, int chkKind, int64_t iS) {
+  uint8_t hb8[8];
+  for (int k = 0; k < 8; k++) hb8[k] = (uint8_t)(hdr >> (56 - 8 * k));
+  HostBitsIn t{hb8, std::min<uint64_t>(64, nbits - at), 0, false};             // the header is 7 bytes at the most
+  int rc = precheck_block_header(t, rd, nbFunctions, blockSize, chkKind);
+  if (!rc && (int64_t)((rd + 7) >> 3) > iS - 64) rc = -KZ_ERR_BLOCK_SIZE;
+  if (!rc && at + rd > nbits) rc = -KZ_ERR_READ_FILE;
+  return rc;
+}
+}  // namespace
+
+// kz_decompress_device and kz_decompress_range_device: decompress_host's contract, source and destination in HBM
+static int64_t decompress_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, int64_t firstBlock, int64_t nBlocks, uint8_t* d_dst, int64_t dstCap) {
   KZ_HIP(hipSetDevice(ctx->device));
   uint8_t hdr[32]; int64_t hn = 0;
   { const int rc = knz_get_header(ctx, d_src, n, hdr, hn); if (rc) return rc; }
@@ -794,20 +834,41 @@ extern "C" int64_t kz_decompress_device(kz_ctx* ctx, const uint8_t* d_src, int64
   else NB = std::min<int64_t>(NB, n / 8 + 1);
   const int CH = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->sw.streamChunk > 0 ? ctx->sw.streamChunk : NB, std::min<int64_t>(NB, KZ_MAX_BATCH)));
   const int64_t iS = (int64_t)kz_align((size_t)blockSize + (size_t)(blockSize >> 3) + 1024 + 64, 256);
-  { const int rc = knz_tables(ctx, (size_t)CH, 24); if (rc) return rc; }
-  KnzWalk T; T.bind(ctx, CH);
-  std::vector<kz_block_result> res(CH);
+  if (nBlocks == 0) return 0;
+  // blocks in front of the range are walked in the index call's chunks (the walk is all that happens to them), unless
+  // KZ_STREAM_CHUNK says otherwise
+  const int SK = firstBlock == 0 ? 0 : (ctx->sw.streamChunk > 0 ? CH : (int)std::min<int64_t>(16384, n / 8 + 16));
+  { const int rc = knz_tables(ctx, (size_t)std::max(CH, SK), 24); if (rc) return rc; }
+  KnzWalk T;
   int64_t pos = (int64_t)bs.pos, produced = 0;
+  if (SK) T.bind(ctx, SK);
+  for (int64_t k = 0; k < firstBlock;) {                         // read and skipped: prefix and block header, not the payload
+    { const int rc = knz_walk_chunk(ctx, T, d_src, n, pos, (int)std::min<int64_t>(SK, firstBlock - k), 3); if (rc) return rc; }
+    const int why = (int)T.res[2];
+    const int have = (int)T.res[0] + (why == KNZ_WALK_PAYLOAD ? 1 : 0);
+    for (int i = 0; i < have; i++) {
+      const int rc = knz_precheck_entry(T.hdr[i], (uint64_t)T.bits[i], (uint64_t)T.off[i], nbits, nbFunctions, blockSize, chkKind, iS);
+      if (rc) return rc;
+    }
+    if (why == KNZ_WALK_PREFIX) return -KZ_ERR_READ_FILE;
+    if (why == KNZ_WALK_END) return 0;                            // the end marker in front of the range
+    pos = T.res[1];
+    k += have;
+  }
+  T.bind(ctx, CH);
+  std::vector<kz_block_result> res(CH);
   bool done = false;
   int pending = 0;
   int64_t batchLeft = 0, fitLeft = 0;
+  int64_t left = nBlocks < 0 ? INT64_MAX : nBlocks;               // blocks of the range not walked yet
   while (!done) {
+    if (left == 0) break;                                         // the end of the range: nothing behind it is read
     if (batchLeft == 0) {
       batchLeft = NB;
       const int64_t room = dstCap - produced;
       fitLeft = (room <= 0) ? 0 : (room + blockSize - 1) / blockSize;
     }
-    const int want = (int)std::min<int64_t>(CH, batchLeft);
+    const int want = (int)std::min<int64_t>(std::min<int64_t>(CH, batchLeft), left);
     // ---- the walk on the device, then kz_decompress's checks in kz_decompress's order on what it recorded.  A fault met here is
     //      held back until the blocks before it have been decoded: the reference reports the FIRST failing block in stream order ----
     { const int rc = knz_walk_chunk(ctx, T, d_src, n, pos, want, 3); if (rc) return rc; }
@@ -816,15 +877,10 @@ extern "C" int64_t kz_decompress_device(kz_ctx* ctx, const uint8_t* d_src, int64
     pos = T.res[1];
     int cnt = 0;
     for (; cnt < have; cnt++) {
-      const uint64_t rd = (uint64_t)T.bits[cnt], at = (uint64_t)T.off[cnt];
-      uint8_t hb8[8];
-      for (int k = 0; k < 8; k++) hb8[k] = (uint8_t)(T.hdr[cnt] >> (56 - 8 * k));
-      HostBitsIn t{hb8, std::min<uint64_t>(64, nbits - at), 0, false};         // the header is 7 bytes at the most
-      pending = precheck_block_header(t, rd, nbFunctions, blockSize, chkKind);
-      if (!pending && (int64_t)((rd + 7) >> 3) > iS - 64) pending = -KZ_ERR_BLOCK_SIZE;
-      if (!pending && at + rd > nbits) pending = -KZ_ERR_READ_FILE;
+      pending = knz_precheck_entry(T.hdr[cnt], (uint64_t)T.bits[cnt], (uint64_t)T.off[cnt], nbits, nbFunctions, blockSize, chkKind, iS);
       if (pending) break;
     }
+    left -= cnt;
     if (!pending) { if (why == KNZ_WALK_PREFIX) pending = -KZ_ERR_READ_FILE; else if (why == KNZ_WALK_END) done = true; }
     if (pending) done = true;
     if (cnt == 0) break;
@@ -870,4 +926,171 @@ extern "C" int64_t kz_decompress_device(kz_ctx* ctx, const uint8_t* d_src, int64
     if (code) return code;
   }
   return pending ? pending : produced;
+}
+
+extern "C" int64_t kz_decompress_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, uint8_t* d_dst, int64_t dstCap) {
+  if (!ctx || !d_src || !d_dst || n < 0) return -KZ_ERR_INVALID_PARAM;
+  return decompress_device(ctx, d_src, n, 0, -1, d_dst, dstCap);
+}
+extern "C" int64_t kz_decompress_range_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, int64_t firstBlock, int64_t nBlocks, uint8_t* d_dst, int64_t dstCap) {
+  if (!ctx || !d_src || !d_dst || n < 0 || firstBlock < 0 || nBlocks < 0) return -KZ_ERR_INVALID_PARAM;
+  return decompress_device(ctx, d_src, n, firstBlock, nBlocks, d_dst, dstCap);
+}
+
+
+// =================================================================================================
+// indexed reads: blocks of a stream by their (bit offset, bit length) pairs, as kz_knz_index / kz_knz_index_device return them, in
+// any order.  No walk: every pair is checked against the stream on its own (k_knz_check on the device, knz_check_entry here), which
+// makes the call memory safe for any index and brings the block-header bytes for the prechecks; it does not prove that a pair lies
+// on the chain of prefixes that starts behind the stream header.
+namespace {
+// the 5 + lr bits in front of bit `off` read (lr - 3, W) for some lr in 3 .. 34, and lie behind bit hdrEnd; W > 0 ends inside the stream
+bool knz_check_entry(const uint8_t* src, int64_t n, int64_t hdrEnd, int64_t off, int64_t W) {
+  const int64_t nbits = n * 8;
+  if (W <= 0 || W >= (1LL << 34) || off < hdrEnd + 8 || off > nbits || W > nbits - off) return false;
+  const int lo = std::max(3, 64 - __builtin_clzll((unsigned long long)W));
+  for (int lr = lo; lr <= 34; lr++) {
+    const int64_t at = off - 5 - lr;
+    if (at < hdrEnd) break;
+    HostBitsIn t{src, (uint64_t)nbits, (uint64_t)at, false};
+    if ((int)t.get(5) + 3 == lr && (int64_t)t.get(lr) == W) return true;
+  }
+  return false;
+}
+struct IndexedCall {                                               // what both forms take from the stream header
+  KnzHeader h; int nbFunctions; int64_t hdrEnd, iS; int CH;
+};
+int indexed_open(kz_ctx* ctx, HostBitsIn& bs, int64_t dstStride, IndexedCall& c) {
+  { const int hrc = read_stream_header(bs, c.h, ctx->err, sizeof(ctx->err)); if (hrc) return hrc; }
+  if (dstStride < c.h.blockSize) {
+    snprintf(ctx->err, sizeof(ctx->err), "dstStride %lld is less than the stream's block size %d", (long long)dstStride, c.h.blockSize);
+    return -KZ_ERR_INVALID_PARAM;
+  }
+  c.nbFunctions = 0;
+  for (int i = 0; i < 8; i++) if (((c.h.transformType >> (42 - 6 * i)) & 0x3F) != 0) c.nbFunctions++;
+  if (c.nbFunctions == 0) c.nbFunctions = 1;
+  c.hdrEnd = (int64_t)bs.pos;
+  c.iS = (int64_t)kz_align((size_t)c.h.blockSize + (size_t)(c.h.blockSize >> 3) + 1024 + 64, 256);
+  c.CH = knz_chunk_blocks(ctx, c.h.blockSize);
+  return 0;
+}
+int indexed_mismatch(kz_ctx* ctx, int64_t i) {
+  snprintf(ctx->err, sizeof(ctx->err), "index entry %lld does not match the stream", (long long)i);
+  return -KZ_ERR_INVALID_PARAM;
+}
+// Decode the chunk's entries that passed their prechecks (res[i].status == 0 on entry), rows `iS` apart at `rows`, into out rows
+// `dstStride` apart: one kz_decode_blocks call per run of neighbours, so that every block lands in its own row.
+int indexed_decode_runs(kz_ctx* ctx, const IndexedCall& c, const uint8_t* rows, const int64_t* W, int cnt, uint8_t* out, int64_t dstStride,
+                        kz_block_result* res, int memKind) {
+  for (int i = 0; i < cnt;) {
+    if (res[i].status) { i++; continue; }
+    int j = i + 1;
+    while (j < cnt && !res[j].status) j++;
+    const int rc = kz_decode_blocks(ctx, c.h.transformType, (uint32_t)c.h.entropyType, c.h.blockSize, rows + (int64_t)i * c.iS, c.iS, W + i, j - i,
+                                    out + (int64_t)i * dstStride, dstStride, res + i, memKind);
+    if (rc) return rc;
+    i = j;
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int32_t kz_decode_indexed(kz_ctx* ctx, const uint8_t* src, int64_t n, const int64_t* blockBitOff, const int64_t* blockBits, int32_t nBlocks,
+                                     uint8_t* dst, int64_t dstStride, kz_block_result* results) {
+  if (!ctx || !src || n < 0 || nBlocks < 0 || (nBlocks > 0 && (!blockBitOff || !blockBits || !dst || !results))) return -KZ_ERR_INVALID_PARAM;
+  KZ_HIP(hipSetDevice(ctx->device));
+  HostBitsIn bs{src, (uint64_t)n * 8, 0, false};
+  IndexedCall c;
+  { const int rc = indexed_open(ctx, bs, dstStride, c); if (rc) return rc; }
+  if (nBlocks == 0) return 0;
+  for (int64_t i = 0; i < nBlocks; i++) if (!knz_check_entry(src, n, c.hdrEnd, blockBitOff[i], blockBits[i])) return indexed_mismatch(ctx, i);
+  const int savedChk = ctx->checksum;
+  ctx->checksum = c.h.chkKind;
+  struct Restore { kz_ctx* c; int v; ~Restore() { c->checksum = v; } } restore_{ctx, savedChk};
+  const int CH = (int)std::min<int64_t>(c.CH, nBlocks);
+  std::unique_ptr<uint8_t[]> inbuf(new uint8_t[(size_t)c.iS * CH]);
+  for (int64_t b0 = 0; b0 < nBlocks; b0 += CH) {
+    const int cnt = (int)std::min<int64_t>(CH, nBlocks - b0);
+    const int64_t* off = blockBitOff + b0; const int64_t* W = blockBits + b0;
+    kz_block_result* res = results + b0;
+    for (int i = 0; i < cnt; i++) {
+      HostBitsIn t = bs; t.pos = (uint64_t)off[i]; t.error = false;
+      int rc = precheck_block_header(t, (uint64_t)W[i], c.nbFunctions, c.h.blockSize, c.h.chkKind);
+      if (!rc && ((W[i] + 7) >> 3) > c.iS - 64) rc = -KZ_ERR_BLOCK_SIZE;
+      memset(&res[i], 0, sizeof(res[i]));
+      res[i].bits = W[i]; res[i].status = rc;
+    }
+    parallel_blocks(cnt, [&](int i) {
+      if (res[i].status) return;
+      HostBitsIn t = bs; t.pos = (uint64_t)off[i]; t.error = false; t.getBytes(inbuf.get() + (size_t)i * c.iS, (uint64_t)W[i]);
+    });
+    const int rc = indexed_decode_runs(ctx, c, inbuf.get(), W, cnt, dst + b0 * dstStride, dstStride, res, KZ_MEM_HOST);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+extern "C" int32_t kz_decode_indexed_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, const int64_t* blockBitOff, const int64_t* blockBits, int32_t nBlocks,
+                                            uint8_t* d_dst, int64_t dstStride, kz_block_result* results) {
+  if (!ctx || !d_src || n < 0 || nBlocks < 0 || (nBlocks > 0 && (!blockBitOff || !blockBits || !d_dst || !results))) return -KZ_ERR_INVALID_PARAM;
+  KZ_HIP(hipSetDevice(ctx->device));
+  uint8_t hdr[32]; int64_t hn = 0;
+  { const int rc = knz_get_header(ctx, d_src, n, hdr, hn); if (rc) return rc; }
+  HostBitsIn bs{hdr, (uint64_t)hn * 8, 0, false};
+  IndexedCall c;
+  { const int rc = indexed_open(ctx, bs, dstStride, c); if (rc) return rc; }
+  if (nBlocks == 0) return 0;
+  const int savedChk = ctx->checksum;
+  ctx->checksum = c.h.chkKind;
+  struct Restore { kz_ctx* c; int v; ~Restore() { c->checksum = v; } } restore_{ctx, savedChk};
+  const int CH = (int)std::min<int64_t>(c.CH, nBlocks);
+  // the chunk's tables, pinned and in HBM: 64 spare bytes, then off[CH], bits[CH], hdr[CH], bad[CH]
+  { const int rc = knz_tables(ctx, (size_t)CH, 32); if (rc) return rc; }
+  int64_t* p_off = (int64_t*)(ctx->knzPin.p + 64); int64_t* p_bits = p_off + CH;
+  const uint64_t* p_hdr = (const uint64_t*)(p_bits + CH); const int64_t* p_bad = (const int64_t*)(p_hdr + CH);
+  int64_t* d_off = (int64_t*)(ctx->knzAux.p + 64); int64_t* d_bits = d_off + CH;
+  uint64_t* d_hdr = (uint64_t*)(d_bits + CH); int64_t* d_bad = (int64_t*)(d_hdr + CH);
+  // ---- every entry against the stream, before anything is unpacked; the block-header bytes stay on the host for the second pass ----
+  std::vector<uint64_t> hdrs((size_t)nBlocks);
+  for (int64_t b0 = 0; b0 < nBlocks; b0 += CH) {
+    const int cnt = (int)std::min<int64_t>(CH, nBlocks - b0);
+    memcpy(p_off, blockBitOff + b0, (size_t)cnt * 8);
+    memcpy(p_bits, blockBits + b0, (size_t)cnt * 8);
+    KZ_HIP(hipMemcpyAsync(d_off, p_off, (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+    KZ_HIP(hipMemcpyAsync(d_bits, p_bits, (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+    { const int rc = kz_knz_check(ctx, d_src, n, c.hdrEnd, d_off, d_bits, cnt, d_hdr, d_bad); if (rc) return rc; }
+    KZ_HIP(hipMemcpyAsync((void*)p_hdr, d_hdr, (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(hipMemcpyAsync((void*)p_bad, d_bad, (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+    kz_ktimer_flush(ctx);
+    for (int i = 0; i < cnt; i++) {
+      if (p_bad[i]) return indexed_mismatch(ctx, b0 + i);
+      hdrs[(size_t)(b0 + i)] = p_hdr[i];
+    }
+  }
+  // ---- chunks: prechecks on the host, unpack the entries that pass into staging rows, decode them into their rows of d_dst ----
+  const uint64_t nbits = (uint64_t)n * 8;
+  for (int64_t b0 = 0; b0 < nBlocks; b0 += CH) {
+    const int cnt = (int)std::min<int64_t>(CH, nBlocks - b0);
+    kz_block_result* res = results + b0;
+    int64_t maxBytes = 0;
+    for (int i = 0; i < cnt; i++) {
+      const int64_t W = blockBits[b0 + i];
+      const int rc = knz_precheck_entry(hdrs[(size_t)(b0 + i)], (uint64_t)W, (uint64_t)blockBitOff[b0 + i], nbits, c.nbFunctions, c.h.blockSize, c.h.chkKind, c.iS);
+      memset(&res[i], 0, sizeof(res[i]));
+      res[i].bits = W; res[i].status = rc;
+      p_off[i] = blockBitOff[b0 + i];
+      p_bits[i] = rc ? 0 : W;                                       // a row of no bits: nothing of it is unpacked
+      if (!rc) maxBytes = std::max<int64_t>(maxBytes, (W + 7) >> 3);
+    }
+    if (maxBytes == 0) continue;
+    KZ_HIP(hipMemcpyAsync(d_off, p_off, (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+    KZ_HIP(hipMemcpyAsync(d_bits, p_bits, (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+    { const int rc = stage_reserve(ctx, ctx->devIn[0], (size_t)cnt * c.iS, false); if (rc) return rc; }
+    { const int rc = kz_knz_unpack(ctx, d_src, n, d_off, d_bits, cnt, maxBytes, ctx->devIn[0].p, c.iS); if (rc) return rc; }
+    { const int rc = indexed_decode_runs(ctx, c, ctx->devIn[0].p, blockBits + b0, cnt, d_dst + b0 * dstStride, dstStride, res, KZ_MEM_DEVICE); if (rc) return rc; }
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));                      // the pinned table is the next chunk's
+    kz_ktimer_flush(ctx);
+  }
+  return 0;
 }
