@@ -324,6 +324,46 @@ int32_t kz_knz_index_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, uint64
                             int32_t* blockSize, int64_t* inputSize, int32_t* checksumBits,
                             int64_t* blockBitOff /* host */, int64_t* blockBits /* host */, int32_t cap);
 
+/* ---- many .knz streams on device memory ---------------------------------------------------------
+ * kz_compress_device / kz_decompress_device for nStreams buffers in one call: the files of a directory, the tensors of a checkpoint,
+ * the pages of a table.  Stream s is the bytes d_src[srcOff[s] .. srcOff[s] + srcLen[s]), its slot d_dst[dstOff[s] .. dstOff[s] +
+ * dstCap[s]); offsets are non-negative and relative to the two base pointers (segments in different allocations: pass the lowest
+ * address as the base).  The single-stream call is the definition of every result: dstLen[s] is what it returns for segment s and
+ * slot s alone under the same context settings, and on success the slot's first dstLen[s] bytes are its bytes.  The serial-per-block
+ * kernels take as long for one block as for thousands, so N small buffers cost about one buffer's chain here and N chains in a loop.
+ *
+ *   addresses   any address and any alignment.  The slots must not overlap each other or any source segment (the caller's duty).
+ *   read        nothing outside each stream's own segment: a stream's result depends on its own bytes only, whatever lies between
+ *               and behind the segments (every table entry of the kernels carries its own stream's bounds).
+ *   written     nothing outside each slot; what lies behind dstLen[s] inside slot s is unspecified, and slots need not be zeroed.
+ *   results     kz_compress_many_device: dstLen[s] = the stream's size, the first failing block's status, or -KZ_ERR_WRITE_FILE for
+ *               a slot that is too small (kz_compress_many_bound, the sum of kz_compress_bound, suffices for slots laid end to end);
+ *               an empty buffer gives the header and end-marker stream.  kz_decompress_many_device: dstLen[s] = the decoded size or
+ *               the stream's fault; on a fault the blocks in front of the first failing block are delivered, a short block followed
+ *               directly by the next.  Each stream's transform word, entropy id, block size and checksum kind come from its own
+ *               header: the streams of one call may differ in all four.  A fault of one stream lives in dstLen[s] only; the other
+ *               streams are coded as if it were not there.  kz_last_error: the text of the first failing stream.
+ *   returns     0, or a negative code for faults of the call itself: -KZ_ERR_INVALID_PARAM for null pointers with nStreams > 0,
+ *               nStreams < 0, or a negative offset, length or capacity; kz_compress_device's block-size code, before anything is
+ *               launched; -KZ_ERR_DEVICE.  nStreams == 0 returns 0 and touches nothing.
+ *   groups      whole streams are collected into groups of at most one chunk's blocks (kz_compress_device's chunk for the writer,
+ *               kz_decompress_device's batch for the reader, KZ_STREAM_CHUNK=<blocks> overrides both).  The blocks of a group are
+ *               one batched encode, or one batched decode per distinct header; launches and host waits per group do not grow with
+ *               the streams in it.  A stream with more blocks than a group takes goes through the single-stream call on its own.
+ *               srcOff, srcLen, dstOff, dstCap and dstLen are host arrays; host memory use is proportional to nStreams and to the
+ *               blocks of one group, device staging to one group's rows, neither to the payload.
+ *   stream      the calls are synchronous and run on the context's stream.
+ */
+int64_t kz_compress_many_bound(const int64_t* srcLen, int32_t nStreams, int32_t blockSize);   /* sum of kz_compress_bound(srcLen[s], blockSize) */
+int32_t kz_compress_many_device(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int32_t blockSize,
+                                const uint8_t* d_src, const int64_t* srcOff /* host */, const int64_t* srcLen /* host */, int32_t nStreams,
+                                uint8_t* d_dst, const int64_t* dstOff /* host */, const int64_t* dstCap /* host */,
+                                int64_t* dstLen /* host, out */);
+int32_t kz_decompress_many_device(kz_ctx* ctx,
+                                  const uint8_t* d_src, const int64_t* srcOff /* host */, const int64_t* srcLen /* host */, int32_t nStreams,
+                                  uint8_t* d_dst, const int64_t* dstOff /* host */, const int64_t* dstCap /* host */,
+                                  int64_t* dstLen /* host, out */);
+
 /* ---- seekable .knz streams: a block range, or blocks by an index ----------------------------------
  * Two ways to read part of a stream, each on host memory and on device memory (the _device forms keep kz_decompress_device's
  * memory contract).  Blocks are numbered from 0 in stream order.

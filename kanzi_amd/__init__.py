@@ -114,6 +114,9 @@ def load_library():
         "kz_decompress_device": (c.c_int64, [vp, u8p, c.c_int64, u8p, c.c_int64]),
         "kz_knz_assemble_device": (c.c_int64, [vp, c.c_uint64, c.c_uint32, c.c_int32, c.c_int64, c.c_int32, u8p, c.c_int64, i64p, c.c_int32, u8p, c.c_int64]),
         "kz_knz_index_device": (c.c_int32, [vp, u8p, c.c_int64, vp, vp, vp, vp, vp, i64p, i64p, c.c_int32]),
+        "kz_compress_many_bound": (c.c_int64, [i64p, c.c_int32, c.c_int32]),
+        "kz_compress_many_device": (c.c_int32, [vp, c.c_uint64, c.c_uint32, c.c_int32, u8p, i64p, i64p, c.c_int32, u8p, i64p, i64p, i64p]),
+        "kz_decompress_many_device": (c.c_int32, [vp, u8p, i64p, i64p, c.c_int32, u8p, i64p, i64p, i64p]),
         "kz_decompress_range": (c.c_int64, [vp, u8p, c.c_int64, c.c_int64, c.c_int64, u8p, c.c_int64]),
         "kz_decompress_range_device": (c.c_int64, [vp, u8p, c.c_int64, c.c_int64, c.c_int64, u8p, c.c_int64]),
         "kz_decode_indexed": (c.c_int32, [vp, u8p, c.c_int64, i64p, i64p, c.c_int32, u8p, c.c_int64, vp]),
@@ -146,6 +149,7 @@ ABI_SYMBOLS = ["kz_abi_version", "kz_ctx_create", "kz_ctx_destroy", "kz_last_err
                "kz_max_block_stream_bytes", "kz_submit_encode_blocks", "kz_submit_decode_blocks", "kz_wait", "kz_poll", "kz_compress", "kz_decompress", "kz_compress_bound", "kz_transform_type",
                "kz_knz_assemble", "kz_knz_index", "kz_knz_writer_open", "kz_knz_writer_add", "kz_knz_writer_close",
                "kz_compress_device", "kz_decompress_device", "kz_knz_assemble_device", "kz_knz_index_device",
+               "kz_compress_many_bound", "kz_compress_many_device", "kz_decompress_many_device",
                "kz_decompress_range", "kz_decompress_range_device", "kz_decode_indexed", "kz_decode_indexed_device",
                "kz_set_timing", "kz_get_stage_count", "kz_get_stage_ms", "kz_get_stage_alg_bytes", "kz_reset_timing",
                "kz_set_kernel_timing", "kz_get_kernel_count", "kz_get_kernel_name", "kz_get_kernel_ms", "kz_get_kernel_max_ms",
@@ -885,6 +889,105 @@ def decompress_tensor(ctx, knz, out=None):
     dst = _byte_view(out)
     size = decompress_device(ctx, src.data_ptr(), n, dst.data_ptr(), dst.numel())
     return dst[:size]
+
+
+# ---- many .knz streams on device memory (kz_compress_many_device / kz_decompress_many_device) ----
+def compress_many_bound(lengths, block_size):
+    """kz_compress_many_bound: the sum of compress_bound(n, block_size) over `lengths`."""
+    n = np.ascontiguousarray(lengths, dtype=np.int64)
+    return int(load_library().kz_compress_many_bound(n.ctypes.data if len(n) else None, len(n), int(block_size)))
+
+
+def _many_arrays(src_off, src_len, dst_off, dst_cap):
+    arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (src_off, src_len, dst_off, dst_cap)]
+    if len({len(a) for a in arrs}) != 1:
+        raise ValueError("src_off, src_len, dst_off and dst_cap must have one length")
+    return arrs
+
+
+def compress_many_device(ctx, transform, entropy, block_size, src, src_off, src_len, dst, dst_off, dst_cap, checksum=0, skip_blocks=False):
+    """kz_compress_many_device: stream s = the src_len[s] bytes at device address src + src_off[s], written into the slot at
+    dst + dst_off[s] (capacity dst_cap[s]) -> a list with each stream's size, or its negative code (as kz_compress_device returns it
+    for that buffer alone).  A fault of the call itself raises."""
+    tt = transform if isinstance(transform, int) else transform_type(transform)
+    et = entropy if isinstance(entropy, int) else ENTROPY_IDS[entropy.upper()]
+    so, sl, do, dc = _many_arrays(src_off, src_len, dst_off, dst_cap)
+    out = np.zeros(len(so), dtype=np.int64)
+    ctx.set_checksum(checksum)
+    ctx.set_skip_blocks(skip_blocks)
+    try:
+        rc = ctx.lib.kz_compress_many_device(ctx.h, tt, et, int(block_size), _ptr(src), so.ctypes.data, sl.ctypes.data, len(so),
+                                             _ptr(dst), do.ctypes.data, dc.ctypes.data, out.ctypes.data)
+    finally:
+        ctx.set_checksum(0)
+        ctx.set_skip_blocks(False)
+    ctx.check(rc)
+    return [int(v) for v in out]
+
+
+def decompress_many_device(ctx, src, src_off, src_len, dst, dst_off, dst_cap):
+    """kz_decompress_many_device: decode the src_len[s]-byte .knz stream at device address src + src_off[s] into the slot at
+    dst + dst_off[s] (capacity dst_cap[s]) -> a list with each stream's decoded size, or its negative code."""
+    so, sl, do, dc = _many_arrays(src_off, src_len, dst_off, dst_cap)
+    out = np.zeros(len(so), dtype=np.int64)
+    ctx.check(ctx.lib.kz_decompress_many_device(ctx.h, _ptr(src), so.ctypes.data, sl.ctypes.data, len(so),
+                                                _ptr(dst), do.ctypes.data, dc.ctypes.data, out.ctypes.data))
+    return [int(v) for v in out]
+
+
+def compress_tensors(ctx, tensors, transform="BWT+RANK+ZRLT", entropy="ANS0", block_size=4 << 20, checksum=0):
+    """compress_tensor for a list of contiguous device tensors in ONE call -> a list of torch.uint8 device tensors, one .knz stream
+    per input.  They are views of one buffer of compress_many_bound bytes, which stays allocated as long as a view lives.  The inputs
+    may lie in separate allocations.  A KanziError names the first tensor that failed."""
+    import torch
+    srcs = [_byte_view(t) for t in tensors]
+    if not srcs:
+        return []
+    dev = srcs[0].device
+    lens = [s.numel() for s in srcs]
+    caps = [compress_bound(n, block_size) for n in lens]
+    dst = torch.empty(compress_many_bound(lens, block_size), dtype=torch.uint8, device=dev)
+    dst_off = [0] * len(caps)
+    for i in range(1, len(caps)):
+        dst_off[i] = dst_off[i - 1] + caps[i - 1]
+    ptrs = [s.data_ptr() if n else dst.data_ptr() for s, n in zip(srcs, lens)]
+    base = min(ptrs)                                             # offsets are relative to the lowest address
+    torch.cuda.current_stream(dev).synchronize()                 # the call runs on the context's own stream
+    sizes = compress_many_device(ctx, transform, entropy, block_size, base, [p - base for p in ptrs], lens,
+                                 dst.data_ptr(), dst_off, caps, checksum=checksum)
+    for i, sz in enumerate(sizes):
+        if sz < 0:
+            raise KanziError(-sz, "compress_tensors: tensor %d" % i)
+    return [dst[o:o + sz] for o, sz in zip(dst_off, sizes)]
+
+
+def decompress_tensors(ctx, streams, sizes=None):
+    """Decode a list of .knz streams held in torch.uint8 device tensors in ONE call -> a list of torch.uint8 device tensors (views of
+    one buffer).  sizes[i]: the capacity for stream i; without `sizes` each result is sized as decompress_tensor sizes it, from the
+    stream's own block walk (blocks x blockSize) and not from the header's untrusted size field."""
+    import torch
+    srcs = [_byte_view(t) for t in streams]
+    if not srcs:
+        return []
+    dev = srcs[0].device
+    torch.cuda.current_stream(dev).synchronize()
+    if sizes is None:
+        sizes = []
+        for s in srcs:
+            idx = knz_index_device(ctx, s.data_ptr(), s.numel())
+            sizes.append(len(idx["blocks"]) * idx["blockSize"])
+    caps = [int(c) for c in sizes]
+    dst_off = [0] * len(caps)
+    for i in range(1, len(caps)):
+        dst_off[i] = dst_off[i - 1] + caps[i - 1]
+    dst = torch.empty(max(sum(caps), 1), dtype=torch.uint8, device=dev)
+    ptrs = [s.data_ptr() if s.numel() else dst.data_ptr() for s in srcs]
+    base = min(ptrs)
+    got = decompress_many_device(ctx, base, [p - base for p in ptrs], [s.numel() for s in srcs], dst.data_ptr(), dst_off, caps)
+    for i, sz in enumerate(got):
+        if sz < 0:
+            raise KanziError(-sz, "decompress_tensors: stream %d" % i)
+    return [dst[o:o + sz] for o, sz in zip(dst_off, got)]
 
 
 # ---- seekable streams: a block range (the reference's from / to), or blocks by an index ----

@@ -47,7 +47,8 @@
   X(KID_LZP_INV, "k_lzp_inv") X(KID_EXE_SETUP, "k_exe_setup") X(KID_EXE_MAP, "k_exe_map") X(KID_EXE_SCAN, "k_exe_scan") \
   X(KID_EXE_HIST, "k_exe_hist") X(KID_EXE_DECIDE, "k_exe_decide") X(KID_EXE_SIZE, "k_exe_size") X(KID_EXE_VERDICT, "k_exe_verdict") \
   X(KID_EXE_EMIT, "k_exe_emit") X(KID_KNZ_PACK, "k_knz_pack") X(KID_KNZ_WALK, "k_knz_walk") X(KID_KNZ_UNPACK, "k_knz_unpack") \
-  X(KID_KNZ_CHECK, "k_knz_check")
+  X(KID_KNZ_CHECK, "k_knz_check") X(KID_KNZ_GATHER, "k_knz_gather") X(KID_KNZ_PACK_MANY, "k_knz_pack_many") X(KID_KNZ_HEADS, "k_knz_heads") \
+  X(KID_KNZ_WALK_MANY, "k_knz_walk_many") X(KID_KNZ_UNPACK_MANY, "k_knz_unpack_many") X(KID_KNZ_SCATTER, "k_knz_scatter")
 #define KZ_KERNEL_ENUM(id, name) id,
 #define KZ_KERNEL_NAME(id, name) name,
 enum KzKernelId { KZ_KERNELS(KZ_KERNEL_ENUM) KID_COUNT };
@@ -316,6 +317,19 @@ int kz_knz_pack(kz_ctx*, const uint8_t* d_rows, const KnzBlk* d_blk, int nb, uin
 int kz_knz_walk(kz_ctx*, const uint8_t* d_src, int64_t n, int64_t startBit, int maxCount, int64_t* d_off, int64_t* d_bits, uint64_t* d_hdr, int64_t* d_res);
 int kz_knz_check(kz_ctx*, const uint8_t* d_src, int64_t n, int64_t hdrEnd, const int64_t* d_off, const int64_t* d_bits, int nb, uint64_t* d_hdr, int64_t* d_bad);
 int kz_knz_unpack(kz_ctx*, const uint8_t* d_src, int64_t n, const int64_t* d_off, const int64_t* d_bits, int nb, int64_t maxBytes, uint8_t* d_rows, int64_t stride);
+// many streams in one call (kz_compress_many_device / kz_decompress_many_device): every table entry carries its own bounds
+struct KnzCopy { int64_t src, dst, len; };    // gather / scatter: len bytes from byte offset src of the source base to byte offset dst of the destination base
+struct KnzSeg { int64_t dst, endBit, unit0; int32_t blk0, nblk, hdrBytes; uint8_t hdr[28]; };   // pack: a slot (byte offset in dst), its stream's last bit, its first
+                                              // 16-byte unit in the launch, its KnzBlk entries (pay relative to the slot) and its stream header
+struct KnzSrc { int64_t off, n, startBit, base; int32_t maxCount, cap; };   // walk: the stream src[off .. off + n), first prefix at startBit; entries go to
+                                              // base + i for i < cap
+struct KnzRow { int64_t seg, n, off, bits, row; };   // unpack: bits from bit off of the stream src[seg .. seg + n) to the row at byte offset `row`
+int kz_knz_gather(kz_ctx*, const uint8_t* d_src, const KnzCopy* d_t, int nr, int64_t maxLen, uint8_t* d_rows);
+int kz_knz_scatter(kz_ctx*, const uint8_t* d_rows, const KnzCopy* d_t, int nr, int64_t maxLen, uint8_t* d_dst);
+int kz_knz_pack_many(kz_ctx*, const uint8_t* d_rows, const KnzSeg* d_seg, int ns, const KnzBlk* d_blk, uint8_t* d_dst, int64_t units);
+int kz_knz_heads(kz_ctx*, const uint8_t* d_src, const KnzSrc* d_t, int ns, uint8_t* d_heads);
+int kz_knz_walk_many(kz_ctx*, const uint8_t* d_src, const KnzSrc* d_t, int ns, int64_t* d_off, int64_t* d_bits, uint64_t* d_hdr, int64_t* d_res);
+int kz_knz_unpack_many(kz_ctx*, const uint8_t* d_src, const KnzRow* d_t, int nr, int64_t maxBytes, uint8_t* d_rows);
 
 // timing helpers
 void kz_stage_begin(kz_ctx*, hipEvent_t* e0);

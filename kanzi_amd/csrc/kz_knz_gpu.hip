@@ -1,7 +1,8 @@
 // kz_knz_gpu.hip -- the .knz container on device memory: the bit-granular concatenation of block streams
 // (K/io/CompressedOutputStream.java:1024-1035) as a copy kernel, its inverse, and the serial walk of the block length
 // prefixes (K/io/CompressedInputStream.java:1127-1129), and the check of a caller's index entries that stands in for the walk in
-// the indexed reads.  The callers (kz_compress_device / kz_decompress_device / kz_decompress_range_device /
+// the indexed reads; behind them the same steps for many streams in one launch (a table entry per segment, slot or row, each with
+// its own bounds: kz_compress_many_device / kz_decompress_many_device).  The callers (kz_compress_device / kz_decompress_device / kz_decompress_range_device /
 // kz_decode_indexed_device / kz_knz_assemble_device / kz_knz_index_device, kz_stream.hip) do the bit-offset arithmetic, the stream
 // header and the block-header prechecks on the host; no payload byte leaves the device.
 #include "kz_device.h"
@@ -219,6 +220,207 @@ __global__ void __launch_bounds__(256) k_knz_unpack(const u8* __restrict__ src, 
   }
 }
 
+// ==== many streams in one call (kz_compress_many_device / kz_decompress_many_device) =========================================
+// The same four steps with a table entry per segment, slot or row that carries its own bounds: a launch serves every stream of a
+// group, and nothing is read outside a stream's own segment or written outside its own slot, wherever the other streams lie.
+
+// ---- ragged copy: gather (segments -> encoder rows) and scatter (decoded rows -> slots) -----------------------------------------
+// Entry r: t[r].len bytes from from[t[r].src ..] to to[t[r].dst ..], any alignment on both sides.  Output-centric like the pack: a
+// lane owns one 16-byte aligned unit of the destination range; a whole unit is one wide store of aligned 32-bit loads that stay
+// inside [src, src + len), the units at either end of the range (and those whose load window would leave the source) go bytewise.
+__device__ __forceinline__ void knz_ragged(const u8* __restrict__ from, const KnzCopy* __restrict__ t, int nr, u8* __restrict__ to) {
+  for (int r = blockIdx.y; r < nr; r += gridDim.y) {
+    const int64_t len = t[r].len;
+    if (len <= 0) continue;
+    const u8* s = from + t[r].src;
+    u8* d = to + t[r].dst;
+    const uintptr_t A0 = (uintptr_t)d & ~(uintptr_t)15;
+    const int64_t units = (int64_t)(((uintptr_t)(d + len) - A0 + 15) >> 4);
+    for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
+      const int64_t ub = (int64_t)(A0 - (uintptr_t)d) + (u << 4);                   // the unit's first byte as an index into the range (may be < 0)
+      const int64_t lo = ub < 0 ? 0 : ub, hi = ub + 16 > len ? len : ub + 16;
+      if (lo >= hi) continue;
+      if (hi - lo == 16) {
+        const u8* p = s + lo;
+        const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
+        if (al >= s && al + knz_window(p, 0) <= s + len) { *(uint4*)(d + lo) = knz_load128(p, 0); continue; }
+      }
+      for (int64_t b = lo; b < hi; b++) d[b] = s[b];
+    }
+  }
+}
+__global__ void __launch_bounds__(256) k_knz_gather(const u8* __restrict__ src, const KnzCopy* __restrict__ t, int nr, u8* __restrict__ rows) { knz_ragged(src, t, nr, rows); }
+__global__ void __launch_bounds__(256) k_knz_scatter(const u8* __restrict__ rows, const KnzCopy* __restrict__ t, int nr, u8* __restrict__ dst) { knz_ragged(rows, t, nr, dst); }
+
+// ---- pack: the blocks of many streams -> their slots -----------------------------------------------------------------------------
+// k_knz_pack's scheme over the slots of a group.  Stream s owns bytes [0, (endBit + 7) / 8) of its slot dst + seg[s].dst: the stream
+// header (seg[s].hdr, a whole number of bytes), the fields of blk[blk0 .. blk0 + nblk) (pay counted from the slot's first bit), zeros
+// up to endBit (the end marker) and to the end of the last byte.  The launch's units are the slots' 16-byte aligned units one slot
+// after the other (seg[s].unit0 = the first of slot s, growing with s, seg[0].unit0 = 0): a lane finds its slot by binary search.
+// Two slots may share an aligned unit of memory: each has a unit of its own for it and writes its own bytes only.  Every stream
+// starts on a byte, so no byte is read back.
+__global__ void __launch_bounds__(256) k_knz_pack_many(const u8* __restrict__ rows, const KnzSeg* __restrict__ seg, int ns, const KnzBlk* __restrict__ blkAll,
+                                                       u8* dst, int64_t units) {
+  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
+    int s = 0;
+    {
+      int a = 0, b = ns;                                                            // invariant: unit0 of slots < a is <= u
+      while (a < b) { const int m = (a + b) >> 1; if (seg[m].unit0 <= u) a = m + 1; else b = m; }
+      s = a > 0 ? a - 1 : 0;
+    }
+    u8* d = dst + seg[s].dst;
+    const int64_t lastByte = (seg[s].endBit + 7) >> 3;
+    const int hdrBytes = seg[s].hdrBytes;
+    const KnzBlk* blk = blkAll + seg[s].blk0;
+    const int nb = seg[s].nblk;
+    const uintptr_t A0 = (uintptr_t)d & ~(uintptr_t)15;
+    const int64_t ub = (int64_t)(A0 - (uintptr_t)d) + ((u - seg[s].unit0) << 4);     // the unit's first byte as an index into the slot (may be < 0)
+    const int64_t lo = ub < 0 ? 0 : ub, hi = ub + 16 > lastByte ? lastByte : ub + 16;
+    if (lo >= hi) continue;
+    const int64_t pos0 = lo << 3;
+    int j = 0;
+    {
+      int a = 0, b = nb;                                                            // invariant: prefix start of blocks < a is <= pos0
+      while (a < b) {
+        const int m = (a + b) >> 1;
+        const int64_t W = blk[m].bits;
+        if (blk[m].pay - 5 - knz_lw(W) <= pos0) a = m + 1; else b = m;
+      }
+      j = a > 0 ? a - 1 : 0;
+    }
+    if (j < nb && hi - lo == 16) {                                                  // the whole unit inside one payload: wide load, wide store
+      const int64_t pay = blk[j].pay, W = blk[j].bits;
+      if (pos0 >= pay && (hi << 3) <= pay + W) {
+        const int64_t k = pos0 - pay;
+        const u8* row = rows + blk[j].src;
+        const u8* p = row + (k >> 3);
+        const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
+        if (al >= row && al + knz_window(p, (int)(k & 7)) <= row + ((W + 7) >> 3)) {
+          *(uint4*)(d + lo) = knz_load128(p, (int)(k & 7));
+          continue;
+        }
+      }
+    }
+    for (int64_t b = lo; b < hi; b++) {
+      if (b < hdrBytes) { d[b] = seg[s].hdr[b]; continue; }
+      const int64_t bend = (b + 1) << 3;
+      int64_t pos = b << 3;
+      u32 acc = 0;
+      while (pos < bend) {
+        while (j < nb && pos >= blk[j].pay + blk[j].bits) j++;
+        if (j >= nb) break;                                                         // behind the last field: zeros
+        const int64_t pay = blk[j].pay, W = blk[j].bits;
+        const int room = (int)(bend - pos);
+        u32 v; int take;
+        if (pos < pay) {                                                            // length prefix: 5 + lw bits
+          const int lw = knz_lw(W), pw = 5 + lw;
+          const u64 field = ((u64)(lw - 3) << lw) | (u64)W;
+          const int k = (int)(pos - (pay - pw));
+          take = (int)(pay - pos) < room ? (int)(pay - pos) : room;
+          v = (u32)(field >> (pw - k - take)) & ((1u << take) - 1);
+        } else {
+          const int64_t k = pos - pay;
+          const int so = (int)(k & 7);
+          take = (W - k) < room ? (int)(W - k) : room;
+          const u8* sp = rows + blk[j].src + (k >> 3);
+          const u32 two = ((u32)sp[0] << 8) | (so + take > 8 ? (u32)sp[1] : 0u);
+          v = (two >> (16 - so - take)) & ((1u << take) - 1);
+        }
+        acc |= v << (room - take);
+        pos += take;
+      }
+      d[b] = (u8)acc;
+    }
+  }
+}
+
+// ---- heads: the first bytes of every stream, for the host's header parse -----------------------------------------------------------
+// heads[32 s + i] = byte i of stream s for i < min(26, n) (the longest stream header), zero behind that
+__global__ void __launch_bounds__(256) k_knz_heads(const u8* __restrict__ src, const KnzSrc* __restrict__ t, int ns, u8* __restrict__ heads) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)ns * 32) return;
+  const int s = (int)(i >> 5), k = (int)(i & 31);
+  heads[i] = (k < 26 && k < t[s].n) ? src[t[s].off + k] : (u8)0;
+}
+
+// ---- walk: one lane per stream -----------------------------------------------------------------------------------------------------
+// k_knz_walk's loop and stop reasons for stream s = src[t[s].off .. + t[s].n) from bit t[s].startBit, at most t[s].maxCount blocks;
+// res[3 s ..] = (blocks recorded whole, bit position, reason).  Entry i of the stream goes to index t[s].base + i of off / bits / hdr
+// when i < t[s].cap: the count pass runs with cap = 0 and writes res only, the fill pass with the counts' exclusive scan as base.
+// Bit offsets count from the stream's own first bit.
+__global__ void __launch_bounds__(64) k_knz_walk_many(const u8* __restrict__ src, const KnzSrc* __restrict__ t, int ns,
+                                                      int64_t* __restrict__ off, int64_t* __restrict__ bits, u64* __restrict__ hdr, int64_t* __restrict__ res) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= ns) return;
+  const u8* p = src + t[s].off;
+  const int64_t n = t[s].n, nbits = n << 3, base = t[s].base;
+  const int maxCount = t[s].maxCount, cap = t[s].cap;
+  int64_t pos = t[s].startBit;
+  int cnt = 0, why = KNZ_WALK_COUNT;
+  while (cnt < maxCount) {
+    if (pos + 5 > nbits) { why = KNZ_WALK_PREFIX; break; }
+    const u64 w = knz_peek64(p, n, pos);
+    const int lr = (int)(w >> 59) + 3;
+    if (pos + 5 + lr > nbits) { why = KNZ_WALK_PREFIX; break; }
+    const int64_t W = (int64_t)((w << 5) >> (64 - lr));
+    const int64_t pay = pos + 5 + lr;
+    if (W == 0) { why = KNZ_WALK_END; pos = pay; break; }
+    if (cnt < cap) { off[base + cnt] = pay; bits[base + cnt] = W; hdr[base + cnt] = knz_peek64(p, n, pay); }
+    pos = pay;
+    if (W > nbits - pay) { why = KNZ_WALK_PAYLOAD; break; }
+    pos = pay + W;
+    cnt++;
+  }
+  res[3 * s] = cnt; res[3 * s + 1] = pos; res[3 * s + 2] = why;
+}
+
+// ---- unpack: the blocks of many streams -> byte-aligned rows ---------------------------------------------------------------------
+// k_knz_unpack with the bounds of each row's own stream: row r (rows + t[r].row, 16-byte aligned) gets t[r].bits bits from bit
+// t[r].off of src[t[r].seg .. + t[r].n), and nothing outside that stream is read, not even bytes of a neighbour in the same buffer
+__global__ void __launch_bounds__(256) k_knz_unpack_many(const u8* __restrict__ srcAll, const KnzRow* __restrict__ t, int nr, u8* __restrict__ rows) {
+  for (int i = blockIdx.y; i < nr; i += gridDim.y) {
+    const u8* src = srcAll + t[i].seg;
+    const int64_t n = t[i].n, W = t[i].bits, o = t[i].off;
+    const int64_t units = (((W + 7) >> 3) + 15) >> 4;
+    u8* row = rows + t[i].row;
+    for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
+      const int64_t sb = o + (u << 7);
+      const int sh = (int)(sb & 7);
+      const u8* p = src + (sb >> 3);
+      const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
+      uint4 v;
+      if (al >= src && al + knz_window(p, sh) <= src + n) v = knz_load128(p, sh);
+      else {
+        u32 o4[4];
+        const int64_t by = sb >> 3;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          u32 x = 0;
+#pragma unroll
+          for (int k = 0; k < 4; k++) {
+            const int64_t c = by + q * 4 + k;
+            const u32 b0 = c < n ? src[c] : 0u, b1 = (sh && c + 1 < n) ? src[c + 1] : 0u;
+            x |= (((b0 << sh) | (b1 >> (8 - sh))) & 0xFFu) << (8 * k);
+          }
+          o4[q] = x;
+        }
+        v = make_uint4(o4[0], o4[1], o4[2], o4[3]);
+      }
+      const int64_t left = W - (u << 7);
+      if (left < 128) {
+        u32* c = (u32*)&v;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int64_t l = left - 32 * q;
+          const u32 keepBE = l >= 32 ? ~0u : (l <= 0 ? 0u : ~0u << (32 - (int)l));
+          c[q] &= __builtin_bswap32(keepBE);
+        }
+      }
+      *(uint4*)(row + (u << 4)) = v;
+    }
+  }
+}
+
 // ---- launchers -------------------------------------------------------------------------------------------------------------------
 int kz_knz_pack(kz_ctx* ctx, const uint8_t* d_rows, const KnzBlk* d_blk, int nb, uint8_t* d_dst, int64_t startBit, int64_t endBit) {
   if (endBit <= startBit) return 0;
@@ -244,6 +446,50 @@ int kz_knz_unpack(kz_ctx* ctx, const uint8_t* d_src, int64_t n, const int64_t* d
   const int64_t units = (maxBytes + 15) >> 4;
   const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((units + 255) / 256, 1 << 16));
   KZ_LAUNCH(ctx, KID_KNZ_UNPACK, k_knz_unpack, dim3(gx, std::min(nb, KZ_MAX_BATCH)), dim3(256), d_src, n, d_off, d_bits, nb, d_rows, stride);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+
+static inline dim3 knz_ragged_grid(int nr, int64_t maxLen) {
+  const int64_t units = ((maxLen + 15) >> 4) + 1;
+  return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((units + 255) / 256, 1 << 16)), (unsigned)std::min(nr, KZ_MAX_BATCH));
+}
+int kz_knz_gather(kz_ctx* ctx, const uint8_t* d_src, const KnzCopy* d_t, int nr, int64_t maxLen, uint8_t* d_rows) {
+  if (nr <= 0) return 0;
+  KZ_LAUNCH(ctx, KID_KNZ_GATHER, k_knz_gather, knz_ragged_grid(nr, maxLen), dim3(256), d_src, d_t, nr, d_rows);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_scatter(kz_ctx* ctx, const uint8_t* d_rows, const KnzCopy* d_t, int nr, int64_t maxLen, uint8_t* d_dst) {
+  if (nr <= 0) return 0;
+  KZ_LAUNCH(ctx, KID_KNZ_SCATTER, k_knz_scatter, knz_ragged_grid(nr, maxLen), dim3(256), d_rows, d_t, nr, d_dst);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_pack_many(kz_ctx* ctx, const uint8_t* d_rows, const KnzSeg* d_seg, int ns, const KnzBlk* d_blk, uint8_t* d_dst, int64_t units) {
+  if (ns <= 0 || units <= 0) return 0;
+  const int grid = (int)std::min<int64_t>((units + 255) / 256, 1 << 20);
+  KZ_LAUNCH(ctx, KID_KNZ_PACK_MANY, k_knz_pack_many, dim3(grid), dim3(256), d_rows, d_seg, ns, d_blk, d_dst, units);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_heads(kz_ctx* ctx, const uint8_t* d_src, const KnzSrc* d_t, int ns, uint8_t* d_heads) {
+  if (ns <= 0) return 0;
+  KZ_LAUNCH(ctx, KID_KNZ_HEADS, k_knz_heads, dim3((unsigned)(((int64_t)ns * 32 + 255) / 256)), dim3(256), d_src, d_t, ns, d_heads);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_walk_many(kz_ctx* ctx, const uint8_t* d_src, const KnzSrc* d_t, int ns, int64_t* d_off, int64_t* d_bits, uint64_t* d_hdr, int64_t* d_res) {
+  if (ns <= 0) return 0;
+  KZ_LAUNCH(ctx, KID_KNZ_WALK_MANY, k_knz_walk_many, dim3((ns + 63) / 64), dim3(64), d_src, d_t, ns, d_off, d_bits, (u64*)d_hdr, d_res);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_unpack_many(kz_ctx* ctx, const uint8_t* d_src, const KnzRow* d_t, int nr, int64_t maxBytes, uint8_t* d_rows) {
+  if (nr <= 0) return 0;
+  const int64_t units = (maxBytes + 15) >> 4;
+  const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((units + 255) / 256, 1 << 16));
+  KZ_LAUNCH(ctx, KID_KNZ_UNPACK_MANY, k_knz_unpack_many, dim3(gx, std::min(nr, KZ_MAX_BATCH)), dim3(256), d_src, d_t, nr, d_rows);
   KZ_HIP(hipGetLastError());
   return 0;
 }

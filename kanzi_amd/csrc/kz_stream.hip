@@ -939,6 +939,379 @@ extern "C" int64_t kz_decompress_range_device(kz_ctx* ctx, const uint8_t* d_src,
 
 
 // =================================================================================================
+// many .knz streams on device memory: kz_compress_device / kz_decompress_device for N (segment, slot) pairs in one call.  Whole
+// streams are collected into groups of at most one chunk's blocks; the blocks of a group go through ONE batched encode (one decode
+// per distinct header), and the container kernels (kz_knz_gpu.hip: gather, pack, heads, walk, unpack, scatter) take a table with an
+// entry per segment, slot or row, so launches and host waits per group do not grow with the streams in it.  A stream with more
+// blocks than a group takes goes through the single-stream call, which is the definition of every result here.
+namespace {
+// `need` bytes of pinned table and of its HBM mirror (the single-stream calls use the same two buffers: nothing is kept in them
+// across one of those calls)
+int knz_many_tables(kz_ctx* ctx, size_t need) {
+  int rc = stage_reserve(ctx, ctx->knzPin, need + 64, true);
+  if (!rc) rc = stage_reserve(ctx, ctx->knzAux, need + 64, false);
+  return rc;
+}
+int knz_many_args(const void* ctx, const void* d_src, const int64_t* srcOff, const int64_t* srcLen, int32_t nStreams,
+                  const void* d_dst, const int64_t* dstOff, const int64_t* dstCap, const int64_t* dstLen) {
+  if (!ctx || nStreams < 0) return -KZ_ERR_INVALID_PARAM;
+  if (nStreams == 0) return 0;
+  if (!d_src || !srcOff || !srcLen || !d_dst || !dstOff || !dstCap || !dstLen) return -KZ_ERR_INVALID_PARAM;
+  for (int s = 0; s < nStreams; s++) if (srcOff[s] < 0 || srcLen[s] < 0 || dstOff[s] < 0 || dstCap[s] < 0) return -KZ_ERR_INVALID_PARAM;
+  return 0;
+}
+inline int64_t knz_units16(const uint8_t* p, int64_t len) {        // 16-byte aligned units of memory that [p, p + len) touches
+  const uintptr_t a = (uintptr_t)p;
+  return (int64_t)((((a + (uintptr_t)len + 15) & ~(uintptr_t)15) - (a & ~(uintptr_t)15)) >> 4);
+}
+
+// streams [s0, s1) of a kz_compress_many_device call: together at most one chunk's blocks
+int compress_group(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int32_t blockSize, const uint8_t* d_src, const int64_t* srcOff,
+                   const int64_t* srcLen, int s0, int s1, uint8_t* d_dst, const int64_t* dstOff, const int64_t* dstCap, int64_t* dstLen) {
+  const int ns = s1 - s0;
+  int64_t nbTot = 0;
+  for (int s = s0; s < s1; s++) nbTot += (srcLen[s] + blockSize - 1) / blockSize;
+  const int NBk = (int)nbTot;
+  const int64_t oS = kz_max_block_stream_bytes(blockSize);
+  const size_t gatherBytes = kz_align((size_t)NBk * sizeof(KnzCopy) + 64, 64), segBytes = (size_t)ns * sizeof(KnzSeg);
+  {
+    int rc = stage_reserve(ctx, ctx->devIn[0], (size_t)std::max(NBk, 1) * (size_t)blockSize, false);
+    if (!rc) rc = stage_reserve(ctx, ctx->devOut[0], (size_t)std::max(NBk, 1) * (size_t)oS, false);
+    if (!rc) rc = knz_many_tables(ctx, gatherBytes + segBytes + (size_t)NBk * sizeof(KnzBlk));
+    if (rc) return rc;
+  }
+  uint8_t* rowsIn = ctx->devIn[0].p;
+  uint8_t* rows = ctx->devOut[0].p;
+  std::vector<int32_t> lens(NBk);
+  std::vector<kz_block_result> res(NBk);
+  int erc = 0;
+  if (NBk) {
+    // ---- gather: every block into a row of its own, blockSize apart (the encoder may read a device row up to the call's longest
+    //      block, and behind a stream's last block lies memory that is not that stream's) ----
+    KnzCopy* g = (KnzCopy*)ctx->knzPin.p;
+    int r = 0;
+    for (int s = s0; s < s1; s++)
+      for (int64_t o = 0; o < srcLen[s]; o += blockSize, r++) {
+        lens[r] = (int32_t)std::min<int64_t>(blockSize, srcLen[s] - o);
+        g[r] = KnzCopy{srcOff[s] + o, (int64_t)r * blockSize, lens[r]};
+      }
+    KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, g, (size_t)NBk * sizeof(KnzCopy), hipMemcpyHostToDevice, ctx->stream));
+    { const int rc = kz_knz_gather(ctx, d_src, (const KnzCopy*)ctx->knzAux.p, NBk, blockSize, rowsIn); if (rc) return rc; }
+    // the encoder takes device input to be complete when it is called: chains led by TEXT / UTF copy rows back on another stream
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+    BlockSizeScope scope(ctx, blockSize);
+    erc = kz_encode_blocks_pre(ctx, transformType, entropyType, blockSize, rowsIn, blockSize, lens.data(), NBk, rows, oS, res.data(), KZ_MEM_DEVICE, nullptr);
+    if (erc == -KZ_ERR_DEVICE) return erc;
+  }
+  // ---- per stream what kz_compress_device does per stream: header, bit offsets over results[], the fit in the slot ----
+  KnzSeg* seg = (KnzSeg*)(ctx->knzPin.p + gatherBytes);
+  KnzBlk* blk = (KnzBlk*)(ctx->knzPin.p + gatherBytes + segBytes);
+  int m = 0, nseg = 0, r0 = 0;
+  int64_t units = 0;
+  for (int s = s0; s < s1; s++) {
+    const int nb = (int)((srcLen[s] + blockSize - 1) / blockSize);
+    const int first = r0;
+    r0 += nb;
+    int64_t code = nb ? erc : 0;                                  // (an empty stream asks nothing of the encoder)
+    for (int i = 0; i < nb && !code; i++) code = res[first + i].status;
+    if (code) { dstLen[s] = code; continue; }
+    KnzSeg S;
+    memset(&S, 0, sizeof(S));
+    uint8_t hdr[32] = {0};
+    HostBits hb{hdr, 32, 0, false};
+    write_stream_header(hb, transformType, entropyType, blockSize, srcLen[s], ctx->checksum);
+    int64_t p = (int64_t)hb.pos;
+    const int m0 = m;
+    for (int i = 0; i < nb; i++) {
+      const int64_t W = res[first + i].bits;
+      if (W <= 0) continue;
+      const int lw = ((uint64_t)W < 8) ? 3 : ilog2((uint32_t)((uint64_t)W >> 3)) + 4;          // write_block
+      p += 5 + lw;
+      blk[m++] = KnzBlk{p, W, (int64_t)(first + i) * oS};
+      p += W;
+    }
+    const int64_t end = p + 8;                                    // end marker (:491-492)
+    if (((end + 7) >> 3) > dstCap[s]) {
+      m = m0;
+      snprintf(ctx->err, sizeof(ctx->err), "kz_compress_many_device: destination %d too small", s);
+      dstLen[s] = -KZ_ERR_WRITE_FILE;
+      continue;
+    }
+    S.dst = dstOff[s]; S.endBit = end; S.unit0 = units; S.blk0 = m0; S.nblk = m - m0; S.hdrBytes = (int32_t)(hb.pos >> 3);
+    memcpy(S.hdr, hdr, 28);
+    seg[nseg++] = S;
+    units += knz_units16(d_dst + dstOff[s], (end + 7) >> 3);
+    dstLen[s] = (end + 7) >> 3;
+  }
+  if (nseg) {
+    uint8_t* a = ctx->knzAux.p + gatherBytes;
+    KZ_HIP(hipMemcpyAsync(a, seg, segBytes + (size_t)m * sizeof(KnzBlk), hipMemcpyHostToDevice, ctx->stream));
+    const int rc = kz_knz_pack_many(ctx, rows, (const KnzSeg*)a, nseg, (const KnzBlk*)(a + segBytes), d_dst, units);
+    if (rc) return rc;
+  }
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  return 0;
+}
+}  // namespace
+
+extern "C" int64_t kz_compress_many_bound(const int64_t* srcLen, int32_t nStreams, int32_t blockSize) {
+  if (nStreams < 0 || (nStreams > 0 && !srcLen)) return -KZ_ERR_INVALID_PARAM;
+  int64_t total = 0;
+  for (int s = 0; s < nStreams; s++) {
+    const int64_t b = kz_compress_bound(srcLen[s], blockSize);
+    if (b < 0) return b;
+    total += b;
+  }
+  return total;
+}
+
+extern "C" int32_t kz_compress_many_device(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int32_t blockSize,
+                                           const uint8_t* d_src, const int64_t* srcOff, const int64_t* srcLen, int32_t nStreams,
+                                           uint8_t* d_dst, const int64_t* dstOff, const int64_t* dstCap, int64_t* dstLen) {
+  { const int rc = knz_many_args(ctx, d_src, srcOff, srcLen, nStreams, d_dst, dstOff, dstCap, dstLen); if (rc || nStreams == 0) return rc; }
+  if (blockSize < 1024 || blockSize > (1 << 30) || (blockSize & 15)) return -KZ_ERR_BLOCK_SIZE;   // kz_compress_device's check
+  KZ_HIP(hipSetDevice(ctx->device));
+  const int64_t G = knz_chunk_blocks(ctx, blockSize);
+  auto blocksOf = [&](int s) { return (srcLen[s] + blockSize - 1) / blockSize; };
+  for (int s0 = 0; s0 < nStreams;) {
+    if (blocksOf(s0) > G) {                                       // larger than a group: the single-stream call, on its own
+      dstLen[s0] = kz_compress_device(ctx, transformType, entropyType, blockSize, d_src + srcOff[s0], srcLen[s0], d_dst + dstOff[s0], dstCap[s0]);
+      if (dstLen[s0] == -KZ_ERR_DEVICE) return -KZ_ERR_DEVICE;
+      s0++;
+      continue;
+    }
+    int s1 = s0;
+    int64_t tot = 0;                                              // (an empty stream counts as one block: a group's tables stay bounded)
+    while (s1 < nStreams && blocksOf(s1) <= G && (s1 == s0 || tot + std::max<int64_t>(blocksOf(s1), 1) <= G)) { tot += std::max<int64_t>(blocksOf(s1), 1); s1++; }
+    const int rc = compress_group(ctx, transformType, entropyType, blockSize, d_src, srcOff, srcLen, s0, s1, d_dst, dstOff, dstCap, dstLen);
+    if (rc) return rc;
+    s0 = s1;
+  }
+  return 0;
+}
+
+namespace {
+struct KnzManyStream {                                             // a stream of a kz_decompress_many_device call after the header parse
+  KnzHeader h; int code; int64_t startBit; int nbFunctions; int CH; int64_t iS;
+  int cnt, why;                                                    // the count pass
+};
+// the streams ids[0 .. ng) of a kz_decompress_many_device call: their walk stops inside a single-stream chunk, and together they
+// hold at most a group's blocks (have[k] entries each, the one of a payload that does not fit included)
+int decompress_group(kz_ctx* ctx, const std::vector<KnzManyStream>& st, const int* ids, const int* have, int ng, const uint8_t* d_src, const int64_t* srcOff,
+                     const int64_t* srcLen, uint8_t* d_dst, const int64_t* dstOff, const int64_t* dstCap, int64_t* dstLen) {
+  int64_t E = 0;
+  for (int k = 0; k < ng; k++) E += have[k];
+  // ---- fill pass: the entries of all streams in one table, at the exclusive scan of the counts ----
+  const size_t tBytes = kz_align((size_t)ng * sizeof(KnzSrc), 64), outBytes = (size_t)ng * 24 + (size_t)E * 24;
+  { const int rc = knz_many_tables(ctx, tBytes + outBytes); if (rc) return rc; }
+  {
+    KnzSrc* t = (KnzSrc*)ctx->knzPin.p;
+    int64_t base = 0;
+    for (int k = 0; k < ng; k++) {
+      const int s = ids[k];
+      t[k] = KnzSrc{srcOff[s], srcLen[s], st[s].startBit, base, st[s].CH + 1, have[k]};
+      base += have[k];
+    }
+  }
+  int64_t* d_res = (int64_t*)(ctx->knzAux.p + tBytes);
+  int64_t* d_off = d_res + 3 * (int64_t)ng;
+  const int64_t* res = (const int64_t*)(ctx->knzPin.p + tBytes);
+  const int64_t* off = res + 3 * (int64_t)ng;
+  const int64_t* bits = off + E;
+  const uint64_t* hdr = (const uint64_t*)(bits + E);
+  KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, ctx->knzPin.p, (size_t)ng * sizeof(KnzSrc), hipMemcpyHostToDevice, ctx->stream));
+  { const int rc = kz_knz_walk_many(ctx, d_src, (const KnzSrc*)ctx->knzAux.p, ng, d_off, d_off + E, (uint64_t*)(d_off + 2 * E), d_res); if (rc) return rc; }
+  KZ_HIP(hipMemcpyAsync(ctx->knzPin.p + tBytes, ctx->knzAux.p + tBytes, outBytes, hipMemcpyDeviceToHost, ctx->stream));
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  // ---- per stream kz_decompress_device's checks on its one chunk, in its order; a fault is held back behind the blocks in front ----
+  struct Part { int s, first, cnt, pending, cls; int64_t base; };
+  struct Cls { uint64_t tt; int et, bs, chk; int64_t iS; int rows; int64_t inBase, outBase; int first; };
+  std::vector<Part> parts(ng);
+  std::vector<Cls> cls;
+  int64_t base = 0;
+  for (int k = 0; k < ng; k++) {
+    const int s = ids[k];
+    const KnzManyStream& S = st[s];
+    const int64_t got = res[3 * k], why = res[3 * k + 2];
+    if (got < 0 || got > S.CH + 1) { snprintf(ctx->err, sizeof(ctx->err), "knz walk: bad count"); return -KZ_ERR_DEVICE; }
+    const int hv = (int)std::min<int64_t>(got + (why == KNZ_WALK_PAYLOAD ? 1 : 0), have[k]);
+    const uint64_t nbits = (uint64_t)srcLen[s] * 8;
+    int cnt = 0, pending = 0;
+    for (; cnt < hv; cnt++) {
+      pending = knz_precheck_entry(hdr[base + cnt], (uint64_t)bits[base + cnt], (uint64_t)off[base + cnt], nbits, S.nbFunctions, S.h.blockSize, S.h.chkKind, S.iS);
+      if (pending) break;
+    }
+    if (!pending && why != KNZ_WALK_END) pending = -KZ_ERR_READ_FILE;     // a prefix that does not fit
+    if (cnt > 0) {                                                // blocks that start past the end of the destination cannot be stored
+      const int64_t fit = dstCap[s] <= 0 ? 0 : (dstCap[s] + S.h.blockSize - 1) / S.h.blockSize;
+      if (fit < cnt) { cnt = (int)fit; pending = -KZ_ERR_WRITE_FILE; }
+    }
+    int c = 0;
+    for (; c < (int)cls.size(); c++) if (cls[c].tt == S.h.transformType && cls[c].et == S.h.entropyType && cls[c].bs == S.h.blockSize && cls[c].chk == S.h.chkKind) break;
+    if (c == (int)cls.size()) cls.push_back(Cls{S.h.transformType, S.h.entropyType, S.h.blockSize, S.h.chkKind, S.iS, 0, 0, 0, 0});
+    parts[k] = Part{s, cls[c].rows, cnt, pending, c, base};
+    cls[c].rows += cnt;
+    base += have[k];
+  }
+  int64_t inBytes = 0, outBytes2 = 0;
+  int R = 0;
+  for (Cls& c : cls) { c.inBase = inBytes; c.outBase = outBytes2; c.first = R; inBytes += (int64_t)c.rows * c.iS; outBytes2 += (int64_t)c.rows * c.bs; R += c.rows; }
+  std::vector<int64_t> W((size_t)std::max(R, 1));
+  std::vector<kz_block_result> bres((size_t)std::max(R, 1));
+  // the walk's tables are read for the last time while the unpack table is built: it goes behind them
+  const size_t rowBytes = kz_align((size_t)R * sizeof(KnzRow), 64), copyBytes = (size_t)R * sizeof(KnzCopy);
+  std::vector<KnzRow> rowT((size_t)R);
+  int64_t maxBytes = 0;
+  for (int k = 0; k < ng; k++) {
+    const Part& P = parts[k];
+    const Cls& c = cls[P.cls];
+    for (int i = 0; i < P.cnt; i++) {
+      const int r = c.first + P.first + i;
+      W[r] = bits[P.base + i];
+      maxBytes = std::max<int64_t>(maxBytes, (W[r] + 7) >> 3);
+      rowT[r] = KnzRow{srcOff[P.s], srcLen[P.s], off[P.base + i], W[r], c.inBase + (int64_t)(P.first + i) * c.iS};
+    }
+  }
+  if (R) {
+    int rc = stage_reserve(ctx, ctx->devIn[0], (size_t)inBytes + 64, false);
+    if (!rc) rc = stage_reserve(ctx, ctx->devOut[0], (size_t)outBytes2 + 64, false);
+    if (!rc) rc = knz_many_tables(ctx, rowBytes + copyBytes);     // (may move the tables: everything needed from them is in W / rowT / parts)
+    if (rc) return rc;
+    memcpy(ctx->knzPin.p, rowT.data(), (size_t)R * sizeof(KnzRow));
+    KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, ctx->knzPin.p, (size_t)R * sizeof(KnzRow), hipMemcpyHostToDevice, ctx->stream));
+    rc = kz_knz_unpack_many(ctx, d_src, (const KnzRow*)ctx->knzAux.p, R, maxBytes, ctx->devIn[0].p);
+    if (rc) return rc;
+  }
+  // ---- one decode per distinct header, into staging rows ----
+  std::vector<int> crc(cls.size(), 0);
+  {
+    const int savedChk = ctx->checksum;
+    struct Restore { kz_ctx* c; int v; ~Restore() { c->checksum = v; } } restore_{ctx, savedChk};
+    for (size_t c = 0; c < cls.size(); c++) {
+      const Cls& C = cls[c];
+      if (!C.rows) continue;
+      ctx->checksum = C.chk;
+      crc[c] = kz_decode_blocks(ctx, C.tt, (uint32_t)C.et, C.bs, ctx->devIn[0].p + C.inBase, C.iS, W.data() + C.first, C.rows,
+                                ctx->devOut[0].p + C.outBase, C.bs, bres.data() + C.first, KZ_MEM_DEVICE);
+      if (crc[c] == -KZ_ERR_DEVICE) return crc[c];
+    }
+  }
+  // ---- scatter: each stream's blocks into its slot back to back, cut where kz_decompress_device cuts it ----
+  KnzCopy* ct = R ? (KnzCopy*)(ctx->knzPin.p + rowBytes) : nullptr;
+  int nc = 0;
+  int64_t maxLen = 0;
+  for (int k = 0; k < ng; k++) {
+    const Part& P = parts[k];
+    const Cls& C = cls[P.cls];
+    if (P.cnt > 0 && crc[P.cls]) { dstLen[P.s] = crc[P.cls]; continue; }
+    int64_t produced = 0;
+    int code = 0;
+    for (int i = 0; i < P.cnt; i++) {
+      const kz_block_result& b = bres[C.first + P.first + i];
+      if (b.status) { code = b.status; break; }
+      if (b.length > C.bs) { code = -KZ_ERR_PROCESS_BLOCK; break; }
+      if (produced + b.length > dstCap[P.s]) { code = -KZ_ERR_WRITE_FILE; break; }
+      if (b.length > 0) {
+        ct[nc++] = KnzCopy{C.outBase + (int64_t)(P.first + i) * C.bs, dstOff[P.s] + produced, b.length};
+        maxLen = std::max<int64_t>(maxLen, b.length);
+      }
+      produced += b.length;
+    }
+    dstLen[P.s] = code ? code : (P.pending ? P.pending : produced);
+  }
+  if (nc) {
+    KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + rowBytes, ct, (size_t)nc * sizeof(KnzCopy), hipMemcpyHostToDevice, ctx->stream));
+    const int rc = kz_knz_scatter(ctx, ctx->devOut[0].p, (const KnzCopy*)(ctx->knzAux.p + rowBytes), nc, maxLen, d_dst);
+    if (rc) return rc;
+  }
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  return 0;
+}
+}  // namespace
+
+extern "C" int32_t kz_decompress_many_device(kz_ctx* ctx, const uint8_t* d_src, const int64_t* srcOff, const int64_t* srcLen, int32_t nStreams,
+                                             uint8_t* d_dst, const int64_t* dstOff, const int64_t* dstCap, int64_t* dstLen) {
+  { const int rc = knz_many_args(ctx, d_src, srcOff, srcLen, nStreams, d_dst, dstOff, dstCap, dstLen); if (rc || nStreams == 0) return rc; }
+  KZ_HIP(hipSetDevice(ctx->device));
+  const int ns = nStreams;
+  std::vector<KnzManyStream> st((size_t)ns);
+  // ---- the first bytes of every stream in one table, one copy; the headers are parsed here with kz_decompress_device's codes ----
+  const size_t tBytes = kz_align((size_t)ns * sizeof(KnzSrc), 64), headBytes = (size_t)ns * 32, resBytes = (size_t)ns * 24;
+  { const int rc = knz_many_tables(ctx, tBytes + std::max(headBytes, resBytes)); if (rc) return rc; }
+  KnzSrc* t = (KnzSrc*)ctx->knzPin.p;
+  const KnzSrc* d_t = (const KnzSrc*)ctx->knzAux.p;
+  for (int s = 0; s < ns; s++) t[s] = KnzSrc{srcOff[s], srcLen[s], 0, 0, 0, 0};
+  KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, t, (size_t)ns * sizeof(KnzSrc), hipMemcpyHostToDevice, ctx->stream));
+  { const int rc = kz_knz_heads(ctx, d_src, d_t, ns, ctx->knzAux.p + tBytes); if (rc) return rc; }
+  KZ_HIP(hipMemcpyAsync(ctx->knzPin.p + tBytes, ctx->knzAux.p + tBytes, headBytes, hipMemcpyDeviceToHost, ctx->stream));
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  bool firstFault = true;
+  for (int s = 0; s < ns; s++) {
+    KnzManyStream& S = st[s];
+    memset(&S, 0, sizeof(S));
+    const int64_t n = srcLen[s], hn = std::min<int64_t>(n, 26);
+    HostBitsIn bs{ctx->knzPin.p + tBytes + (size_t)s * 32, (uint64_t)hn * 8, 0, false};
+    S.code = read_stream_header(bs, S.h, firstFault ? ctx->err : nullptr, sizeof(ctx->err));   // (the text of the first failing stream stays)
+    if (S.code) { firstFault = false; t[s].maxCount = 0; continue; }
+    const int blockSize = S.h.blockSize;
+    for (int i = 0; i < 8; i++) if (((S.h.transformType >> (42 - 6 * i)) & 0x3F) != 0) S.nbFunctions++;
+    if (S.nbFunctions == 0) S.nbFunctions = 1;
+    int64_t NB = batch_blocks(blockSize);                         // decompress_device's batch and chunk
+    if (S.h.szMask && S.h.inputSize > 0) NB = std::min<int64_t>(NB, (S.h.inputSize + blockSize - 1) / blockSize);
+    else NB = std::min<int64_t>(NB, n / 8 + 1);
+    S.CH = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->sw.streamChunk > 0 ? ctx->sw.streamChunk : NB, std::min<int64_t>(NB, KZ_MAX_BATCH)));
+    S.iS = (int64_t)kz_align((size_t)blockSize + (size_t)(blockSize >> 3) + 1024 + 64, 256);
+    S.startBit = (int64_t)bs.pos;
+    t[s].startBit = S.startBit; t[s].maxCount = S.CH + 1;
+  }
+  // ---- count pass: one lane per stream walks one block further than a single-stream chunk goes.  A walk that stops by itself
+  //      (end marker or fault) is what kz_decompress_device sees in its one chunk with blocks: such a stream can join a group ----
+  KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, t, (size_t)ns * sizeof(KnzSrc), hipMemcpyHostToDevice, ctx->stream));
+  { const int rc = kz_knz_walk_many(ctx, d_src, d_t, ns, nullptr, nullptr, nullptr, (int64_t*)(ctx->knzAux.p + tBytes)); if (rc) return rc; }
+  KZ_HIP(hipMemcpyAsync(ctx->knzPin.p + tBytes, ctx->knzAux.p + tBytes, resBytes, hipMemcpyDeviceToHost, ctx->stream));
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  {
+    const int64_t* res = (const int64_t*)(ctx->knzPin.p + tBytes);
+    for (int s = 0; s < ns; s++) {
+      if (st[s].code) continue;
+      if (res[3 * s] < 0 || res[3 * s] > st[s].CH + 1) { snprintf(ctx->err, sizeof(ctx->err), "knz walk: bad count"); return -KZ_ERR_DEVICE; }
+      st[s].cnt = (int)res[3 * s]; st[s].why = (int)res[3 * s + 2];
+    }
+  }
+  // ---- groups of whole streams: at most a chunk's blocks (decompress_device's batch: 2048 blocks, 8 GiB) ----
+  const int64_t capBlocks = ctx->sw.streamChunk > 0 ? ctx->sw.streamChunk : 2048, capBytes = 8LL << 30;
+  std::vector<int> ids, have;
+  int64_t gBlocks = 0, gBytes = 0;
+  auto flush = [&]() -> int {
+    if (ids.empty()) return 0;
+    const int rc = decompress_group(ctx, st, ids.data(), have.data(), (int)ids.size(), d_src, srcOff, srcLen, d_dst, dstOff, dstCap, dstLen);
+    ids.clear(); have.clear(); gBlocks = 0; gBytes = 0;
+    return rc;
+  };
+  for (int s = 0; s < ns; s++) {
+    const KnzManyStream& S = st[s];
+    if (S.code) { dstLen[s] = S.code; continue; }
+    if (S.why == KNZ_WALK_COUNT) {                                // more blocks than a group takes: the single-stream call, on its own
+      dstLen[s] = decompress_device(ctx, d_src + srcOff[s], srcLen[s], 0, -1, d_dst + dstOff[s], dstCap[s]);
+      if (dstLen[s] == -KZ_ERR_DEVICE) return -KZ_ERR_DEVICE;
+      continue;
+    }
+    const int hv = S.cnt + (S.why == KNZ_WALK_PAYLOAD ? 1 : 0);
+    const int64_t blocks = std::max(hv, 1), bytes = blocks * S.h.blockSize;
+    if (!ids.empty() && (gBlocks + blocks > capBlocks || gBytes + bytes > capBytes)) { const int rc = flush(); if (rc) return rc; }
+    ids.push_back(s); have.push_back(hv);
+    gBlocks += blocks; gBytes += bytes;
+  }
+  return flush();
+}
+
+
+// =================================================================================================
 // indexed reads: blocks of a stream by their (bit offset, bit length) pairs, as kz_knz_index / kz_knz_index_device return them, in
 // any order.  No walk: every pair is checked against the stream on its own (k_knz_check on the device, knz_check_entry here), which
 // makes the call memory safe for any index and brings the block-header bytes for the prechecks; it does not prove that a pair lies
