@@ -3,7 +3,7 @@
 // prefixes (K/io/CompressedInputStream.java:1127-1129), and the check of a caller's index entries that stands in for the walk in
 // the indexed reads; behind them the same steps for many streams in one launch (a table entry per segment, slot or row, each with
 // its own bounds: kz_compress_many_device / kz_decompress_many_device).  The callers (kz_compress_device / kz_decompress_device / kz_decompress_range_device /
-// kz_decode_indexed_device / kz_knz_assemble_device / kz_knz_index_device, kz_stream.hip) do the bit-offset arithmetic, the stream
+// kz_decode_indexed_device / kz_knz_assemble_device / kz_knz_index_device, kz_stream_device.hip) do the bit-offset arithmetic, the stream
 // header and the block-header prechecks on the host; no payload byte leaves the device.
 #include "kz_device.h"
 #include "kz_internal.h"
@@ -29,7 +29,61 @@ __device__ __forceinline__ uint4 knz_load128(const u8* p, int sh) {
   for (int i = 0; i < 4; i++) o[i] = s ? ((w[i] << s) | (w[i + 1] >> (32 - s))) : w[i];
   return make_uint4(__builtin_bswap32(o[0]), __builtin_bswap32(o[1]), __builtin_bswap32(o[2]), __builtin_bswap32(o[3]));
 }
-__device__ __forceinline__ int knz_lw(int64_t W) { return W < 8 ? 3 : kz_ilog2((u32)(W >> 3)) + 4; }   // write_block, kz_stream.hip
+__device__ __forceinline__ int knz_lw(int64_t W) { return W < 8 ? 3 : kz_ilog2((u32)(W >> 3)) + 4; }   // the device form of knz_prefix_width (kz_knz_host.h)
+
+// ---- the pack's steps, shared by k_knz_pack and k_knz_pack_many ----
+// the last block whose prefix starts at or before pos0 (prefix starts grow with i)
+__device__ __forceinline__ int knz_find_field(const KnzBlk* __restrict__ blk, int nb, int64_t pos0) {
+  int a = 0, b = nb;                                                                // invariant: prefix start of blocks < a is <= pos0
+  while (a < b) {
+    const int m = (a + b) >> 1;
+    const int64_t W = blk[m].bits;
+    if (blk[m].pay - 5 - knz_lw(W) <= pos0) a = m + 1; else b = m;
+  }
+  return a > 0 ? a - 1 : 0;
+}
+// the 16 bytes [pos0, hiBit) of the destination when they lie inside the payload of block j alone: wide load, wide store at `out`.
+// From the row only aligned words inside the bytes of its W bits are read; false, nothing stored, when the unit is not of that kind.
+__device__ __forceinline__ bool knz_wide_unit(const u8* __restrict__ rows, const KnzBlk* __restrict__ blk, int nb, int j, int64_t pos0, int64_t hiBit, u8* out) {
+  if (j >= nb) return false;
+  const int64_t pay = blk[j].pay, W = blk[j].bits;
+  if (pos0 < pay || hiBit > pay + W) return false;
+  const int64_t k = pos0 - pay;
+  const u8* row = rows + blk[j].src;
+  const u8* p = row + (k >> 3);
+  const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
+  if (al < row || al + knz_window(p, (int)(k & 7)) > row + ((W + 7) >> 3)) return false;
+  *(uint4*)out = knz_load128(p, (int)(k & 7));
+  return true;
+}
+// the byte that ends at bit bend, composed from bit pos on (acc: the bits in front of pos, already in place) out of whatever fields
+// it holds; j moves to the last field looked at.  From a row only the bytes of its W bits are read.
+__device__ __forceinline__ u8 knz_compose_byte(const u8* __restrict__ rows, const KnzBlk* __restrict__ blk, int nb, int& j, int64_t pos, int64_t bend, u32 acc) {
+  while (pos < bend) {
+    while (j < nb && pos >= blk[j].pay + blk[j].bits) j++;
+    if (j >= nb) break;                                                             // behind the last field: zeros
+    const int64_t pay = blk[j].pay, W = blk[j].bits;
+    const int room = (int)(bend - pos);
+    u32 v; int take;
+    if (pos < pay) {                                                                // length prefix: 5 + lw bits
+      const int lw = knz_lw(W), pw = 5 + lw;
+      const u64 field = ((u64)(lw - 3) << lw) | (u64)W;
+      const int k = (int)(pos - (pay - pw));
+      take = (int)(pay - pos) < room ? (int)(pay - pos) : room;
+      v = (u32)(field >> (pw - k - take)) & ((1u << take) - 1);
+    } else {
+      const int64_t k = pos - pay;
+      const int so = (int)(k & 7);
+      take = (W - k) < room ? (int)(W - k) : room;
+      const u8* s = rows + blk[j].src + (k >> 3);
+      const u32 two = ((u32)s[0] << 8) | (so + take > 8 ? (u32)s[1] : 0u);
+      v = (two >> (16 - so - take)) & ((1u << take) - 1);
+    }
+    acc |= v << (room - take);
+    pos += take;
+  }
+  return (u8)acc;
+}
 }  // namespace
 
 // ---- pack: blocks -> container --------------------------------------------------------------------------------------------
@@ -48,59 +102,13 @@ __global__ void __launch_bounds__(256) k_knz_pack(const u8* __restrict__ rows, c
     const int64_t lo = ub < firstByte ? firstByte : ub, hi = ub + 16 > lastByte ? lastByte : ub + 16;
     if (lo >= hi) continue;
     const int64_t pos0 = (lo == firstByte) ? startBit : (lo << 3);
-    // the last block whose prefix starts at or before pos0 (prefix starts grow with i)
-    int j = 0;
-    {
-      int a = 0, b = nb;                                                            // invariant: prefix start of blocks < a is <= pos0
-      while (a < b) {
-        const int m = (a + b) >> 1;
-        const int64_t W = blk[m].bits;
-        if (blk[m].pay - 5 - knz_lw(W) <= pos0) a = m + 1; else b = m;
-      }
-      j = a > 0 ? a - 1 : 0;
-    }
-    if (j < nb && hi - lo == 16) {                                                  // the whole unit inside one payload: wide load, wide store
-      const int64_t pay = blk[j].pay, W = blk[j].bits;
-      if (pos0 >= pay && (hi << 3) <= pay + W) {
-        const int64_t k = pos0 - pay;
-        const u8* row = rows + blk[j].src;
-        const u8* p = row + (k >> 3);
-        const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
-        if (al >= row && al + knz_window(p, (int)(k & 7)) <= row + ((W + 7) >> 3)) {
-          *(uint4*)(dst + lo) = knz_load128(p, (int)(k & 7));
-          continue;
-        }
-      }
-    }
+    int j = knz_find_field(blk, nb, pos0);
+    if (hi - lo == 16 && knz_wide_unit(rows, blk, nb, j, pos0, hi << 3, dst + lo)) continue;
     int64_t pos = pos0;
     for (int64_t b = lo; b < hi; b++) {
       const int64_t bend = (b + 1) << 3;
-      u32 acc = 0;
-      if (pos & 7) acc = dst[b] & (0xFFu << (8 - (int)(pos & 7)));                  // only the launch's first byte: see above
-      while (pos < bend) {
-        while (j < nb && pos >= blk[j].pay + blk[j].bits) j++;
-        if (j >= nb) break;                                                         // behind the last field: zeros
-        const int64_t pay = blk[j].pay, W = blk[j].bits;
-        const int room = (int)(bend - pos);
-        u32 v; int take;
-        if (pos < pay) {                                                            // length prefix: 5 + lw bits
-          const int lw = knz_lw(W), pw = 5 + lw;
-          const u64 field = ((u64)(lw - 3) << lw) | (u64)W;
-          const int k = (int)(pos - (pay - pw));
-          take = (int)(pay - pos) < room ? (int)(pay - pos) : room;
-          v = (u32)(field >> (pw - k - take)) & ((1u << take) - 1);
-        } else {
-          const int64_t k = pos - pay;
-          const int so = (int)(k & 7);
-          take = (W - k) < room ? (int)(W - k) : room;
-          const u8* s = rows + blk[j].src + (k >> 3);
-          const u32 two = ((u32)s[0] << 8) | (so + take > 8 ? (u32)s[1] : 0u);
-          v = (two >> (16 - so - take)) & ((1u << take) - 1);
-        }
-        acc |= v << (room - take);
-        pos += take;
-      }
-      dst[b] = (u8)acc;
+      const u32 acc = (pos & 7) ? dst[b] & (0xFFu << (8 - (int)(pos & 7))) : 0u;    // only the launch's first byte: see above
+      dst[b] = knz_compose_byte(rows, blk, nb, j, pos, bend, acc);
       pos = bend;
     }
   }
@@ -121,27 +129,33 @@ __device__ __forceinline__ u64 knz_peek64(const u8* __restrict__ src, int64_t n,
   const int sh = (int)(pos & 7);
   return sh ? ((hi << sh) | (lo >> (8 - sh))) : hi;
 }
-__global__ void k_knz_walk(const u8* __restrict__ src, int64_t n, int64_t startBit, int maxCount,
-                           int64_t* __restrict__ off, int64_t* __restrict__ bits, u64* __restrict__ hdr, int64_t* __restrict__ res) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+// the walk of one stream p[0 .. n) by one lane: entry i goes to index base + i of off / bits / hdr when i < cap, res[0 .. 3) as above
+// (base by value, not folded into the pointers: the tables' addresses stay wave-uniform)
+__device__ __forceinline__ void knz_walk_stream(const u8* __restrict__ p, int64_t n, int64_t startBit, int maxCount, int cap, int64_t base,
+                                                int64_t* __restrict__ off, int64_t* __restrict__ bits, u64* __restrict__ hdr, int64_t* __restrict__ res) {
   const int64_t nbits = n << 3;
   int64_t pos = startBit;
   int cnt = 0, why = KNZ_WALK_COUNT;
   while (cnt < maxCount) {
     if (pos + 5 > nbits) { why = KNZ_WALK_PREFIX; break; }
-    const u64 w = knz_peek64(src, n, pos);                                          // 5 + 34 bits at the most
+    const u64 w = knz_peek64(p, n, pos);                                            // 5 + 34 bits at the most
     const int lr = (int)(w >> 59) + 3;
     if (pos + 5 + lr > nbits) { why = KNZ_WALK_PREFIX; break; }
     const int64_t W = (int64_t)((w << 5) >> (64 - lr));
     const int64_t pay = pos + 5 + lr;
     if (W == 0) { why = KNZ_WALK_END; pos = pay; break; }
-    off[cnt] = pay; bits[cnt] = W; hdr[cnt] = knz_peek64(src, n, pay);               // (bytes at and behind src[n] read as zero)
+    if (cnt < cap) { off[base + cnt] = pay; bits[base + cnt] = W; hdr[base + cnt] = knz_peek64(p, n, pay); }   // (bytes at and behind p[n] read as zero)
     pos = pay;
     if (W > nbits - pay) { why = KNZ_WALK_PAYLOAD; break; }
     pos = pay + W;
     cnt++;
   }
   res[0] = cnt; res[1] = pos; res[2] = why;
+}
+__global__ void k_knz_walk(const u8* __restrict__ src, int64_t n, int64_t startBit, int maxCount,
+                           int64_t* __restrict__ off, int64_t* __restrict__ bits, u64* __restrict__ hdr, int64_t* __restrict__ res) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  knz_walk_stream(src, n, startBit, maxCount, maxCount, 0, off, bits, hdr, res);   // cap = maxCount: every entry is recorded, the one of a payload that does not fit included
 }
 
 // ---- check: index entries against the stream, each on its own ------------------------------------------------------------------
@@ -176,47 +190,50 @@ __global__ void __launch_bounds__(256) k_knz_check(const u8* __restrict__ src, i
 // Row i (rows + i * stride, 16-byte aligned) gets the bits[i] bits from bit off[i] of src, in 16-byte units; the bits behind them in
 // the last unit are zero (rows carry KZ_STREAM_SLACK bytes behind their streams).  Nothing outside src[0 .. n) is read: units
 // near either end of src load bytewise.
+// the unit u (16 bytes) of a row: the bits from bit o + 128 u of src[0 .. n), zero behind the row's W bits
+__device__ __forceinline__ uint4 knz_unpack_unit(const u8* __restrict__ src, int64_t n, int64_t o, int64_t W, int64_t u) {
+  const int64_t sb = o + (u << 7);
+  const int sh = (int)(sb & 7);
+  const u8* p = src + (sb >> 3);
+  const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
+  uint4 v;
+  if (al >= src && al + knz_window(p, sh) <= src + n) v = knz_load128(p, sh);
+  else {
+    u32 o4[4];
+    const int64_t by = sb >> 3;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      u32 x = 0;
+#pragma unroll
+      for (int t = 0; t < 4; t++) {
+        const int64_t c = by + q * 4 + t;
+        const u32 b0 = c < n ? src[c] : 0u, b1 = (sh && c + 1 < n) ? src[c + 1] : 0u;
+        x |= (((b0 << sh) | (b1 >> (8 - sh))) & 0xFFu) << (8 * t);
+      }
+      o4[q] = x;
+    }
+    v = make_uint4(o4[0], o4[1], o4[2], o4[3]);
+  }
+  const int64_t left = W - (u << 7);                                                 // bits of this unit that belong to the block
+  if (left < 128) {
+    u32* c = (u32*)&v;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int64_t l = left - 32 * q;
+      const u32 keepBE = l >= 32 ? ~0u : (l <= 0 ? 0u : ~0u << (32 - (int)l));       // mask on the big-endian view
+      c[q] &= __builtin_bswap32(keepBE);
+    }
+  }
+  return v;
+}
 __global__ void __launch_bounds__(256) k_knz_unpack(const u8* __restrict__ src, int64_t n, const int64_t* __restrict__ off, const int64_t* __restrict__ bits, int nb,
                                                     u8* __restrict__ rows, int64_t stride) {
   for (int i = blockIdx.y; i < nb; i += gridDim.y) {
     const int64_t W = bits[i], o = off[i];
     const int64_t units = (((W + 7) >> 3) + 15) >> 4;
     u8* row = rows + (int64_t)i * stride;
-    for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
-      const int64_t sb = o + (u << 7);
-      const int sh = (int)(sb & 7);
-      const u8* p = src + (sb >> 3);
-      const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
-      uint4 v;
-      if (al >= src && al + knz_window(p, sh) <= src + n) v = knz_load128(p, sh);
-      else {
-        u32 o4[4];
-        const int64_t by = sb >> 3;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          u32 x = 0;
-#pragma unroll
-          for (int t = 0; t < 4; t++) {
-            const int64_t c = by + q * 4 + t;
-            const u32 b0 = c < n ? src[c] : 0u, b1 = (sh && c + 1 < n) ? src[c + 1] : 0u;
-            x |= (((b0 << sh) | (b1 >> (8 - sh))) & 0xFFu) << (8 * t);
-          }
-          o4[q] = x;
-        }
-        v = make_uint4(o4[0], o4[1], o4[2], o4[3]);
-      }
-      const int64_t left = W - (u << 7);                                             // bits of this unit that belong to the block
-      if (left < 128) {
-        u32* c = (u32*)&v;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          const int64_t l = left - 32 * q;
-          const u32 keepBE = l >= 32 ? ~0u : (l <= 0 ? 0u : ~0u << (32 - (int)l));   // mask on the big-endian view
-          c[q] &= __builtin_bswap32(keepBE);
-        }
-      }
-      *(uint4*)(row + (u << 4)) = v;
-    }
+    for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x)
+      *(uint4*)(row + (u << 4)) = knz_unpack_unit(src, n, o, W, u);
   }
 }
 
@@ -278,58 +295,11 @@ __global__ void __launch_bounds__(256) k_knz_pack_many(const u8* __restrict__ ro
     const int64_t lo = ub < 0 ? 0 : ub, hi = ub + 16 > lastByte ? lastByte : ub + 16;
     if (lo >= hi) continue;
     const int64_t pos0 = lo << 3;
-    int j = 0;
-    {
-      int a = 0, b = nb;                                                            // invariant: prefix start of blocks < a is <= pos0
-      while (a < b) {
-        const int m = (a + b) >> 1;
-        const int64_t W = blk[m].bits;
-        if (blk[m].pay - 5 - knz_lw(W) <= pos0) a = m + 1; else b = m;
-      }
-      j = a > 0 ? a - 1 : 0;
-    }
-    if (j < nb && hi - lo == 16) {                                                  // the whole unit inside one payload: wide load, wide store
-      const int64_t pay = blk[j].pay, W = blk[j].bits;
-      if (pos0 >= pay && (hi << 3) <= pay + W) {
-        const int64_t k = pos0 - pay;
-        const u8* row = rows + blk[j].src;
-        const u8* p = row + (k >> 3);
-        const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
-        if (al >= row && al + knz_window(p, (int)(k & 7)) <= row + ((W + 7) >> 3)) {
-          *(uint4*)(d + lo) = knz_load128(p, (int)(k & 7));
-          continue;
-        }
-      }
-    }
+    int j = knz_find_field(blk, nb, pos0);
+    if (hi - lo == 16 && knz_wide_unit(rows, blk, nb, j, pos0, hi << 3, d + lo)) continue;
     for (int64_t b = lo; b < hi; b++) {
       if (b < hdrBytes) { d[b] = seg[s].hdr[b]; continue; }
-      const int64_t bend = (b + 1) << 3;
-      int64_t pos = b << 3;
-      u32 acc = 0;
-      while (pos < bend) {
-        while (j < nb && pos >= blk[j].pay + blk[j].bits) j++;
-        if (j >= nb) break;                                                         // behind the last field: zeros
-        const int64_t pay = blk[j].pay, W = blk[j].bits;
-        const int room = (int)(bend - pos);
-        u32 v; int take;
-        if (pos < pay) {                                                            // length prefix: 5 + lw bits
-          const int lw = knz_lw(W), pw = 5 + lw;
-          const u64 field = ((u64)(lw - 3) << lw) | (u64)W;
-          const int k = (int)(pos - (pay - pw));
-          take = (int)(pay - pos) < room ? (int)(pay - pos) : room;
-          v = (u32)(field >> (pw - k - take)) & ((1u << take) - 1);
-        } else {
-          const int64_t k = pos - pay;
-          const int so = (int)(k & 7);
-          take = (W - k) < room ? (int)(W - k) : room;
-          const u8* sp = rows + blk[j].src + (k >> 3);
-          const u32 two = ((u32)sp[0] << 8) | (so + take > 8 ? (u32)sp[1] : 0u);
-          v = (two >> (16 - so - take)) & ((1u << take) - 1);
-        }
-        acc |= v << (room - take);
-        pos += take;
-      }
-      d[b] = (u8)acc;
+      d[b] = knz_compose_byte(rows, blk, nb, j, b << 3, (b + 1) << 3, 0u);
     }
   }
 }
@@ -352,26 +322,7 @@ __global__ void __launch_bounds__(64) k_knz_walk_many(const u8* __restrict__ src
                                                       int64_t* __restrict__ off, int64_t* __restrict__ bits, u64* __restrict__ hdr, int64_t* __restrict__ res) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= ns) return;
-  const u8* p = src + t[s].off;
-  const int64_t n = t[s].n, nbits = n << 3, base = t[s].base;
-  const int maxCount = t[s].maxCount, cap = t[s].cap;
-  int64_t pos = t[s].startBit;
-  int cnt = 0, why = KNZ_WALK_COUNT;
-  while (cnt < maxCount) {
-    if (pos + 5 > nbits) { why = KNZ_WALK_PREFIX; break; }
-    const u64 w = knz_peek64(p, n, pos);
-    const int lr = (int)(w >> 59) + 3;
-    if (pos + 5 + lr > nbits) { why = KNZ_WALK_PREFIX; break; }
-    const int64_t W = (int64_t)((w << 5) >> (64 - lr));
-    const int64_t pay = pos + 5 + lr;
-    if (W == 0) { why = KNZ_WALK_END; pos = pay; break; }
-    if (cnt < cap) { off[base + cnt] = pay; bits[base + cnt] = W; hdr[base + cnt] = knz_peek64(p, n, pay); }
-    pos = pay;
-    if (W > nbits - pay) { why = KNZ_WALK_PAYLOAD; break; }
-    pos = pay + W;
-    cnt++;
-  }
-  res[3 * s] = cnt; res[3 * s + 1] = pos; res[3 * s + 2] = why;
+  knz_walk_stream(src + t[s].off, t[s].n, t[s].startBit, t[s].maxCount, t[s].cap, t[s].base, off, bits, hdr, res + 3 * s);
 }
 
 // ---- unpack: the blocks of many streams -> byte-aligned rows ---------------------------------------------------------------------
@@ -383,50 +334,21 @@ __global__ void __launch_bounds__(256) k_knz_unpack_many(const u8* __restrict__ 
     const int64_t n = t[i].n, W = t[i].bits, o = t[i].off;
     const int64_t units = (((W + 7) >> 3) + 15) >> 4;
     u8* row = rows + t[i].row;
-    for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
-      const int64_t sb = o + (u << 7);
-      const int sh = (int)(sb & 7);
-      const u8* p = src + (sb >> 3);
-      const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
-      uint4 v;
-      if (al >= src && al + knz_window(p, sh) <= src + n) v = knz_load128(p, sh);
-      else {
-        u32 o4[4];
-        const int64_t by = sb >> 3;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          u32 x = 0;
-#pragma unroll
-          for (int k = 0; k < 4; k++) {
-            const int64_t c = by + q * 4 + k;
-            const u32 b0 = c < n ? src[c] : 0u, b1 = (sh && c + 1 < n) ? src[c + 1] : 0u;
-            x |= (((b0 << sh) | (b1 >> (8 - sh))) & 0xFFu) << (8 * k);
-          }
-          o4[q] = x;
-        }
-        v = make_uint4(o4[0], o4[1], o4[2], o4[3]);
-      }
-      const int64_t left = W - (u << 7);
-      if (left < 128) {
-        u32* c = (u32*)&v;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          const int64_t l = left - 32 * q;
-          const u32 keepBE = l >= 32 ? ~0u : (l <= 0 ? 0u : ~0u << (32 - (int)l));
-          c[q] &= __builtin_bswap32(keepBE);
-        }
-      }
-      *(uint4*)(row + (u << 4)) = v;
-    }
+    for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x)
+      *(uint4*)(row + (u << 4)) = knz_unpack_unit(src, n, o, W, u);
   }
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------
+static inline dim3 knz_pack_grid(int64_t units) { return dim3((unsigned)std::min<int64_t>((units + 255) / 256, 1 << 20)); }
+static inline dim3 knz_unpack_grid(int nb, int64_t maxBytes) {
+  const int64_t units = (maxBytes + 15) >> 4;
+  return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((units + 255) / 256, 1 << 16)), (unsigned)std::min(nb, KZ_MAX_BATCH));
+}
 int kz_knz_pack(kz_ctx* ctx, const uint8_t* d_rows, const KnzBlk* d_blk, int nb, uint8_t* d_dst, int64_t startBit, int64_t endBit) {
   if (endBit <= startBit) return 0;
   const int64_t units = (((endBit + 7) >> 3) - (startBit >> 3) + 15 + 15) >> 4;
-  const int grid = (int)std::min<int64_t>((units + 255) / 256, 1 << 20);
-  KZ_LAUNCH(ctx, KID_KNZ_PACK, k_knz_pack, dim3(grid), dim3(256), d_rows, d_blk, nb, d_dst, startBit, endBit);
+  KZ_LAUNCH(ctx, KID_KNZ_PACK, k_knz_pack, knz_pack_grid(units), dim3(256), d_rows, d_blk, nb, d_dst, startBit, endBit);
   KZ_HIP(hipGetLastError());
   return 0;
 }
@@ -443,9 +365,7 @@ int kz_knz_check(kz_ctx* ctx, const uint8_t* d_src, int64_t n, int64_t hdrEnd, c
 }
 int kz_knz_unpack(kz_ctx* ctx, const uint8_t* d_src, int64_t n, const int64_t* d_off, const int64_t* d_bits, int nb, int64_t maxBytes, uint8_t* d_rows, int64_t stride) {
   if (nb <= 0) return 0;
-  const int64_t units = (maxBytes + 15) >> 4;
-  const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((units + 255) / 256, 1 << 16));
-  KZ_LAUNCH(ctx, KID_KNZ_UNPACK, k_knz_unpack, dim3(gx, std::min(nb, KZ_MAX_BATCH)), dim3(256), d_src, n, d_off, d_bits, nb, d_rows, stride);
+  KZ_LAUNCH(ctx, KID_KNZ_UNPACK, k_knz_unpack, knz_unpack_grid(nb, maxBytes), dim3(256), d_src, n, d_off, d_bits, nb, d_rows, stride);
   KZ_HIP(hipGetLastError());
   return 0;
 }
@@ -468,8 +388,7 @@ int kz_knz_scatter(kz_ctx* ctx, const uint8_t* d_rows, const KnzCopy* d_t, int n
 }
 int kz_knz_pack_many(kz_ctx* ctx, const uint8_t* d_rows, const KnzSeg* d_seg, int ns, const KnzBlk* d_blk, uint8_t* d_dst, int64_t units) {
   if (ns <= 0 || units <= 0) return 0;
-  const int grid = (int)std::min<int64_t>((units + 255) / 256, 1 << 20);
-  KZ_LAUNCH(ctx, KID_KNZ_PACK_MANY, k_knz_pack_many, dim3(grid), dim3(256), d_rows, d_seg, ns, d_blk, d_dst, units);
+  KZ_LAUNCH(ctx, KID_KNZ_PACK_MANY, k_knz_pack_many, knz_pack_grid(units), dim3(256), d_rows, d_seg, ns, d_blk, d_dst, units);
   KZ_HIP(hipGetLastError());
   return 0;
 }
@@ -487,9 +406,7 @@ int kz_knz_walk_many(kz_ctx* ctx, const uint8_t* d_src, const KnzSrc* d_t, int n
 }
 int kz_knz_unpack_many(kz_ctx* ctx, const uint8_t* d_src, const KnzRow* d_t, int nr, int64_t maxBytes, uint8_t* d_rows) {
   if (nr <= 0) return 0;
-  const int64_t units = (maxBytes + 15) >> 4;
-  const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((units + 255) / 256, 1 << 16));
-  KZ_LAUNCH(ctx, KID_KNZ_UNPACK_MANY, k_knz_unpack_many, dim3(gx, std::min(nr, KZ_MAX_BATCH)), dim3(256), d_src, d_t, nr, d_rows);
+  KZ_LAUNCH(ctx, KID_KNZ_UNPACK_MANY, k_knz_unpack_many, knz_unpack_grid(nr, maxBytes), dim3(256), d_src, d_t, nr, d_rows);
   KZ_HIP(hipGetLastError());
   return 0;
 }

@@ -1,0 +1,256 @@
+// kz_knz_host.h -- the host-only core of the .knz container: bit I/O, the stream header, the chain of block length prefixes, the
+// block-header precheck and the check of an index entry, and the container's rules that every call must share, each written once.
+// This is the part that parses untrusted input.  It needs no GPU and no HIP header, so that a plain C++ program can run it under
+// the sanitizers (tools/knz_host_check.cpp); kz_stream.hip and kz_stream_device.hip are its users.
+// Layout: K/io/CompressedOutputStream.java (writeHeader :236-313, ordered block emission :1024-1035, end marker :483-493) and
+// K/io/CompressedInputStream.java (readHeader :359-515, block length prefix :1127-1129).
+#pragma once
+#include <stdint.h>
+#include <string.h>
+#include <stdio.h>
+#include <algorithm>
+#include "../../include/kanzi_hip.h"
+
+struct HostBits {            // MSB-first writer (DefaultOutputBitStream.java:103-205)
+  uint8_t* p; int64_t cap; uint64_t pos; bool overflow;
+  void put(uint64_t v, int count) {
+    if (count <= 0) return;
+    if ((int64_t)((pos + count + 7) >> 3) > cap) { overflow = true; return; }
+    if (count < 64) v &= ((1ULL << count) - 1);
+    while (count > 0) {
+      const int bitoff = (int)(pos & 7), room = 8 - bitoff;
+      const int take = count < room ? count : room;
+      const uint8_t bits = (uint8_t)((v >> (count - take)) & ((1u << take) - 1));
+      if (bitoff == 0) p[pos >> 3] = 0;
+      p[pos >> 3] |= (uint8_t)(bits << (room - take));
+      pos += take; count -= take;
+    }
+  }
+  void putBytes(const uint8_t* s, uint64_t nbits) {
+    if (!nbits) return;
+    if ((int64_t)((pos + nbits + 7) >> 3) > cap) { overflow = true; return; }
+    const int sh = (int)(pos & 7);
+    const uint64_t full = nbits >> 3;
+    if (sh == 0) { if (full) memcpy(p + (pos >> 3), s, (size_t)full); pos += full << 3; }
+    else {
+      uint8_t* d = p + (pos >> 3);
+      const int up = 8 - sh;
+      if (full) {
+        d[0] = (uint8_t)((d[0] & (0xFF << up)) | (s[0] >> sh));         // keep the bits already in the partial byte
+        for (uint64_t i = 1; i < full; i++) d[i] = (uint8_t)((s[i - 1] << up) | (s[i] >> sh));   // no carried dependency: vectorises
+        d[full] = (uint8_t)(s[full - 1] << up);
+      }
+      pos += full << 3;
+    }
+    const int r = (int)(nbits & 7);
+    if (r) put((uint64_t)(s[full] >> (8 - r)), r);
+  }
+};
+struct HostBitsIn {
+  const uint8_t* p; uint64_t nbits; uint64_t pos; bool error;
+  uint64_t get(int count) {
+    if (count <= 0) return 0;
+    if (pos + (uint64_t)count > nbits) { error = true; pos = nbits; return 0; }
+    uint64_t v = 0;
+    while (count > 0) {
+      const int bitoff = (int)(pos & 7), room = 8 - bitoff;
+      const int take = count < room ? count : room;
+      v = (v << take) | (uint64_t)((p[pos >> 3] >> (room - take)) & ((1u << take) - 1));
+      pos += take; count -= take;
+    }
+    return v;
+  }
+  void getBytes(uint8_t* d, uint64_t nb) {
+    if (pos + nb > nbits) { error = true; pos = nbits; return; }
+    const int sh = (int)(pos & 7);
+    const uint64_t full = nb >> 3;
+    const uint8_t* s = p + (pos >> 3);
+    if (sh == 0) { if (full) memcpy(d, s, (size_t)full); }
+    else for (uint64_t i = 0; i < full; i++) d[i] = (uint8_t)((s[i] << sh) | (s[i + 1] >> (8 - sh)));
+    pos += full << 3;
+    const int r = (int)(nb & 7);
+    if (r) d[full] = (uint8_t)(get(r) << (8 - r));
+  }
+};
+static inline uint32_t mix32(uint32_t c, uint32_t h, uint32_t v) { c ^= h * ~v; c = (c << 13) | (c >> 19); return c * 5u + 0x52DCE729u; }
+static inline int ilog2(uint32_t x) { return 31 - __builtin_clz(x); }
+
+// ---- the container's rules, one definition each ----
+// width of the length field of a block of W bits (:1024-1035): the smallest lw >= 3 with W < 2^lw
+static inline int knz_prefix_width(uint64_t W) { return W < 8 ? 3 : ilog2((uint32_t)(W >> 3)) + 4; }
+// the 2-bit checksum field of the stream header <-> the ABI's checksumBits (0 / 32 / 64); -1: not a value of the ABI
+static inline int knz_chk_kind(int32_t checksumBits) { return checksumBits == 0 ? 0 : (checksumBits == 32 ? 1 : (checksumBits == 64 ? 2 : -1)); }
+static inline int32_t knz_chk_bits(int chkKind) { return chkKind == 1 ? 32 : (chkKind == 2 ? 64 : 0); }
+// block sizes a writer takes (CompressedOutputStream.java:165-174)
+static inline bool knz_block_size_ok(int32_t blockSize) { return blockSize >= 1024 && blockSize <= (1 << 30) && !(blockSize & 15); }
+// Sequence length (TransformFactory.java:240-266): the non-zero 6-bit fields of the transform word, 1 at the least
+static inline int knz_nb_functions(uint64_t transformType) {
+  int nb = 0;
+  for (int i = 0; i < 8; i++) if (((transformType >> (42 - 6 * i)) & 0x3F) != 0) nb++;
+  return nb ? nb : 1;
+}
+// the decoder's staging row: a block's stream bound and 64 bytes of slack, in whole 256-byte lines
+static inline int64_t knz_dec_row_stride(int32_t blockSize) {
+  return (int64_t)(((size_t)blockSize + (size_t)(blockSize >> 3) + 1024 + 64 + 255) / 256 * 256);
+}
+// how many blocks may still start inside `room` bytes of destination
+static inline int64_t knz_fit_blocks(int64_t room, int32_t blockSize) { return room <= 0 ? 0 : (room + blockSize - 1) / blockSize; }
+
+// ---- stream header ----
+static inline uint32_t header_cksum(int chkKind, int entropyType, uint64_t tt, int blockSize, int szMask, int64_t inputSize) {
+  const uint32_t HASH = 0x1E35A7BDu;                          // CompressedOutputStream.java:293-309
+  uint32_t c = HASH * (0x01030507u * 7u);
+  c = mix32(c, HASH, (uint32_t)chkKind);
+  c = mix32(c, HASH, (uint32_t)entropyType);
+  c = mix32(c, HASH, (uint32_t)(tt >> 32));
+  c = mix32(c, HASH, (uint32_t)tt);
+  c = mix32(c, HASH, (uint32_t)blockSize);
+  if (szMask > 0) { c = mix32(c, HASH, (uint32_t)((uint64_t)inputSize >> 32)); c = mix32(c, HASH, (uint32_t)inputSize); }
+  return ((c >> 23) ^ (c >> 3)) & 0xFFFFFF;
+}
+static inline int write_stream_header(HostBits& bs, uint64_t transformType, uint32_t entropyType, int32_t blockSize, int64_t n, int chkKind = 0) {
+  bs.put(0x4B414E5A, 32); bs.put(7, 4); bs.put((uint64_t)chkKind, 2);
+  bs.put(entropyType, 5); bs.put(transformType, 48); bs.put((uint32_t)blockSize >> 4, 28);
+  int szMask = 0;
+  if (n != 0 && n < (1LL << 48)) {
+    if (n >= (1LL << 32)) szMask = 3;
+    else { int64_t isz = n; if (isz > (1LL << 30)) { isz >>= 4; szMask++; } szMask += (ilog2((uint32_t)isz) >> 4) + 1; }
+  }
+  bs.put((uint64_t)szMask, 2);
+  if (szMask > 0) bs.put((uint64_t)n, 16 * szMask);
+  bs.put(0, 15);
+  bs.put(header_cksum(chkKind, (int)entropyType, transformType, blockSize, szMask, n), 24);
+  return szMask;
+}
+// Stream header, checked in the reference's order and with its codes (CompressedInputStream.java:359-478).
+struct KnzHeader { int chkKind, entropyType, blockSize, szMask; uint64_t transformType; int64_t inputSize; };
+static inline int read_stream_header(HostBitsIn& bs, KnzHeader& h, char* err, size_t errCap) {
+  if (bs.get(32) != 0x4B414E5A) return -KZ_ERR_INVALID_FILE;                                    // :367-368
+  const int bsVersion = (int)bs.get(4);
+  if (bsVersion != 7) {                                                                            // :374-377; older layouts are not built here
+    if (err) snprintf(err, errCap, "cannot read this version of the stream: %d (only 7 is built)", bsVersion);
+    return -KZ_ERR_STREAM_VERSION;
+  }
+  h.chkKind = (int)bs.get(2);
+  if (h.chkKind > 2) return -KZ_ERR_INVALID_FILE;                                               // :390-392
+  h.entropyType = (int)bs.get(5);
+  if (h.entropyType == 3 || h.entropyType > 9) return -KZ_ERR_INVALID_CODEC;                     // EntropyCodecFactory.getName :212-243
+  h.transformType = bs.get(48);
+  for (int i = 0; i < 8; i++) {                                                                  // TransformFactory.getName :368-449
+    const int t = (int)((h.transformType >> (42 - 6 * i)) & 0x3F);
+    if (t == 4 || t > 19) return -KZ_ERR_INVALID_CODEC;
+  }
+  h.blockSize = (int)(bs.get(28) << 4);
+  if (h.blockSize < 1024 || h.blockSize > (1 << 30)) return -KZ_ERR_BLOCK_SIZE;                  // :419-422
+  h.szMask = (int)bs.get(2);
+  h.inputSize = h.szMask ? (int64_t)bs.get(16 * h.szMask) : 0;
+  bs.get(15);
+  const uint32_t ck = (uint32_t)bs.get(24);
+  if (bs.error || ck != header_cksum(h.chkKind, h.entropyType, h.transformType, h.blockSize, h.szMask, h.inputSize))
+    return -KZ_ERR_CRC_CHECK;                                                                    // :477-478
+  return 0;
+}
+// the header's fields into the out-pointers of the index calls (each may be null)
+static inline void knz_header_out(const KnzHeader& h, uint64_t* transformType, uint32_t* entropyType, int32_t* blockSize, int64_t* inputSize, int32_t* checksumBits) {
+  if (transformType) *transformType = h.transformType;
+  if (entropyType) *entropyType = (uint32_t)h.entropyType;
+  if (blockSize) *blockSize = h.blockSize;
+  if (inputSize) *inputSize = h.inputSize;
+  if (checksumBits) *checksumBits = knz_chk_bits(h.chkKind);
+}
+
+// What a reading call derives from a parsed header, once (filled by knz_plan, kz_knz_stream.h): the transform count, the decoder's
+// staging row, the decoder's batch NB and chunk CH, and the bit behind the stream header.
+struct KnzPlan { KnzHeader h; int nbFunctions; int64_t iS; int64_t NB; int CH; int64_t hdrEnd; };
+
+// ---- blocks ----
+static inline void write_block(HostBits& bs, const uint8_t* stream, uint64_t written) {   // :1024-1035
+  const int lw = knz_prefix_width(written);
+  bs.put((uint64_t)(lw - 3), 5);
+  bs.put(written, lw);
+  bs.putBytes(stream, written);
+}
+static inline void write_end_marker(HostBits& bs) { bs.put(0, 5); bs.put(0, 3); }         // :491-492
+// one length prefix (:1127-1129): 0 and W > 0 with bs at the block's payload, KNZ_PREFIX_END behind the end marker, or
+// -KZ_ERR_READ_FILE when the prefix does not fit in the stream
+enum { KNZ_PREFIX_END = 1 };
+static inline int knz_read_prefix(HostBitsIn& bs, uint64_t& W) {
+  const int lr = (int)bs.get(5) + 3;
+  W = bs.get(lr);
+  if (bs.error) return -KZ_ERR_READ_FILE;
+  return W == 0 ? KNZ_PREFIX_END : 0;
+}
+
+// Host restatement of DecodingTask.readBlockHeader + the two checks that follow it
+// (CompressedInputStream.java:1025-1095, :1145-1164): the reference validates a block's header on the shared
+// bit stream BEFORE it reads the payload, so a truncated or tampered stream is reported with the header's error
+// (ERR_CRC_CHECK / ERR_BLOCK_SIZE / ERR_READ_FILE), not as a short read.  Returns 0 or -(error code).
+static inline int precheck_block_header(HostBitsIn bs /* by value: peek */, uint64_t W, int nbFunctions, int blockSize, int chkKind) {
+  if (W < 8) return -KZ_ERR_BLOCK_SIZE;
+  const uint32_t mode = (uint32_t)bs.get(8);
+  uint32_t skipFlags = 0;
+  bool hasSkip = false;
+  if (mode & 0x80) {
+    if (mode & 0x10) { if (nbFunctions > 4) hasSkip = true; else skipFlags = ((mode << 4) | 0x0F) & 0xFF; }
+  } else if (mode & 0x10) hasSkip = true;
+  else skipFlags = ((mode << 4) | 0x0F) & 0xFF;
+  const int dataSize = 1 + (int)((mode >> 5) & 3);
+  const int headerSize = 1 + (hasSkip ? 1 : 0) + dataSize + 1;
+  if (W < (uint64_t)headerSize * 8) return -KZ_ERR_BLOCK_SIZE;
+  if (hasSkip) skipFlags = (uint32_t)bs.get(8);
+  uint32_t preLen = 0;
+  for (int i = 0; i < dataSize; i++) preLen = (preLen << 8) | (uint32_t)bs.get(8);
+  const uint32_t ck = (uint32_t)bs.get(8);
+  if (bs.error) return -KZ_ERR_READ_FILE;
+  const uint32_t HASH = 0x1E35A7BDu;
+  uint32_t c = HASH * 0x01030507u;
+  c = mix32(c, HASH, mode & 0xFF);
+  c = mix32(c, HASH, skipFlags & 0xFF);
+  c = mix32(c, HASH, preLen);
+  c = mix32(c, HASH, (uint32_t)(W >> 32));
+  c = mix32(c, HASH, (uint32_t)W);
+  c = (c >> 23) ^ (c >> 3);
+  if (ck != (c & 0xFF)) return -KZ_ERR_CRC_CHECK;
+  const int64_t maxTL = std::min<int64_t>(std::max<int64_t>((int64_t)blockSize + blockSize / 2, 2048), 1LL << 30);
+  if ((int32_t)preLen < 0 || (int64_t)preLen > maxTL) return -KZ_ERR_READ_FILE;
+  const int checksumSize = (chkKind == 2) ? 8 : (chkKind == 1 ? 4 : 0);
+  if ((int64_t)((W + 7) >> 3) > (int64_t)preLen + headerSize + checksumSize) return -KZ_ERR_BLOCK_SIZE;
+  return 0;
+}
+// A reader's checks on one block of W bits whose payload starts at bit `at` of a stream of nbits bits, in the reader's order: the
+// block header (peek: a reader at the payload's first bit), the staging-row bound, the payload's end inside the stream.  The indexed
+// host read leaves the last one to knz_check_entry (checkEnd = false).  Returns 0 or -(error code).
+static inline int knz_check_block(HostBitsIn peek, uint64_t W, uint64_t at, uint64_t nbits, const KnzPlan& P, bool checkEnd = true) {
+  int rc = precheck_block_header(peek, W, P.nbFunctions, P.h.blockSize, P.h.chkKind);
+  if (!rc && (int64_t)((W + 7) >> 3) > P.iS - 64) rc = -KZ_ERR_BLOCK_SIZE;
+  if (!rc && checkEnd && at + W > nbits) rc = -KZ_ERR_READ_FILE;
+  return rc;
+}
+// the next block of a serial reader: knz_read_prefix's results, then knz_check_block's code for the block; bs stays at the payload
+static inline int knz_next_block(HostBitsIn& bs, const KnzPlan& P, uint64_t& W) {
+  const int rc = knz_read_prefix(bs, W);
+  return rc ? rc : knz_check_block(bs, W, bs.pos, bs.nbits, P);
+}
+// What becomes of a decoded block when `produced` bytes of a destination of dstCap bytes are taken: 0 (it is appended, :783-785) or
+// the code that ends the stream, in the reader's order -- its status, "incorrectly decompressed" (:756-759), no room.
+static inline int knz_block_verdict(const kz_block_result& r, int32_t blockSize, int64_t produced, int64_t dstCap) {
+  if (r.status) return r.status;
+  if (r.length > blockSize) return -KZ_ERR_PROCESS_BLOCK;
+  if (produced + r.length > dstCap) return -KZ_ERR_WRITE_FILE;
+  return 0;
+}
+
+// An index entry against the stream, on its own (no walk): the 5 + lr bits in front of bit `off` read (lr - 3, W) for some lr in
+// 3 .. 34, and lie behind bit hdrEnd; W > 0 ends inside the stream
+static inline bool knz_check_entry(const uint8_t* src, int64_t n, int64_t hdrEnd, int64_t off, int64_t W) {
+  const int64_t nbits = n * 8;
+  if (W <= 0 || W >= (1LL << 34) || off < hdrEnd + 8 || off > nbits || W > nbits - off) return false;
+  const int lo = std::max(3, 64 - __builtin_clzll((unsigned long long)W));
+  for (int lr = lo; lr <= 34; lr++) {
+    const int64_t at = off - 5 - lr;
+    if (at < hdrEnd) break;
+    HostBitsIn t{src, (uint64_t)nbits, (uint64_t)at, false};
+    if ((int)t.get(5) + 3 == lr && (int64_t)t.get(lr) == W) return true;
+  }
+  return false;
+}

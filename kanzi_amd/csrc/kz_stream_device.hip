@@ -1,0 +1,724 @@
+// kz_stream_device.hip -- the .knz container with source and destination in HBM: the same streams as kz_stream.hip's calls write and
+// read, whole, by block range, by index, and many at a time.  The kernels are in kz_knz_gpu.hip; what stays on the host is what
+// kz_compress / kz_decompress do there as well and costs nothing: the stream header (kz_knz_host.h, on a copy of at most 26 bytes),
+// the bit-offset arithmetic over results[] (host arrays anyway), and the block checks on the 8 header bytes per block that the walk
+// kernel brings back.  The rules shared with the host-buffer calls are in kz_knz_host.h and kz_knz_stream.h.
+#include "kz_knz_stream.h"
+
+namespace {
+// `need` bytes of pinned table and of its HBM mirror behind 64 bytes of front (the stream header resp. a walk's result).  All device
+// calls use the same two buffers: nothing is kept in them across a call.
+int knz_tables(kz_ctx* ctx, size_t need) {
+  int rc = kz_stage_reserve(ctx, ctx->knzPin, need + 64, true);
+  if (!rc) rc = kz_stage_reserve(ctx, ctx->knzAux, need + 64, false);
+  return rc;
+}
+// A view of those tables from byte `at` of both: `front` bytes, then columns of cap 8-byte entries each.  The walk's tables are
+// (off, bits, hdr), the index check's (off, bits, hdr, bad); the d_ forms are the HBM mirror's.
+struct KnzTable {
+  uint8_t* pin; uint8_t* dev; size_t front; int64_t cap;
+  KnzTable(kz_ctx* ctx, int64_t cap_, size_t at = 0, size_t front_ = 64) : pin(ctx->knzPin.p + at), dev(ctx->knzAux.p + at), front(front_), cap(cap_) {}
+  size_t bytes(int cols) const { return front + (size_t)cols * (size_t)cap * 8; }
+  int64_t* head() const { return (int64_t*)pin; }
+  int64_t* col(int k) const { return (int64_t*)(pin + front) + k * cap; }
+  int64_t* d_head() const { return (int64_t*)dev; }
+  int64_t* d_col(int k) const { return (int64_t*)(dev + front) + k * cap; }
+  int64_t* off() const { return col(0); }
+  int64_t* bits() const { return col(1); }
+  uint64_t* hdr() const { return (uint64_t*)col(2); }
+  int64_t* bad() const { return col(3); }
+  int64_t* d_off() const { return d_col(0); }
+  int64_t* d_bits() const { return d_col(1); }
+  uint64_t* d_hdr() const { return (uint64_t*)d_col(2); }
+  int64_t* d_bad() const { return d_col(3); }
+};
+// The layout of a run of blocks behind bit `pos` of a stream: rows of W[i] bits (W[i] <= 0: no block), the row of block i at byte
+// rowBase + i * stride.  Per block its length prefix, then its payload, entered at t[m++].  Returns the bit behind the last payload.
+int64_t knz_layout_rows(const int64_t* W, int cnt, int64_t pos, int64_t rowBase, int64_t stride, KnzBlk* t, int& m) {
+  for (int i = 0; i < cnt; i++) {
+    if (W[i] <= 0) continue;
+    pos += 5 + knz_prefix_width((uint64_t)W[i]);
+    t[m++] = KnzBlk{pos, W[i], rowBase + (int64_t)i * stride};
+    pos += W[i];
+  }
+  return pos;
+}
+// The rows' streams (W[i] bits each, rows `stride` apart, W[i] <= 0: no block) go behind bit `pos` of d_dst, then tailBits zero bits;
+// pos moves behind them.  -KZ_ERR_WRITE_FILE, nothing launched, when that does not fit in dstCap bytes.
+int knz_pack_rows(kz_ctx* ctx, const uint8_t* d_rows, int64_t stride, const int64_t* W, int cnt, uint8_t* d_dst, int64_t dstCap, int64_t& pos, int tailBits) {
+  KnzBlk* t = (KnzBlk*)(ctx->knzPin.p + 64);
+  int m = 0;
+  const int64_t end = knz_layout_rows(W, cnt, pos, 0, stride, t, m) + tailBits;
+  if (((end + 7) >> 3) > dstCap) return -KZ_ERR_WRITE_FILE;
+  if (m) KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + 64, t, (size_t)m * sizeof(KnzBlk), hipMemcpyHostToDevice, ctx->stream));
+  const int rc = kz_knz_pack(ctx, d_rows, (const KnzBlk*)(ctx->knzAux.p + 64), m, d_dst, pos, end);
+  pos = end;
+  return rc;
+}
+// the stream header goes up from the front of the pinned table; the caller waits for the stream before it returns
+int knz_put_header(kz_ctx* ctx, const uint8_t* hdr, int64_t hdrBytes, uint8_t* d_dst) {
+  memcpy(ctx->knzPin.p, hdr, (size_t)hdrBytes);
+  KZ_HIP(hipMemcpyAsync(d_dst, ctx->knzPin.p, (size_t)hdrBytes, hipMemcpyHostToDevice, ctx->stream));
+  return 0;
+}
+int knz_get_header(kz_ctx* ctx, const uint8_t* d_src, int64_t n, uint8_t* hdr /*32*/, int64_t& hn) {
+  memset(hdr, 0, 32);
+  hn = std::min<int64_t>(n, 26);                                 // the longest header: 160 + 48 bits
+  if (hn > 0) {
+    KZ_HIP(hipMemcpyAsync(hdr, d_src, (size_t)hn, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  }
+  return 0;
+}
+// a reader over the first bytes of d_src (hdr: the 32 bytes that hold them), for the stream header of a reading call
+int knz_open(kz_ctx* ctx, const uint8_t* d_src, int64_t n, uint8_t* hdr /*32*/, HostBitsIn& bs) {
+  int64_t hn = 0;
+  { const int rc = knz_get_header(ctx, d_src, n, hdr, hn); if (rc) return rc; }
+  bs = HostBitsIn{hdr, (uint64_t)hn * 8, 0, false};
+  return 0;
+}
+}  // namespace
+
+extern "C" int64_t kz_knz_assemble_device(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int32_t blockSize, int64_t inputSize,
+                                          int32_t checksumBits, const uint8_t* d_streams, int64_t stride, const int64_t* bits, int32_t nBlocks,
+                                          uint8_t* d_dst, int64_t dstCap) {
+  if (!ctx || !d_dst || nBlocks < 0 || (nBlocks > 0 && (!d_streams || !bits))) return -KZ_ERR_INVALID_PARAM;
+  if (knz_chk_kind(checksumBits) < 0) return -KZ_ERR_INVALID_PARAM;
+  KZ_HIP(hipSetDevice(ctx->device));
+  uint8_t hdr[32];
+  HostBits hb{hdr, 32, 0, false};
+  write_stream_header(hb, transformType, entropyType, blockSize, inputSize, knz_chk_kind(checksumBits));
+  { const int rc = knz_tables(ctx, (size_t)std::max(nBlocks, 1) * sizeof(KnzBlk)); if (rc) return rc; }
+  int64_t pos = (int64_t)hb.pos;                                // (a whole number of bytes: 160 + 16 k bits)
+  const int rc = knz_pack_rows(ctx, d_streams, stride, bits, nBlocks, d_dst, dstCap, pos, 8);   // end marker (:491-492)
+  if (rc) return rc;
+  { const int hrc = knz_put_header(ctx, hdr, (int64_t)(hb.pos >> 3), d_dst); if (hrc) return hrc; }
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  return (pos + 7) >> 3;
+}
+
+extern "C" int64_t kz_compress_device(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int32_t blockSize,
+                                      const uint8_t* d_src, int64_t n, uint8_t* d_dst, int64_t dstCap) {
+  if (!ctx || !d_src || !d_dst || n < 0) return -KZ_ERR_INVALID_PARAM;
+  if (!knz_block_size_ok(blockSize)) return -KZ_ERR_BLOCK_SIZE;
+  KZ_HIP(hipSetDevice(ctx->device));
+  uint8_t hdr[32];
+  HostBits hb{hdr, 32, 0, false};
+  write_stream_header(hb, transformType, entropyType, blockSize, n, ctx->checksum);
+  const int64_t nblocks = (n + blockSize - 1) / blockSize;
+  BlockSizeScope scope(ctx, blockSize);
+  const int CH = (int)std::min<int64_t>(knz_chunk_blocks(ctx, blockSize), std::max<int64_t>(nblocks, 1));
+  const int64_t oS = kz_max_block_stream_bytes(blockSize);
+  {
+    int rc = kz_stage_reserve(ctx, ctx->devOut[0], (size_t)CH * oS, false);
+    if (!rc) rc = knz_tables(ctx, (size_t)CH * sizeof(KnzBlk));
+    if (rc) return rc;
+  }
+  auto tooSmall = [&]() { snprintf(ctx->err, sizeof(ctx->err), "kz_compress_device: destination too small"); return (int64_t)-KZ_ERR_WRITE_FILE; };
+  uint8_t* rows = ctx->devOut[0].p;
+  std::vector<int32_t> lens(CH);
+  std::vector<kz_block_result> res(CH);
+  std::vector<int64_t> W(CH);
+  int64_t pos = (int64_t)hb.pos;
+  // ---- chunks, one after the other: encode HBM -> HBM rows, pack the rows behind the previous chunk's last bit ----
+  for (int64_t b0 = 0; b0 < nblocks; b0 += CH) {
+    const int cnt = (int)std::min<int64_t>(CH, nblocks - b0);
+    for (int i = 0; i < cnt; i++) lens[i] = (int32_t)std::min<int64_t>(blockSize, n - (b0 + i) * blockSize);
+    // a device row may be read up to the call's longest block whatever its own length is (kz_encode_blocks's contract), and behind
+    // the stream's last, short block lies memory that is not the caller's: that block goes in a call of its own
+    const int full = lens[cnt - 1] < blockSize ? cnt - 1 : cnt;
+    int rc = 0;
+    if (full) rc = kz_encode_blocks_pre(ctx, transformType, entropyType, blockSize, d_src + b0 * blockSize, blockSize, lens.data(), full,
+                                        rows, oS, res.data(), KZ_MEM_DEVICE, nullptr);
+    if (!rc && full < cnt) rc = kz_encode_blocks_pre(ctx, transformType, entropyType, blockSize, d_src + (b0 + full) * blockSize, blockSize, lens.data() + full, 1,
+                                                     rows + (int64_t)full * oS, oS, res.data() + full, KZ_MEM_DEVICE, nullptr);
+    if (rc) return rc;
+    for (int i = 0; i < cnt; i++) { if (res[i].status) return res[i].status; W[i] = res[i].bits; }
+    rc = knz_pack_rows(ctx, rows, oS, W.data(), cnt, d_dst, dstCap, pos, b0 + cnt >= nblocks ? 8 : 0);   // the last chunk: end marker (:491-492)
+    if (rc == -KZ_ERR_WRITE_FILE) return tooSmall();
+    if (rc) return rc;
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));                    // the rows and the pinned table are the next chunk's
+    kz_ktimer_flush(ctx);
+  }
+  if (nblocks == 0) {
+    const int rc = knz_pack_rows(ctx, rows, oS, W.data(), 0, d_dst, dstCap, pos, 8);
+    if (rc == -KZ_ERR_WRITE_FILE) return tooSmall();
+    if (rc) return rc;
+  }
+  { const int hrc = knz_put_header(ctx, hdr, (int64_t)(hb.pos >> 3), d_dst); if (hrc) return hrc; }
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  return (pos + 7) >> 3;
+}
+
+namespace {
+// walk up to maxCount (<= T.cap) prefixes from bit pos and bring the tables back (arrays = 2: offsets and lengths, 3: the header bytes as well)
+int knz_walk_chunk(kz_ctx* ctx, const KnzTable& T, const uint8_t* d_src, int64_t n, int64_t pos, int maxCount, int arrays) {
+  { const int rc = kz_knz_walk(ctx, d_src, n, pos, maxCount, T.d_off(), T.d_bits(), T.d_hdr(), T.d_head()); if (rc) return rc; }
+  KZ_HIP(hipMemcpyAsync(T.pin, T.dev, T.bytes(arrays), hipMemcpyDeviceToHost, ctx->stream));
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  if (T.head()[0] < 0 || T.head()[0] > maxCount) { snprintf(ctx->err, sizeof(ctx->err), "knz walk: bad count"); return -KZ_ERR_DEVICE; }
+  return 0;
+}
+// the entries a walk recorded: the blocks walked whole, and the one whose payload does not fit (recorded before its end is looked at)
+inline int knz_walk_have(int64_t got, int64_t why) { return (int)got + (why == KNZ_WALK_PAYLOAD ? 1 : 0); }
+// knz_check_block on a block that the device walked or checked: the block header is read from the 8 bytes it brought back
+int knz_check_walked(uint64_t hdr, uint64_t rd, uint64_t at, uint64_t nbits, const KnzPlan& P) {
+  uint8_t hb8[8];
+  for (int k = 0; k < 8; k++) hb8[k] = (uint8_t)(hdr >> (56 - 8 * k));
+  const HostBitsIn t{hb8, std::min<uint64_t>(64, nbits - at), 0, false};          // the header is 7 bytes at the most
+  return knz_check_block(t, rd, at, nbits, P);
+}
+}  // namespace
+
+extern "C" int32_t kz_knz_index_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, uint64_t* transformType, uint32_t* entropyType,
+                                       int32_t* blockSize, int64_t* inputSize, int32_t* checksumBits, int64_t* blockBitOff, int64_t* blockBits, int32_t cap) {
+  if (!ctx) return -KZ_ERR_INVALID_PARAM;
+  if (!d_src || n < 20) return -KZ_ERR_INVALID_FILE;
+  KZ_HIP(hipSetDevice(ctx->device));
+  uint8_t hdr[32]; HostBitsIn bs;
+  { const int rc = knz_open(ctx, d_src, n, hdr, bs); if (rc) return rc; }
+  KnzHeader h;
+  { const int hrc = read_stream_header(bs, h, nullptr, 0); if (hrc) return hrc; }
+  knz_header_out(h, transformType, entropyType, blockSize, inputSize, checksumBits);
+  const int CH = (int)std::min<int64_t>(16384, n / 8 + 16);
+  { const int rc = knz_tables(ctx, (size_t)CH * 24); if (rc) return rc; }
+  const KnzTable T(ctx, CH);
+  int64_t pos = (int64_t)bs.pos, nb = 0;
+  for (;;) {
+    { const int rc = knz_walk_chunk(ctx, T, d_src, n, pos, CH, 2); if (rc) return rc; }
+    const int why = (int)T.head()[2], have = knz_walk_have(T.head()[0], why);     // kz_knz_index records a block before it looks at its end
+    for (int i = 0; i < have; i++, nb++)
+      if (nb < cap) { if (blockBitOff) blockBitOff[nb] = T.off()[i]; if (blockBits) blockBits[nb] = T.bits()[i]; }
+    if (why == KNZ_WALK_PREFIX || why == KNZ_WALK_PAYLOAD) return -KZ_ERR_READ_FILE;
+    if (why == KNZ_WALK_END) break;
+    pos = T.head()[1];
+    if (nb > 0x7FFFFFFF - CH) return -KZ_ERR_INVALID_FILE;
+  }
+  return (int32_t)nb;
+}
+
+// kz_decompress_device and kz_decompress_range_device: decompress_host's contract (kz_stream.hip), source and destination in HBM.
+// kz_decompress looks at the room left in dst once per batch of ITS size (KnzPlan::NB), so chunks never straddle those batches and
+// carry the batch's count of blocks that may still start inside dst: both calls cut a stream at the same block.
+static int64_t decompress_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, int64_t firstBlock, int64_t nBlocks, uint8_t* d_dst, int64_t dstCap) {
+  KZ_HIP(hipSetDevice(ctx->device));
+  uint8_t hdr[32]; HostBitsIn bs;
+  { const int rc = knz_open(ctx, d_src, n, hdr, bs); if (rc) return rc; }
+  KnzHeader h;
+  { const int hrc = read_stream_header(bs, h, ctx->err, sizeof(ctx->err)); if (hrc) return hrc; }
+  const KnzPlan P = knz_plan(ctx, h, n, (int64_t)bs.pos);
+  const int entropyType = h.entropyType, blockSize = h.blockSize, CH = P.CH;
+  const uint64_t tt = h.transformType, nbits = (uint64_t)n * 8;
+  const int64_t iS = P.iS;
+  ChecksumScope chk(ctx, h.chkKind);
+  if (nBlocks == 0) return 0;
+  // blocks in front of the range are walked in the index call's chunks (the walk is all that happens to them), unless
+  // KZ_STREAM_CHUNK says otherwise
+  const int SK = firstBlock == 0 ? 0 : (ctx->sw.streamChunk > 0 ? CH : (int)std::min<int64_t>(16384, n / 8 + 16));
+  { const int rc = knz_tables(ctx, (size_t)std::max(CH, SK) * 24); if (rc) return rc; }
+  int64_t pos = P.hdrEnd, produced = 0;
+  for (int64_t k = 0; k < firstBlock;) {                         // read and skipped: prefix and block header, not the payload
+    const KnzTable T(ctx, SK);
+    { const int rc = knz_walk_chunk(ctx, T, d_src, n, pos, (int)std::min<int64_t>(SK, firstBlock - k), 3); if (rc) return rc; }
+    const int why = (int)T.head()[2], have = knz_walk_have(T.head()[0], why);
+    for (int i = 0; i < have; i++) {
+      const int rc = knz_check_walked(T.hdr()[i], (uint64_t)T.bits()[i], (uint64_t)T.off()[i], nbits, P);
+      if (rc) return rc;
+    }
+    if (why == KNZ_WALK_PREFIX) return -KZ_ERR_READ_FILE;
+    if (why == KNZ_WALK_END) return 0;                            // the end marker in front of the range
+    pos = T.head()[1];
+    k += have;
+  }
+  const KnzTable T(ctx, CH);
+  std::vector<kz_block_result> res(CH);
+  bool done = false;
+  int pending = 0;
+  int64_t batchLeft = 0, fitLeft = 0;
+  int64_t left = nBlocks < 0 ? INT64_MAX : nBlocks;               // blocks of the range not walked yet
+  while (!done) {
+    if (left == 0) break;                                         // the end of the range: nothing behind it is read
+    if (batchLeft == 0) { batchLeft = P.NB; fitLeft = knz_fit_blocks(dstCap - produced, blockSize); }
+    const int want = (int)std::min<int64_t>(std::min<int64_t>(CH, batchLeft), left);
+    // ---- the walk on the device, then kz_decompress's checks in kz_decompress's order on what it recorded.  A fault met here is
+    //      held back until the blocks before it have been decoded: the reference reports the FIRST failing block in stream order ----
+    { const int rc = knz_walk_chunk(ctx, T, d_src, n, pos, want, 3); if (rc) return rc; }
+    const int why = (int)T.head()[2], have = knz_walk_have(T.head()[0], why);
+    pos = T.head()[1];
+    int cnt = 0;
+    for (; cnt < have; cnt++) {
+      pending = knz_check_walked(T.hdr()[cnt], (uint64_t)T.bits()[cnt], (uint64_t)T.off()[cnt], nbits, P);
+      if (pending) break;
+    }
+    left -= cnt;
+    if (!pending) { if (why == KNZ_WALK_PREFIX) pending = -KZ_ERR_READ_FILE; else if (why == KNZ_WALK_END) done = true; }
+    if (pending) done = true;
+    if (cnt == 0) break;
+    // blocks that start past the end of the destination cannot be stored (kz_decompress)
+    if (fitLeft < cnt) { cnt = (int)fitLeft; pending = -KZ_ERR_WRITE_FILE; done = true; }
+    if (cnt == 0) break;
+    fitLeft -= cnt; batchLeft -= cnt;
+    int64_t maxBytes = 0;
+    for (int i = 0; i < cnt; i++) maxBytes = std::max<int64_t>(maxBytes, (T.bits()[i] + 7) >> 3);
+    { const int rc = kz_stage_reserve(ctx, ctx->devIn[0], (size_t)cnt * iS, false); if (rc) return rc; }   // (grow-only: the blocks walked, not the chunk's most)
+    { const int rc = kz_knz_unpack(ctx, d_src, n, T.d_off(), T.d_bits(), cnt, maxBytes, ctx->devIn[0].p, iS); if (rc) return rc; }
+    // ---- blocks whose whole blockSize row lies inside what is left of dst are decoded in place; the others (as a rule the last
+    //      block of a destination of the exact size) into staging rows ----
+    const int nd = (int)std::min<int64_t>(cnt, (dstCap - produced) / blockSize);
+    if (cnt > nd) { const int rc = kz_stage_reserve(ctx, ctx->devOut[0], (size_t)(cnt - nd) * blockSize, false); if (rc) return rc; }
+    int rc = 0;
+    if (nd) rc = kz_decode_blocks(ctx, tt, (uint32_t)entropyType, blockSize, ctx->devIn[0].p, iS, T.bits(), nd,
+                                  d_dst + produced, blockSize, res.data(), KZ_MEM_DEVICE);
+    if (!rc && cnt > nd) rc = kz_decode_blocks(ctx, tt, (uint32_t)entropyType, blockSize, ctx->devIn[0].p + (int64_t)nd * iS, iS, T.bits() + nd, cnt - nd,
+                                               ctx->devOut[0].p, blockSize, res.data() + nd, KZ_MEM_DEVICE);
+    if (rc) return rc;
+    // ---- the reader appends whatever a block produced (:783-785): a block behind a short one moves left, in stream order; the
+    //      first failing block ends the stream, the blocks in front of it are delivered ----
+    const int64_t base = produced;
+    int code = 0;
+    for (int i = 0; i < cnt; i++) {
+      code = knz_block_verdict(res[i], blockSize, produced, dstCap);
+      if (code) break;
+      const int64_t len = res[i].length;
+      const uint8_t* from = i < nd ? d_dst + base + (int64_t)i * blockSize : ctx->devOut[0].p + (int64_t)(i - nd) * blockSize;
+      uint8_t* to = d_dst + produced;
+      if (len > 0 && from != to) {
+        if (i < nd && from - to < len) {                          // overlapping move: through the staging rows, which are done with
+          KZ_HIP(hipMemcpyAsync(ctx->devIn[0].p, from, (size_t)len, hipMemcpyDeviceToDevice, ctx->stream));
+          from = ctx->devIn[0].p;
+        }
+        KZ_HIP(hipMemcpyAsync(to, from, (size_t)len, hipMemcpyDeviceToDevice, ctx->stream));
+      }
+      produced += len;
+    }
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+    if (code) return code;
+  }
+  return pending ? pending : produced;
+}
+
+extern "C" int64_t kz_decompress_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, uint8_t* d_dst, int64_t dstCap) {
+  if (!ctx || !d_src || !d_dst || n < 0) return -KZ_ERR_INVALID_PARAM;
+  return decompress_device(ctx, d_src, n, 0, -1, d_dst, dstCap);
+}
+extern "C" int64_t kz_decompress_range_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, int64_t firstBlock, int64_t nBlocks, uint8_t* d_dst, int64_t dstCap) {
+  if (!ctx || !d_src || !d_dst || n < 0 || firstBlock < 0 || nBlocks < 0) return -KZ_ERR_INVALID_PARAM;
+  return decompress_device(ctx, d_src, n, firstBlock, nBlocks, d_dst, dstCap);
+}
+
+
+// =================================================================================================
+// many .knz streams on device memory: kz_compress_device / kz_decompress_device for N (segment, slot) pairs in one call.  Whole
+// streams are collected into groups of at most one chunk's blocks; the blocks of a group go through ONE batched encode (one decode
+// per distinct header), and the container kernels (kz_knz_gpu.hip: gather, pack, heads, walk, unpack, scatter) take a table with an
+// entry per segment, slot or row, so launches and host waits per group do not grow with the streams in it.  A stream with more
+// blocks than a group takes goes through the single-stream call, which is the definition of every result here.
+namespace {
+int knz_many_args(const void* ctx, const void* d_src, const int64_t* srcOff, const int64_t* srcLen, int32_t nStreams,
+                  const void* d_dst, const int64_t* dstOff, const int64_t* dstCap, const int64_t* dstLen) {
+  if (!ctx || nStreams < 0) return -KZ_ERR_INVALID_PARAM;
+  if (nStreams == 0) return 0;
+  if (!d_src || !srcOff || !srcLen || !d_dst || !dstOff || !dstCap || !dstLen) return -KZ_ERR_INVALID_PARAM;
+  for (int s = 0; s < nStreams; s++) if (srcOff[s] < 0 || srcLen[s] < 0 || dstOff[s] < 0 || dstCap[s] < 0) return -KZ_ERR_INVALID_PARAM;
+  return 0;
+}
+inline int64_t knz_units16(const uint8_t* p, int64_t len) {        // 16-byte aligned units of memory that [p, p + len) touches
+  const uintptr_t a = (uintptr_t)p;
+  return (int64_t)((((a + (uintptr_t)len + 15) & ~(uintptr_t)15) - (a & ~(uintptr_t)15)) >> 4);
+}
+
+// streams [s0, s1) of a kz_compress_many_device call: together at most one chunk's blocks
+int compress_group(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int32_t blockSize, const uint8_t* d_src, const int64_t* srcOff,
+                   const int64_t* srcLen, int s0, int s1, uint8_t* d_dst, const int64_t* dstOff, const int64_t* dstCap, int64_t* dstLen) {
+  const int ns = s1 - s0;
+  int64_t nbTot = 0;
+  for (int s = s0; s < s1; s++) nbTot += (srcLen[s] + blockSize - 1) / blockSize;
+  const int NBk = (int)nbTot;
+  const int64_t oS = kz_max_block_stream_bytes(blockSize);
+  const size_t gatherBytes = kz_align((size_t)NBk * sizeof(KnzCopy) + 64, 64), segBytes = (size_t)ns * sizeof(KnzSeg);
+  {
+    int rc = kz_stage_reserve(ctx, ctx->devIn[0], (size_t)std::max(NBk, 1) * (size_t)blockSize, false);
+    if (!rc) rc = kz_stage_reserve(ctx, ctx->devOut[0], (size_t)std::max(NBk, 1) * (size_t)oS, false);
+    if (!rc) rc = knz_tables(ctx, gatherBytes + segBytes + (size_t)NBk * sizeof(KnzBlk));
+    if (rc) return rc;
+  }
+  uint8_t* rowsIn = ctx->devIn[0].p;
+  uint8_t* rows = ctx->devOut[0].p;
+  std::vector<int32_t> lens(NBk);
+  std::vector<kz_block_result> res(NBk);
+  int erc = 0;
+  if (NBk) {
+    // ---- gather: every block into a row of its own, blockSize apart (the encoder may read a device row up to the call's longest
+    //      block, and behind a stream's last block lies memory that is not that stream's) ----
+    KnzCopy* g = (KnzCopy*)ctx->knzPin.p;
+    int r = 0;
+    for (int s = s0; s < s1; s++)
+      for (int64_t o = 0; o < srcLen[s]; o += blockSize, r++) {
+        lens[r] = (int32_t)std::min<int64_t>(blockSize, srcLen[s] - o);
+        g[r] = KnzCopy{srcOff[s] + o, (int64_t)r * blockSize, lens[r]};
+      }
+    KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, g, (size_t)NBk * sizeof(KnzCopy), hipMemcpyHostToDevice, ctx->stream));
+    { const int rc = kz_knz_gather(ctx, d_src, (const KnzCopy*)ctx->knzAux.p, NBk, blockSize, rowsIn); if (rc) return rc; }
+    // the encoder takes device input to be complete when it is called: chains led by TEXT / UTF copy rows back on another stream
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+    BlockSizeScope scope(ctx, blockSize);
+    erc = kz_encode_blocks_pre(ctx, transformType, entropyType, blockSize, rowsIn, blockSize, lens.data(), NBk, rows, oS, res.data(), KZ_MEM_DEVICE, nullptr);
+    if (erc == -KZ_ERR_DEVICE) return erc;
+  }
+  std::vector<int64_t> W((size_t)NBk);
+  for (int i = 0; i < NBk; i++) W[i] = res[i].bits;
+  // ---- per stream what kz_compress_device does per stream: header, bit offsets over results[], the fit in the slot ----
+  KnzSeg* seg = (KnzSeg*)(ctx->knzPin.p + gatherBytes);
+  KnzBlk* blk = (KnzBlk*)(ctx->knzPin.p + gatherBytes + segBytes);
+  int m = 0, nseg = 0, r0 = 0;
+  int64_t units = 0;
+  for (int s = s0; s < s1; s++) {
+    const int nb = (int)((srcLen[s] + blockSize - 1) / blockSize);
+    const int first = r0;
+    r0 += nb;
+    int64_t code = nb ? erc : 0;                                  // (an empty stream asks nothing of the encoder)
+    for (int i = 0; i < nb && !code; i++) code = res[first + i].status;
+    if (code) { dstLen[s] = code; continue; }
+    KnzSeg S;
+    memset(&S, 0, sizeof(S));
+    uint8_t hdr[32] = {0};
+    HostBits hb{hdr, 32, 0, false};
+    write_stream_header(hb, transformType, entropyType, blockSize, srcLen[s], ctx->checksum);
+    const int m0 = m;
+    const int64_t end = knz_layout_rows(W.data() + first, nb, (int64_t)hb.pos, (int64_t)first * oS, oS, blk, m) + 8;   // end marker (:491-492)
+    if (((end + 7) >> 3) > dstCap[s]) {
+      m = m0;
+      snprintf(ctx->err, sizeof(ctx->err), "kz_compress_many_device: destination %d too small", s);
+      dstLen[s] = -KZ_ERR_WRITE_FILE;
+      continue;
+    }
+    S.dst = dstOff[s]; S.endBit = end; S.unit0 = units; S.blk0 = m0; S.nblk = m - m0; S.hdrBytes = (int32_t)(hb.pos >> 3);
+    memcpy(S.hdr, hdr, 28);
+    seg[nseg++] = S;
+    units += knz_units16(d_dst + dstOff[s], (end + 7) >> 3);
+    dstLen[s] = (end + 7) >> 3;
+  }
+  if (nseg) {
+    uint8_t* a = ctx->knzAux.p + gatherBytes;
+    KZ_HIP(hipMemcpyAsync(a, seg, segBytes + (size_t)m * sizeof(KnzBlk), hipMemcpyHostToDevice, ctx->stream));
+    const int rc = kz_knz_pack_many(ctx, rows, (const KnzSeg*)a, nseg, (const KnzBlk*)(a + segBytes), d_dst, units);
+    if (rc) return rc;
+  }
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  return 0;
+}
+}  // namespace
+
+extern "C" int64_t kz_compress_many_bound(const int64_t* srcLen, int32_t nStreams, int32_t blockSize) {
+  if (nStreams < 0 || (nStreams > 0 && !srcLen)) return -KZ_ERR_INVALID_PARAM;
+  int64_t total = 0;
+  for (int s = 0; s < nStreams; s++) {
+    const int64_t b = kz_compress_bound(srcLen[s], blockSize);
+    if (b < 0) return b;
+    total += b;
+  }
+  return total;
+}
+
+extern "C" int32_t kz_compress_many_device(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int32_t blockSize,
+                                           const uint8_t* d_src, const int64_t* srcOff, const int64_t* srcLen, int32_t nStreams,
+                                           uint8_t* d_dst, const int64_t* dstOff, const int64_t* dstCap, int64_t* dstLen) {
+  { const int rc = knz_many_args(ctx, d_src, srcOff, srcLen, nStreams, d_dst, dstOff, dstCap, dstLen); if (rc || nStreams == 0) return rc; }
+  if (!knz_block_size_ok(blockSize)) return -KZ_ERR_BLOCK_SIZE;   // kz_compress_device's check
+  KZ_HIP(hipSetDevice(ctx->device));
+  const int64_t G = knz_chunk_blocks(ctx, blockSize);
+  auto blocksOf = [&](int s) { return (srcLen[s] + blockSize - 1) / blockSize; };
+  for (int s0 = 0; s0 < nStreams;) {
+    if (blocksOf(s0) > G) {                                       // larger than a group: the single-stream call, on its own
+      dstLen[s0] = kz_compress_device(ctx, transformType, entropyType, blockSize, d_src + srcOff[s0], srcLen[s0], d_dst + dstOff[s0], dstCap[s0]);
+      if (dstLen[s0] == -KZ_ERR_DEVICE) return -KZ_ERR_DEVICE;
+      s0++;
+      continue;
+    }
+    int s1 = s0;
+    int64_t tot = 0;                                              // (an empty stream counts as one block: a group's tables stay bounded)
+    while (s1 < nStreams && blocksOf(s1) <= G && (s1 == s0 || tot + std::max<int64_t>(blocksOf(s1), 1) <= G)) { tot += std::max<int64_t>(blocksOf(s1), 1); s1++; }
+    const int rc = compress_group(ctx, transformType, entropyType, blockSize, d_src, srcOff, srcLen, s0, s1, d_dst, dstOff, dstCap, dstLen);
+    if (rc) return rc;
+    s0 = s1;
+  }
+  return 0;
+}
+
+namespace {
+struct KnzManyStream {                                             // a stream of a kz_decompress_many_device call after the header parse
+  KnzPlan plan; int code;                                          // (the walk starts at plan.hdrEnd)
+  int cnt, why;                                                    // the count pass
+};
+// the streams ids[0 .. ng) of a kz_decompress_many_device call: their walk stops inside a single-stream chunk, and together they
+// hold at most a group's blocks (have[k] entries each, the one of a payload that does not fit included)
+int decompress_group(kz_ctx* ctx, const std::vector<KnzManyStream>& st, const int* ids, const int* have, int ng, const uint8_t* d_src, const int64_t* srcOff,
+                     const int64_t* srcLen, uint8_t* d_dst, const int64_t* dstOff, const int64_t* dstCap, int64_t* dstLen) {
+  int64_t E = 0;
+  for (int k = 0; k < ng; k++) E += have[k];
+  // ---- fill pass: the entries of all streams in one table, at the exclusive scan of the counts ----
+  const size_t tBytes = kz_align((size_t)ng * sizeof(KnzSrc), 64), outBytes = (size_t)ng * 24 + (size_t)E * 24;
+  { const int rc = knz_tables(ctx, tBytes + outBytes); if (rc) return rc; }
+  const KnzTable T(ctx, E, tBytes, (size_t)ng * 24);              // behind the KnzSrc entries: res[3 ng], then off[E], bits[E], hdr[E]
+  {
+    KnzSrc* t = (KnzSrc*)ctx->knzPin.p;
+    int64_t base = 0;
+    for (int k = 0; k < ng; k++) {
+      const int s = ids[k];
+      t[k] = KnzSrc{srcOff[s], srcLen[s], st[s].plan.hdrEnd, base, st[s].plan.CH + 1, have[k]};
+      base += have[k];
+    }
+  }
+  const int64_t* res = T.head();
+  const int64_t* off = T.off();
+  const int64_t* bits = T.bits();
+  const uint64_t* hdr = T.hdr();
+  KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, ctx->knzPin.p, (size_t)ng * sizeof(KnzSrc), hipMemcpyHostToDevice, ctx->stream));
+  { const int rc = kz_knz_walk_many(ctx, d_src, (const KnzSrc*)ctx->knzAux.p, ng, T.d_off(), T.d_bits(), T.d_hdr(), T.d_head()); if (rc) return rc; }
+  KZ_HIP(hipMemcpyAsync(T.pin, T.dev, outBytes, hipMemcpyDeviceToHost, ctx->stream));
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  // ---- per stream kz_decompress_device's checks on its one chunk, in its order; a fault is held back behind the blocks in front ----
+  struct Part { int s, first, cnt, pending, cls; int64_t base; };
+  struct Cls { uint64_t tt; int et, bs, chk; int64_t iS; int rows; int64_t inBase, outBase; int first; };
+  std::vector<Part> parts(ng);
+  std::vector<Cls> cls;
+  int64_t base = 0;
+  for (int k = 0; k < ng; k++) {
+    const int s = ids[k];
+    const KnzPlan& S = st[s].plan;
+    const int64_t got = res[3 * k], why = res[3 * k + 2];
+    if (got < 0 || got > S.CH + 1) { snprintf(ctx->err, sizeof(ctx->err), "knz walk: bad count"); return -KZ_ERR_DEVICE; }
+    const int hv = std::min(knz_walk_have(got, why), have[k]);
+    const uint64_t nbits = (uint64_t)srcLen[s] * 8;
+    int cnt = 0, pending = 0;
+    for (; cnt < hv; cnt++) {
+      pending = knz_check_walked(hdr[base + cnt], (uint64_t)bits[base + cnt], (uint64_t)off[base + cnt], nbits, S);
+      if (pending) break;
+    }
+    if (!pending && why != KNZ_WALK_END) pending = -KZ_ERR_READ_FILE;     // a prefix that does not fit
+    if (cnt > 0) {                                                // blocks that start past the end of the destination cannot be stored
+      const int64_t fit = knz_fit_blocks(dstCap[s], S.h.blockSize);
+      if (fit < cnt) { cnt = (int)fit; pending = -KZ_ERR_WRITE_FILE; }
+    }
+    int c = 0;
+    for (; c < (int)cls.size(); c++) if (cls[c].tt == S.h.transformType && cls[c].et == S.h.entropyType && cls[c].bs == S.h.blockSize && cls[c].chk == S.h.chkKind) break;
+    if (c == (int)cls.size()) cls.push_back(Cls{S.h.transformType, S.h.entropyType, S.h.blockSize, S.h.chkKind, S.iS, 0, 0, 0, 0});
+    parts[k] = Part{s, cls[c].rows, cnt, pending, c, base};
+    cls[c].rows += cnt;
+    base += have[k];
+  }
+  int64_t inBytes = 0, outBytes2 = 0;
+  int R = 0;
+  for (Cls& c : cls) { c.inBase = inBytes; c.outBase = outBytes2; c.first = R; inBytes += (int64_t)c.rows * c.iS; outBytes2 += (int64_t)c.rows * c.bs; R += c.rows; }
+  std::vector<int64_t> W((size_t)std::max(R, 1));
+  std::vector<kz_block_result> bres((size_t)std::max(R, 1));
+  // the walk's tables are read for the last time while the unpack table is built: it goes behind them
+  const size_t rowBytes = kz_align((size_t)R * sizeof(KnzRow), 64), copyBytes = (size_t)R * sizeof(KnzCopy);
+  std::vector<KnzRow> rowT((size_t)R);
+  int64_t maxBytes = 0;
+  for (int k = 0; k < ng; k++) {
+    const Part& P = parts[k];
+    const Cls& c = cls[P.cls];
+    for (int i = 0; i < P.cnt; i++) {
+      const int r = c.first + P.first + i;
+      W[r] = bits[P.base + i];
+      maxBytes = std::max<int64_t>(maxBytes, (W[r] + 7) >> 3);
+      rowT[r] = KnzRow{srcOff[P.s], srcLen[P.s], off[P.base + i], W[r], c.inBase + (int64_t)(P.first + i) * c.iS};
+    }
+  }
+  if (R) {
+    int rc = kz_stage_reserve(ctx, ctx->devIn[0], (size_t)inBytes + 64, false);
+    if (!rc) rc = kz_stage_reserve(ctx, ctx->devOut[0], (size_t)outBytes2 + 64, false);
+    if (!rc) rc = knz_tables(ctx, rowBytes + copyBytes);          // (may move the tables: everything needed from them is in W / rowT / parts)
+    if (rc) return rc;
+    memcpy(ctx->knzPin.p, rowT.data(), (size_t)R * sizeof(KnzRow));
+    KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, ctx->knzPin.p, (size_t)R * sizeof(KnzRow), hipMemcpyHostToDevice, ctx->stream));
+    rc = kz_knz_unpack_many(ctx, d_src, (const KnzRow*)ctx->knzAux.p, R, maxBytes, ctx->devIn[0].p);
+    if (rc) return rc;
+  }
+  // ---- one decode per distinct header, into staging rows ----
+  std::vector<int> crc(cls.size(), 0);
+  {
+    ChecksumScope chk(ctx, ctx->checksum);                        // each class decodes under its own header's kind
+    for (size_t c = 0; c < cls.size(); c++) {
+      const Cls& C = cls[c];
+      if (!C.rows) continue;
+      ctx->checksum = C.chk;
+      crc[c] = kz_decode_blocks(ctx, C.tt, (uint32_t)C.et, C.bs, ctx->devIn[0].p + C.inBase, C.iS, W.data() + C.first, C.rows,
+                                ctx->devOut[0].p + C.outBase, C.bs, bres.data() + C.first, KZ_MEM_DEVICE);
+      if (crc[c] == -KZ_ERR_DEVICE) return crc[c];
+    }
+  }
+  // ---- scatter: each stream's blocks into its slot back to back, cut where kz_decompress_device cuts it ----
+  KnzCopy* ct = R ? (KnzCopy*)(ctx->knzPin.p + rowBytes) : nullptr;
+  int nc = 0;
+  int64_t maxLen = 0;
+  for (int k = 0; k < ng; k++) {
+    const Part& P = parts[k];
+    const Cls& C = cls[P.cls];
+    if (P.cnt > 0 && crc[P.cls]) { dstLen[P.s] = crc[P.cls]; continue; }
+    int64_t produced = 0;
+    int code = 0;
+    for (int i = 0; i < P.cnt; i++) {
+      const kz_block_result& b = bres[C.first + P.first + i];
+      code = knz_block_verdict(b, C.bs, produced, dstCap[P.s]);
+      if (code) break;
+      if (b.length > 0) {
+        ct[nc++] = KnzCopy{C.outBase + (int64_t)(P.first + i) * C.bs, dstOff[P.s] + produced, b.length};
+        maxLen = std::max<int64_t>(maxLen, b.length);
+      }
+      produced += b.length;
+    }
+    dstLen[P.s] = code ? code : (P.pending ? P.pending : produced);
+  }
+  if (nc) {
+    KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + rowBytes, ct, (size_t)nc * sizeof(KnzCopy), hipMemcpyHostToDevice, ctx->stream));
+    const int rc = kz_knz_scatter(ctx, ctx->devOut[0].p, (const KnzCopy*)(ctx->knzAux.p + rowBytes), nc, maxLen, d_dst);
+    if (rc) return rc;
+  }
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  return 0;
+}
+}  // namespace
+
+extern "C" int32_t kz_decompress_many_device(kz_ctx* ctx, const uint8_t* d_src, const int64_t* srcOff, const int64_t* srcLen, int32_t nStreams,
+                                             uint8_t* d_dst, const int64_t* dstOff, const int64_t* dstCap, int64_t* dstLen) {
+  { const int rc = knz_many_args(ctx, d_src, srcOff, srcLen, nStreams, d_dst, dstOff, dstCap, dstLen); if (rc || nStreams == 0) return rc; }
+  KZ_HIP(hipSetDevice(ctx->device));
+  const int ns = nStreams;
+  std::vector<KnzManyStream> st((size_t)ns);
+  // ---- the first bytes of every stream in one table, one copy; the headers are parsed here with kz_decompress_device's codes ----
+  const size_t tBytes = kz_align((size_t)ns * sizeof(KnzSrc), 64), headBytes = (size_t)ns * 32, resBytes = (size_t)ns * 24;
+  { const int rc = knz_tables(ctx, tBytes + std::max(headBytes, resBytes)); if (rc) return rc; }
+  KnzSrc* t = (KnzSrc*)ctx->knzPin.p;
+  const KnzSrc* d_t = (const KnzSrc*)ctx->knzAux.p;
+  for (int s = 0; s < ns; s++) t[s] = KnzSrc{srcOff[s], srcLen[s], 0, 0, 0, 0};
+  KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, t, (size_t)ns * sizeof(KnzSrc), hipMemcpyHostToDevice, ctx->stream));
+  { const int rc = kz_knz_heads(ctx, d_src, d_t, ns, ctx->knzAux.p + tBytes); if (rc) return rc; }
+  KZ_HIP(hipMemcpyAsync(ctx->knzPin.p + tBytes, ctx->knzAux.p + tBytes, headBytes, hipMemcpyDeviceToHost, ctx->stream));
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  bool firstFault = true;
+  for (int s = 0; s < ns; s++) {
+    KnzManyStream& S = st[s];
+    memset(&S, 0, sizeof(S));
+    const int64_t n = srcLen[s], hn = std::min<int64_t>(n, 26);
+    HostBitsIn bs{ctx->knzPin.p + tBytes + (size_t)s * 32, (uint64_t)hn * 8, 0, false};
+    KnzHeader h;
+    S.code = read_stream_header(bs, h, firstFault ? ctx->err : nullptr, sizeof(ctx->err));   // (the text of the first failing stream stays)
+    if (S.code) { firstFault = false; t[s].maxCount = 0; continue; }
+    S.plan = knz_plan(ctx, h, n, (int64_t)bs.pos);                // decompress_device's batch and chunk
+    t[s].startBit = S.plan.hdrEnd; t[s].maxCount = S.plan.CH + 1;
+  }
+  // ---- count pass: one lane per stream walks one block further than a single-stream chunk goes.  A walk that stops by itself
+  //      (end marker or fault) is what kz_decompress_device sees in its one chunk with blocks: such a stream can join a group ----
+  KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, t, (size_t)ns * sizeof(KnzSrc), hipMemcpyHostToDevice, ctx->stream));
+  { const int rc = kz_knz_walk_many(ctx, d_src, d_t, ns, nullptr, nullptr, nullptr, (int64_t*)(ctx->knzAux.p + tBytes)); if (rc) return rc; }
+  KZ_HIP(hipMemcpyAsync(ctx->knzPin.p + tBytes, ctx->knzAux.p + tBytes, resBytes, hipMemcpyDeviceToHost, ctx->stream));
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  {
+    const int64_t* res = (const int64_t*)(ctx->knzPin.p + tBytes);
+    for (int s = 0; s < ns; s++) {
+      if (st[s].code) continue;
+      if (res[3 * s] < 0 || res[3 * s] > st[s].plan.CH + 1) { snprintf(ctx->err, sizeof(ctx->err), "knz walk: bad count"); return -KZ_ERR_DEVICE; }
+      st[s].cnt = (int)res[3 * s]; st[s].why = (int)res[3 * s + 2];
+    }
+  }
+  // ---- groups of whole streams: at most a chunk's blocks (decompress_device's batch: 2048 blocks, 8 GiB) ----
+  const int64_t capBlocks = ctx->sw.streamChunk > 0 ? ctx->sw.streamChunk : 2048, capBytes = 8LL << 30;
+  std::vector<int> ids, have;
+  int64_t gBlocks = 0, gBytes = 0;
+  auto flush = [&]() -> int {
+    if (ids.empty()) return 0;
+    const int rc = decompress_group(ctx, st, ids.data(), have.data(), (int)ids.size(), d_src, srcOff, srcLen, d_dst, dstOff, dstCap, dstLen);
+    ids.clear(); have.clear(); gBlocks = 0; gBytes = 0;
+    return rc;
+  };
+  for (int s = 0; s < ns; s++) {
+    const KnzManyStream& S = st[s];
+    if (S.code) { dstLen[s] = S.code; continue; }
+    if (S.why == KNZ_WALK_COUNT) {                                // more blocks than a group takes: the single-stream call, on its own
+      dstLen[s] = decompress_device(ctx, d_src + srcOff[s], srcLen[s], 0, -1, d_dst + dstOff[s], dstCap[s]);
+      if (dstLen[s] == -KZ_ERR_DEVICE) return -KZ_ERR_DEVICE;
+      continue;
+    }
+    const int hv = knz_walk_have(S.cnt, S.why);
+    const int64_t blocks = std::max(hv, 1), bytes = blocks * S.plan.h.blockSize;
+    if (!ids.empty() && (gBlocks + blocks > capBlocks || gBytes + bytes > capBytes)) { const int rc = flush(); if (rc) return rc; }
+    ids.push_back(s); have.push_back(hv);
+    gBlocks += blocks; gBytes += bytes;
+  }
+  return flush();
+}
+
+
+// =================================================================================================
+// indexed reads: blocks of a stream by their (bit offset, bit length) pairs, as kz_knz_index / kz_knz_index_device return them, in
+// any order.  No walk: every pair is checked against the stream on its own (k_knz_check), which makes the call memory safe for any
+// index and brings the block-header bytes for the prechecks; it does not prove that a pair lies on the chain of prefixes that
+// starts behind the stream header.
+extern "C" int32_t kz_decode_indexed_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, const int64_t* blockBitOff, const int64_t* blockBits, int32_t nBlocks,
+                                            uint8_t* d_dst, int64_t dstStride, kz_block_result* results) {
+  if (!ctx || !d_src || n < 0 || nBlocks < 0 || (nBlocks > 0 && (!blockBitOff || !blockBits || !d_dst || !results))) return -KZ_ERR_INVALID_PARAM;
+  KZ_HIP(hipSetDevice(ctx->device));
+  uint8_t hdr[32]; HostBitsIn bs;
+  { const int rc = knz_open(ctx, d_src, n, hdr, bs); if (rc) return rc; }
+  KnzPlan P;
+  { const int rc = indexed_open(ctx, bs, n, dstStride, P); if (rc) return rc; }
+  if (nBlocks == 0) return 0;
+  ChecksumScope chk(ctx, P.h.chkKind);
+  const int CH = (int)std::min<int64_t>(knz_chunk_blocks(ctx, P.h.blockSize), nBlocks);
+  // the chunk's tables, pinned and in HBM: 64 spare bytes, then off[CH], bits[CH], hdr[CH], bad[CH]
+  { const int rc = knz_tables(ctx, (size_t)CH * 32); if (rc) return rc; }
+  const KnzTable T(ctx, CH);
+  // ---- every entry against the stream, before anything is unpacked; the block-header bytes stay on the host for the second pass ----
+  std::vector<uint64_t> hdrs((size_t)nBlocks);
+  for (int64_t b0 = 0; b0 < nBlocks; b0 += CH) {
+    const int cnt = (int)std::min<int64_t>(CH, nBlocks - b0);
+    memcpy(T.off(), blockBitOff + b0, (size_t)cnt * 8);
+    memcpy(T.bits(), blockBits + b0, (size_t)cnt * 8);
+    KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+    KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+    { const int rc = kz_knz_check(ctx, d_src, n, P.hdrEnd, T.d_off(), T.d_bits(), cnt, T.d_hdr(), T.d_bad()); if (rc) return rc; }
+    KZ_HIP(hipMemcpyAsync(T.hdr(), T.d_hdr(), (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(hipMemcpyAsync(T.bad(), T.d_bad(), (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+    kz_ktimer_flush(ctx);
+    for (int i = 0; i < cnt; i++) {
+      if (T.bad()[i]) return indexed_mismatch(ctx, b0 + i);
+      hdrs[(size_t)(b0 + i)] = T.hdr()[i];
+    }
+  }
+  // ---- chunks: prechecks on the host, unpack the entries that pass into staging rows, decode them into their rows of d_dst ----
+  const uint64_t nbits = (uint64_t)n * 8;
+  for (int64_t b0 = 0; b0 < nBlocks; b0 += CH) {
+    const int cnt = (int)std::min<int64_t>(CH, nBlocks - b0);
+    kz_block_result* res = results + b0;
+    int64_t maxBytes = 0;
+    for (int i = 0; i < cnt; i++) {
+      const int64_t W = blockBits[b0 + i];
+      const int rc = knz_check_walked(hdrs[(size_t)(b0 + i)], (uint64_t)W, (uint64_t)blockBitOff[b0 + i], nbits, P);
+      memset(&res[i], 0, sizeof(res[i]));
+      res[i].bits = W; res[i].status = rc;
+      T.off()[i] = blockBitOff[b0 + i];
+      T.bits()[i] = rc ? 0 : W;                                     // a row of no bits: nothing of it is unpacked
+      if (!rc) maxBytes = std::max<int64_t>(maxBytes, (W + 7) >> 3);
+    }
+    if (maxBytes == 0) continue;
+    KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+    KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+    { const int rc = kz_stage_reserve(ctx, ctx->devIn[0], (size_t)cnt * P.iS, false); if (rc) return rc; }
+    { const int rc = kz_knz_unpack(ctx, d_src, n, T.d_off(), T.d_bits(), cnt, maxBytes, ctx->devIn[0].p, P.iS); if (rc) return rc; }
+    { const int rc = indexed_decode_runs(ctx, P, ctx->devIn[0].p, blockBits + b0, cnt, d_dst + b0 * dstStride, dstStride, res, KZ_MEM_DEVICE); if (rc) return rc; }
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));                      // the pinned table is the next chunk's
+    kz_ktimer_flush(ctx);
+  }
+  return 0;
+}

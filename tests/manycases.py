@@ -159,7 +159,7 @@ def interleave(bad, good):
     return streams, goods
 
 
-# ---- the grouping both calls use, restated (kz_stream.hip) ----------------------------------------------------------------------
+# ---- the grouping both calls use, restated (kz_stream_device.hip) ----------------------------------------------------------------------
 def writer_groups(lens, bs, chunk):
     """kz_compress_many_device: consecutive streams with at most `chunk` blocks together (an empty stream counts as one); a
     stream with more blocks goes alone through the single-stream call -> [("group", [i ...]) | ("single", [i])]"""

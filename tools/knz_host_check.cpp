@@ -1,0 +1,272 @@
+// knz_host_check.cpp -- the host-only core of the .knz container (kanzi_amd/csrc/kz_knz_host.h: bit I/O, stream header, prefix chain,
+// block-header precheck, index-entry check) under the sanitizers, on the CPU:
+//   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I kanzi_amd/csrc tools/knz_host_check.cpp -o /tmp/knz_host_check && /tmp/knz_host_check
+// Every buffer is a heap allocation of the exact size, so a read or write one byte outside it is reported.
+#include "kz_knz_host.h"
+#include <stdlib.h>
+#include <memory>
+#include <vector>
+
+typedef std::unique_ptr<uint8_t[]> Buf;
+static Buf buf(size_t n, int fill = 0xA5) { Buf b(new uint8_t[n]); if (n) memset(b.get(), fill, n); return b; }
+static long checked = 0;
+#define CHECK(cond, ...) do { if (!(cond)) { printf("knz_host_check FAILED %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); exit(1); } checked++; } while (0)
+static uint32_t rnd() { static uint32_t s = 0x2545F491u; s ^= s << 13; s ^= s >> 17; s ^= s << 5; return s; }
+
+// ---- prefix width: the smallest lw >= 3 with W < 2^lw, and a prefix written by write_block read back by knz_read_prefix ----
+static void check_prefix_width() {
+  std::vector<uint64_t> Ws = {1, 7, 8, 15, 16};
+  for (int k = 4; k <= 33; k++) { Ws.push_back((1ULL << k) - 1); Ws.push_back(1ULL << k); Ws.push_back((1ULL << k) + 1); }
+  for (uint64_t W : Ws) {
+    int want = 3;
+    while (W >= (1ULL << want)) want++;
+    const int lw = knz_prefix_width(W);
+    CHECK(lw == want, "prefix width of %llu: %d, want %d", (unsigned long long)W, lw, want);
+    // the prefix alone: the destination ends with it and the payload buffer is empty, so write_block must stop at the payload
+    // (overflow) without reading a byte of it
+    const size_t pb = (size_t)(5 + lw + 7) / 8;
+    Buf d = buf(pb), none = buf(0);
+    HostBits bs{d.get(), (int64_t)pb, 0, false};
+    write_block(bs, none.get(), W);
+    CHECK(bs.overflow && bs.pos == (uint64_t)(5 + lw), "write_block of %llu bits into a prefix-sized buffer: pos %llu", (unsigned long long)W, (unsigned long long)bs.pos);
+    HostBitsIn in{d.get(), (uint64_t)(5 + lw), 0, false};
+    uint64_t rd = 0;
+    CHECK(knz_read_prefix(in, rd) == 0 && rd == W && in.pos == (uint64_t)(5 + lw) && !in.error, "prefix of %llu read back as %llu", (unsigned long long)W, (unsigned long long)rd);
+  }
+  // the end marker reads as the end, a cut prefix as a fault
+  Buf e = buf(1);
+  HostBits bs{e.get(), 1, 0, false};
+  write_end_marker(bs);
+  HostBitsIn in{e.get(), 8, 0, false};
+  uint64_t rd = 1;
+  CHECK(knz_read_prefix(in, rd) == KNZ_PREFIX_END && rd == 0, "end marker");
+  HostBitsIn cut{e.get(), 7, 0, false};
+  CHECK(knz_read_prefix(cut, rd) == -KZ_ERR_READ_FILE, "cut prefix");
+}
+
+// ---- bit I/O: putBytes / getBytes against put(., 1) / get(1), at every start phase ----
+static void check_bit_io() {
+  std::vector<int> lens;
+  for (int l = 0; l <= 40; l++) lens.push_back(l);
+  for (int l : {63, 64, 65, 127, 128, 129}) lens.push_back(l);
+  for (int phase = 0; phase < 8; phase++)
+    for (int L : lens) {
+      const size_t sb = (size_t)(L + 7) / 8, total = (size_t)(phase + L + 7) / 8;
+      Buf src = buf(sb);
+      for (size_t i = 0; i < sb; i++) src[i] = (uint8_t)rnd();
+      auto bit = [&](int i) { return (src[i >> 3] >> (7 - (i & 7))) & 1; };
+      // cap exactly reached
+      Buf a = buf(total, 0xFF), b = buf(total, 0xFF);
+      HostBits wa{a.get(), (int64_t)total, 0, false}, wb{b.get(), (int64_t)total, 0, false};
+      for (int i = 0; i < phase; i++) { wa.put((uint64_t)(i & 1), 1); wb.put((uint64_t)(i & 1), 1); }
+      wa.putBytes(src.get(), (uint64_t)L);
+      for (int i = 0; i < L; i++) wb.put((uint64_t)bit(i), 1);
+      CHECK(!wa.overflow && !wb.overflow && wa.pos == wb.pos && wa.pos == (uint64_t)(phase + L), "putBytes phase %d len %d: pos %llu", phase, L, (unsigned long long)wa.pos);
+      CHECK(total == 0 || memcmp(a.get(), b.get(), total) == 0, "putBytes phase %d len %d differs from bit-by-bit put", phase, L);
+      // read back, both ways
+      HostBitsIn ra{a.get(), (uint64_t)(phase + L), 0, false}, rb{a.get(), (uint64_t)(phase + L), 0, false};
+      for (int i = 0; i < phase; i++) { CHECK(ra.get(1) == (uint64_t)(i & 1), "phase bit %d", i); rb.get(1); }
+      Buf out = buf(sb, 0xFF);
+      ra.getBytes(out.get(), (uint64_t)L);
+      CHECK(!ra.error && ra.pos == (uint64_t)(phase + L), "getBytes phase %d len %d", phase, L);
+      for (int i = 0; i < L; i++) {
+        const int g = (int)rb.get(1);
+        CHECK(g == bit(i) && ((out[i >> 3] >> (7 - (i & 7))) & 1) == bit(i), "bit %d of phase %d len %d", i, phase, L);
+      }
+      CHECK(!rb.error, "get(1) phase %d len %d", phase, L);
+      if (L & 7) CHECK((out[sb - 1] & (0xFF >> (L & 7))) == 0, "getBytes phase %d len %d: spare bits not zero", phase, L);
+      // one bit more than there is: an error, nothing read outside
+      CHECK(rb.get(1) == 0 && rb.error, "get past the end, phase %d len %d", phase, L);
+      if (L > 0) {
+        HostBitsIn rs{a.get(), (uint64_t)(phase + L - 1), (uint64_t)phase, false};
+        Buf o2 = buf(sb, 0xFF);
+        rs.getBytes(o2.get(), (uint64_t)L);
+        CHECK(rs.error, "getBytes past the end, phase %d len %d", phase, L);
+      }
+      // cap one byte short: overflow, nothing written
+      if (L > 0 && total >= 1 && total - 1 >= (size_t)(phase + 7) / 8) {
+        const size_t cap = total - 1;
+        Buf c = buf(cap, 0xFF), ref = buf(cap, 0xFF);
+        HostBits wc{c.get(), (int64_t)cap, 0, false}, wr{ref.get(), (int64_t)cap, 0, false};
+        for (int i = 0; i < phase; i++) { wc.put((uint64_t)(i & 1), 1); wr.put((uint64_t)(i & 1), 1); }
+        wc.putBytes(src.get(), (uint64_t)L);
+        CHECK(wc.overflow && wc.pos == (uint64_t)phase && (cap == 0 || memcmp(c.get(), ref.get(), cap) == 0), "putBytes into a short buffer, phase %d len %d", phase, L);
+        wr.put(0, L > 64 ? 64 : L);
+        if (L <= 64) CHECK(wr.overflow && wr.pos == (uint64_t)phase && (cap == 0 || memcmp(c.get(), ref.get(), cap) == 0), "put into a short buffer, phase %d len %d", phase, L);
+      }
+    }
+}
+
+// ---- stream header: round trip, and every truncation an error ----
+static void check_stream_header() {
+  const int64_t ns[] = {0, 1, 65535, 65536, 1LL << 30, (1LL << 30) + 1, (1LL << 32) - 1, 1LL << 32, (1LL << 48) - 1, 1LL << 48};
+  const uint64_t tt = (2ULL << 42) | (3ULL << 36);
+  for (int64_t n : ns)
+    for (int chk = 0; chk <= 2; chk++)
+      for (int32_t bsz : {1024, 1 << 30}) {
+        Buf probe = buf(32);
+        HostBits p{probe.get(), 32, 0, false};
+        const int szMask = write_stream_header(p, tt, 1, bsz, n, chk);
+        CHECK(!p.overflow && (p.pos & 7) == 0 && p.pos == (uint64_t)(160 + 16 * szMask), "header of n %lld: %llu bits", (long long)n, (unsigned long long)p.pos);
+        const size_t len = (size_t)(p.pos >> 3);
+        Buf h = buf(len);
+        HostBits w{h.get(), (int64_t)len, 0, false};
+        write_stream_header(w, tt, 1, bsz, n, chk);
+        CHECK(!w.overflow && w.pos == p.pos, "header into its exact size");
+        HostBitsIn in{h.get(), (uint64_t)len * 8, 0, false};
+        KnzHeader k;
+        const int rc = read_stream_header(in, k, nullptr, 0);
+        const int64_t wantSize = (n != 0 && n < (1LL << 48)) ? n : 0;
+        CHECK(rc == 0 && in.pos == p.pos && k.chkKind == chk && k.entropyType == 1 && k.transformType == tt && k.blockSize == bsz && k.szMask == szMask && k.inputSize == wantSize,
+              "header round trip n %lld chk %d bs %d: rc %d size %lld", (long long)n, chk, bsz, rc, (long long)k.inputSize);
+        for (size_t t = 0; t < len; t++) {
+          Buf cut = buf(t);
+          if (t) memcpy(cut.get(), h.get(), t);
+          HostBitsIn ci{cut.get(), (uint64_t)t * 8, 0, false};
+          KnzHeader kc;
+          CHECK(read_stream_header(ci, kc, nullptr, 0) < 0, "header of %zu bytes cut to %zu reads as whole", len, t);
+        }
+        // a short destination: overflow, nothing outside
+        if (len > 0) { Buf s = buf(len - 1); HostBits ws{s.get(), (int64_t)len - 1, 0, false}; write_stream_header(ws, tt, 1, bsz, n, chk); CHECK(ws.overflow, "header into a short buffer"); }
+      }
+  char err[128] = {0};
+  Buf v = buf(5, 0);
+  HostBits w{v.get(), 5, 0, false};
+  w.put(0x4B414E5A, 32); w.put(6, 4);
+  HostBitsIn in{v.get(), 40, 0, false};
+  KnzHeader k;
+  CHECK(read_stream_header(in, k, err, sizeof(err)) == -KZ_ERR_STREAM_VERSION && err[0], "version 6");
+}
+
+// ---- knz_check_entry: the true entries of a stream, and their neighbours ----
+static void check_entries() {
+  const uint64_t Ws[] = {9, 64, 100, 1000, 7, 4096 + 3};
+  const int nb = (int)(sizeof(Ws) / sizeof(Ws[0]));
+  const size_t cap = 4096;
+  Buf tmp = buf(cap);
+  HostBits w{tmp.get(), (int64_t)cap, 0, false};
+  write_stream_header(w, 2ULL << 42, 0, 65536, 12345, 0);
+  const int64_t hdrEnd = (int64_t)w.pos;
+  int64_t off[8];
+  for (int i = 0; i < nb; i++) {
+    const size_t pb = (size_t)(Ws[i] + 7) / 8;
+    Buf pay = buf(pb);
+    for (size_t j = 0; j < pb; j++) pay[j] = (uint8_t)rnd();
+    off[i] = (int64_t)w.pos + 5 + knz_prefix_width(Ws[i]);
+    write_block(w, pay.get(), Ws[i]);
+    CHECK((int64_t)w.pos == off[i] + (int64_t)Ws[i], "write_block %d", i);
+  }
+  write_end_marker(w);
+  CHECK(!w.overflow, "stream of the entry check");
+  const int64_t n = (int64_t)((w.pos + 7) >> 3), nbits = n * 8;
+  Buf s = buf((size_t)n);
+  memcpy(s.get(), tmp.get(), (size_t)n);
+  // the chain of prefixes gives the same entries
+  HostBitsIn in{s.get(), (uint64_t)nbits, (uint64_t)hdrEnd, false};
+  for (int i = 0; i < nb; i++) {
+    uint64_t rd = 0;
+    CHECK(knz_read_prefix(in, rd) == 0 && rd == Ws[i] && (int64_t)in.pos == off[i], "prefix %d on the chain", i);
+    in.pos += rd;
+  }
+  uint64_t rd = 1;
+  CHECK(knz_read_prefix(in, rd) == KNZ_PREFIX_END, "end of the chain");
+  for (int i = 0; i < nb; i++) {
+    const int64_t o = off[i], W = (int64_t)Ws[i];
+    CHECK(knz_check_entry(s.get(), n, hdrEnd, o, W), "true entry %d refused", i);
+    CHECK(!knz_check_entry(s.get(), n, hdrEnd, o - 1, W), "entry %d at off - 1", i);
+    CHECK(!knz_check_entry(s.get(), n, hdrEnd, o + 1, W), "entry %d at off + 1", i);
+    CHECK(!knz_check_entry(s.get(), n, hdrEnd, o, W - 1), "entry %d with W - 1", i);
+    CHECK(!knz_check_entry(s.get(), n, hdrEnd, o, W + 1), "entry %d with W + 1", i);
+    CHECK(!knz_check_entry(s.get(), n, hdrEnd, hdrEnd, W), "entry %d at hdrEnd", i);
+    CHECK(!knz_check_entry(s.get(), n, hdrEnd, nbits, W), "entry %d at nbits", i);
+    CHECK(!knz_check_entry(s.get(), n, hdrEnd, o, 0), "entry %d with W = 0", i);
+    CHECK(!knz_check_entry(s.get(), n, hdrEnd, o, 1LL << 34), "entry %d with W = 2^34", i);
+  }
+}
+
+// ---- precheck_block_header and knz_check_block: whole and truncated block headers ----
+static void check_block_header() {
+  const int blockSize = 1024;
+  for (int nbFunctions : {1, 5})
+    for (int hi : {0, 0x80})
+      for (int sk : {0, 0x10})
+        for (int dataSize = 1; dataSize <= 4; dataSize++)
+          for (int chk = 0; chk <= 2; chk++) {
+            const uint32_t mode = (uint32_t)(hi | sk | ((dataSize - 1) << 5) | 0x05);
+            const bool hasSkip = hi ? (sk && nbFunctions > 4) : sk != 0;
+            const uint32_t skipFlags = hasSkip ? 0x3Cu : ((hi && !sk) ? 0u : (((mode << 4) | 0x0F) & 0xFF));   // (0x80 alone: no transform is skipped)
+            const uint32_t preLen = dataSize == 1 ? 200 : 1000;
+            const int headerSize = 1 + (hasSkip ? 1 : 0) + dataSize + 1;
+            const uint64_t W = (uint64_t)(preLen + headerSize + (chk == 2 ? 8 : chk == 1 ? 4 : 0)) * 8;
+            const uint32_t HASH = 0x1E35A7BDu;
+            uint32_t c = HASH * 0x01030507u;
+            c = mix32(c, HASH, mode); c = mix32(c, HASH, skipFlags); c = mix32(c, HASH, preLen);
+            c = mix32(c, HASH, (uint32_t)(W >> 32)); c = mix32(c, HASH, (uint32_t)W);
+            c = (c >> 23) ^ (c >> 3);
+            Buf h = buf((size_t)headerSize);
+            HostBits w{h.get(), headerSize, 0, false};
+            w.put(mode, 8);
+            if (hasSkip) w.put(skipFlags, 8);
+            w.put(preLen, 8 * dataSize);
+            w.put(c & 0xFF, 8);
+            CHECK(!w.overflow && w.pos == (uint64_t)headerSize * 8, "block header built");
+            const HostBitsIn whole{h.get(), (uint64_t)headerSize * 8, 0, false};
+            CHECK(precheck_block_header(whole, W, nbFunctions, blockSize, chk) == 0, "whole block header, mode %02x nbf %d chk %d", mode, nbFunctions, chk);
+            {
+              Buf bad = buf((size_t)headerSize);
+              memcpy(bad.get(), h.get(), (size_t)headerSize);
+              bad[headerSize - 1] ^= 1;
+              const HostBitsIn bi{bad.get(), (uint64_t)headerSize * 8, 0, false};
+              CHECK(precheck_block_header(bi, W, nbFunctions, blockSize, chk) == -KZ_ERR_CRC_CHECK, "block header with another checksum byte, mode %02x", mode);
+            }
+            CHECK(precheck_block_header(whole, W + 8, nbFunctions, blockSize, chk) < 0, "block header under a longer W, mode %02x", mode);
+            CHECK(precheck_block_header(whole, 7, nbFunctions, blockSize, chk) == -KZ_ERR_BLOCK_SIZE, "W = 7");
+            for (int t = 1; t <= 2 && t < headerSize; t++) {
+              Buf cut = buf((size_t)t);
+              memcpy(cut.get(), h.get(), (size_t)t);
+              const HostBitsIn ci{cut.get(), (uint64_t)t * 8, 0, false};
+              CHECK(precheck_block_header(ci, W, nbFunctions, blockSize, chk) < 0, "block header cut to %d bytes, mode %02x", t, mode);
+            }
+            // the three checks of a reader, in their order
+            KnzPlan P;
+            memset(&P, 0, sizeof(P));
+            P.h.blockSize = blockSize; P.h.chkKind = chk; P.nbFunctions = nbFunctions; P.iS = knz_dec_row_stride(blockSize);
+            CHECK(knz_check_block(whole, W, 1000, 1000 + W, P) == 0, "knz_check_block, block that ends with the stream");
+            CHECK(knz_check_block(whole, W, 1000, 1000 + W - 1, P) == -KZ_ERR_READ_FILE, "knz_check_block, payload past the stream");
+            CHECK(knz_check_block(whole, W, 1000, 1000 + W - 1, P, false) == 0, "knz_check_block without the end check");
+            P.iS = (int64_t)(W >> 3) + 63;
+            CHECK(knz_check_block(whole, W, 1000, 1000 + W - 1, P) == -KZ_ERR_BLOCK_SIZE, "knz_check_block, staging row bound first");
+          }
+}
+
+// ---- the small rules ----
+static void check_rules() {
+  CHECK(knz_chk_kind(0) == 0 && knz_chk_kind(32) == 1 && knz_chk_kind(64) == 2 && knz_chk_kind(16) == -1 && knz_chk_kind(-32) == -1, "knz_chk_kind");
+  for (int k = 0; k <= 2; k++) CHECK(knz_chk_kind(knz_chk_bits(k)) == k, "knz_chk_bits %d", k);
+  CHECK(knz_block_size_ok(1024) && knz_block_size_ok(1 << 30) && !knz_block_size_ok(1008) && !knz_block_size_ok((1 << 30) + 16) && !knz_block_size_ok(1025) && !knz_block_size_ok(-16), "knz_block_size_ok");
+  CHECK(knz_nb_functions(0) == 1 && knz_nb_functions(2ULL << 42) == 1 && knz_nb_functions((2ULL << 42) | 1) == 2 && knz_nb_functions(0x0000FFFFFFFFFFFFULL) == 8, "knz_nb_functions");
+  for (int32_t b : {1024, 1040, 65536, 1 << 22, 1 << 30}) {
+    const int64_t s = knz_dec_row_stride(b), need = (int64_t)b + (b >> 3) + 1024 + 64;
+    CHECK(s >= need && s < need + 256 && (s & 255) == 0, "knz_dec_row_stride %d", b);
+  }
+  CHECK(knz_fit_blocks(0, 1024) == 0 && knz_fit_blocks(-5, 1024) == 0 && knz_fit_blocks(1, 1024) == 1 && knz_fit_blocks(1024, 1024) == 1 && knz_fit_blocks(1025, 1024) == 2, "knz_fit_blocks");
+  kz_block_result r;
+  memset(&r, 0, sizeof(r));
+  r.length = 1024;
+  CHECK(knz_block_verdict(r, 1024, 10, 1034) == 0 && knz_block_verdict(r, 1024, 11, 1034) == -KZ_ERR_WRITE_FILE, "verdict: room");
+  r.length = 1025;
+  CHECK(knz_block_verdict(r, 1024, 0, 10) == -KZ_ERR_PROCESS_BLOCK, "verdict: length before room");
+  r.status = -KZ_ERR_CRC_CHECK;
+  CHECK(knz_block_verdict(r, 1024, 0, 10) == -KZ_ERR_CRC_CHECK, "verdict: status first");
+}
+
+int main() {
+  check_prefix_width();
+  check_bit_io();
+  check_stream_header();
+  check_entries();
+  check_block_header();
+  check_rules();
+  printf("knz_host_check ok: %ld checks\n", checked);
+  return 0;
+}
