@@ -420,6 +420,55 @@ int32_t kz_decode_indexed_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n,
                                  const int64_t* blockBitOff /* host */, const int64_t* blockBits /* host */, int32_t nBlocks,
                                  uint8_t* d_dst, int64_t dstStride, kz_block_result* results /* host */);
 
+/* ---- splice: a new .knz stream out of blocks of existing ones, without recoding -------------------
+ * Blocks are independent of one another, and a stream is its header, then per block 5 + lw prefix bits and W payload bits, then the
+ * end marker (:1024-1035, :483-493): a stream made of blocks taken from existing streams is a bit-granular copy.  One call joins the
+ * streams kz_compress_many_device (or N ranks) wrote, cuts a block range out as a stream of its own, or replaces or appends a block
+ * after only the new bytes were compressed.  No block is decoded.
+ *
+ * Source s is the .knz stream src[srcOff[s] .. srcOff[s] + srcLen[s]) (offsets relative to one base pointer, as in the many-stream
+ * calls).  Piece i is the block of source pieceSrc[i] whose payload is pieceBits[i] bits at bit pieceBitOff[i], counted from that
+ * source's first bit, exactly as kz_knz_index / kz_knz_index_device return it: any subset, in any order, with repeats, from any mix
+ * of sources.  The result is the stream header, each piece as a minimal-width prefix and its payload bits verbatim, the end
+ * marker, the spare bits of the last byte zero: byte for byte kz_knz_assemble(the sources' header parameters, the pieces' extracted
+ * bit strings, their W).  The transform word, entropy id, block size and checksum kind come from the sources' own headers, which
+ * must agree in all four (a source that no piece names is parsed and compared all the same); inputSize is the caller's, with the
+ * meaning kz_knz_assemble gives it (0: unknown).  nSrc >= 1; nPieces == 0 gives the header and end-marker stream.
+ * kz_knz_splice_bound returns a dstCap that suffices: the longest stream header, 5 + lw + W bits per piece, the end marker, in bytes.
+ *
+ * Nothing is trusted: before a bit is copied every piece is checked against ITS OWN source with the rule of the indexed reads
+ * (above; k_knz_check_many on the device), using that source's header end and length.  As there, the check gives memory safety and
+ * does not prove that a piece lies on the true chain of prefixes.
+ *
+ *   addresses   src / d_src and dst / d_dst: any address, any alignment; dst overlaps no source.  srcOff, srcLen, pieceSrc,
+ *               pieceBitOff and pieceBits are host arrays in both forms.  kz_knz_splice works on host memory and needs no context
+ *               and no GPU, like kz_knz_assemble.
+ *   read        nothing outside a source's own segment, not even a neighbour's bytes in the same buffer.
+ *   written     nothing outside dst[0 .. dstCap).  On success dst[0 .. size) is the stream, dst[size .. dstCap) is untouched by the
+ *               host form and unspecified for the device form; dst need not be zeroed.  On every refusal except -KZ_ERR_DEVICE
+ *               dst is untouched.
+ *   returns     the stream's size, or in this order: -KZ_ERR_INVALID_PARAM for bad arguments (null pointers, nSrc < 1, nPieces < 0,
+ *               a negative offset, length, inputSize or dstCap) or a pieceSrc[i] outside 0 .. nSrc; the first bad source header's
+ *               code as the reader of a stream header gives it, on the source's first min(26, srcLen[s]) bytes (kz_last_error:
+ *               "source %d: ..."); -KZ_ERR_INVALID_PARAM for sources that disagree
+ *               ("source %d differs from source 0 in ...") and for the first piece that fails its check ("piece %d does not match
+ *               its source"); -KZ_ERR_WRITE_FILE when dstCap is too small, decided from the bit arithmetic before anything is
+ *               written; -KZ_ERR_DEVICE (device form).  The host form has no context and returns the code alone.
+ *   chunks      the device form takes the pieces in chunks of kz_compress_device's size (KZ_STREAM_CHUNK=<blocks> overrides): per
+ *               chunk one launch checks the pieces and one copies them, whatever the chunk holds; a chunk's first bit is wherever
+ *               the previous chunk's last bit ended.  Payload bits go from the sources straight to their place in dst (k_knz_splice:
+ *               any byte misalignment, any of the 8 x 8 bit phases of the two sides); there are no staging rows.  Tables live in
+ *               the context's grow-only buffers; host memory proportional to nSrc and nPieces (8 bytes each) is used besides.
+ *   stream      the device call is synchronous and runs on the context's stream.
+ */
+int64_t kz_knz_splice_bound(const int64_t* pieceBits, int32_t nPieces);
+int64_t kz_knz_splice(const uint8_t* src, const int64_t* srcOff, const int64_t* srcLen, int32_t nSrc,
+                      const int32_t* pieceSrc, const int64_t* pieceBitOff, const int64_t* pieceBits, int32_t nPieces,
+                      int64_t inputSize, uint8_t* dst, int64_t dstCap);
+int64_t kz_knz_splice_device(kz_ctx* ctx, const uint8_t* d_src, const int64_t* srcOff /* host */, const int64_t* srcLen /* host */, int32_t nSrc,
+                             const int32_t* pieceSrc /* host */, const int64_t* pieceBitOff /* host */, const int64_t* pieceBits /* host */, int32_t nPieces,
+                             int64_t inputSize, uint8_t* d_dst, int64_t dstCap);
+
 /* ---- instrumentation (bench.py / roofline) ----------------------------------------------------- */
 /* blocks that went through a TEXT / UTF stage on a HOST thread since the last reset (process-wide counter; inverse = 0: forward,
  * 1: inverse).  The stage timers KZ_STAGE_HOST_FWD / _INV measure the TEXT / UTF stage's wall time INCLUDING its device forms

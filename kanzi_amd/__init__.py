@@ -121,6 +121,9 @@ def load_library():
         "kz_decompress_range_device": (c.c_int64, [vp, u8p, c.c_int64, c.c_int64, c.c_int64, u8p, c.c_int64]),
         "kz_decode_indexed": (c.c_int32, [vp, u8p, c.c_int64, i64p, i64p, c.c_int32, u8p, c.c_int64, vp]),
         "kz_decode_indexed_device": (c.c_int32, [vp, u8p, c.c_int64, i64p, i64p, c.c_int32, u8p, c.c_int64, vp]),
+        "kz_knz_splice_bound": (c.c_int64, [i64p, c.c_int32]),
+        "kz_knz_splice": (c.c_int64, [u8p, i64p, i64p, c.c_int32, i32p, i64p, i64p, c.c_int32, c.c_int64, u8p, c.c_int64]),
+        "kz_knz_splice_device": (c.c_int64, [vp, u8p, i64p, i64p, c.c_int32, i32p, i64p, i64p, c.c_int32, c.c_int64, u8p, c.c_int64]),
         "kz_set_timing": (None, [vp, c.c_int32]),
         "kz_get_stage_count": (c.c_int32, [vp]),
         "kz_get_stage_ms": (c.c_float, [vp, c.c_int32]),
@@ -151,6 +154,7 @@ ABI_SYMBOLS = ["kz_abi_version", "kz_ctx_create", "kz_ctx_destroy", "kz_last_err
                "kz_compress_device", "kz_decompress_device", "kz_knz_assemble_device", "kz_knz_index_device",
                "kz_compress_many_bound", "kz_compress_many_device", "kz_decompress_many_device",
                "kz_decompress_range", "kz_decompress_range_device", "kz_decode_indexed", "kz_decode_indexed_device",
+               "kz_knz_splice_bound", "kz_knz_splice", "kz_knz_splice_device",
                "kz_set_timing", "kz_get_stage_count", "kz_get_stage_ms", "kz_get_stage_alg_bytes", "kz_reset_timing",
                "kz_set_kernel_timing", "kz_get_kernel_count", "kz_get_kernel_name", "kz_get_kernel_ms", "kz_get_kernel_max_ms",
                "kz_get_kernel_launches", "kz_reset_kernel_timing"]
@@ -1113,6 +1117,118 @@ class KnzReader:
         if self.device:
             return flat[lo:max(hi, lo)].clone()
         return flat[lo:max(hi, lo)].tobytes()
+
+
+# ---- splice: a new .knz stream out of blocks of existing ones, without recoding (kz_knz_splice / kz_knz_splice_device) ----
+def knz_splice_bound(bits):
+    """kz_knz_splice_bound: a capacity that suffices for a splice of pieces of `bits` bits each."""
+    b = np.ascontiguousarray(bits, dtype=np.int64)
+    rc = int(load_library().kz_knz_splice_bound(b.ctypes.data if len(b) else None, len(b)))
+    if rc < 0:
+        raise KanziError(-rc, "knz_splice_bound")
+    return rc
+
+
+def _piece_arrays(pieces):
+    ps = np.ascontiguousarray([p[0] for p in pieces], dtype=np.int32)
+    po = np.ascontiguousarray([p[1] for p in pieces], dtype=np.int64)
+    pw = np.ascontiguousarray([p[2] for p in pieces], dtype=np.int64)
+    return ps, po, pw
+
+
+def _arg(a):
+    return a.ctypes.data if len(a) else None
+
+
+def knz_splice(sources, pieces, input_size, cap=None):
+    """kz_knz_splice (host memory, no GPU): the stream made of `pieces` = [(source, bitOff, bits)], blocks of the .knz streams in
+    `sources` (a list of bytes) named as knz_index names them, in this order; the header parameters are the sources' own, which must
+    agree, and `input_size` goes into the header's size field (0: unknown) -> the stream's bytes.  Blocks are not decoded."""
+    L = load_library()
+    sources = [bytes(s) for s in sources]
+    ps, po, pw = _piece_arrays(pieces)
+    so = np.zeros(len(sources), dtype=np.int64)
+    sl = np.ascontiguousarray([len(s) for s in sources], dtype=np.int64)
+    if len(sources) > 1:
+        so[1:] = np.cumsum(sl)[:-1]
+    src = np.frombuffer(b"".join(sources) + b"\0", dtype=np.uint8)
+    if cap is None:
+        cap = knz_splice_bound(np.clip(pw, 0, (1 << 34) - 1))
+    dst = np.zeros(max(int(cap), 1), dtype=np.uint8)
+    rc = L.kz_knz_splice(src.ctypes.data, _arg(so), _arg(sl), len(sources), _arg(ps), _arg(po), _arg(pw), len(ps), int(input_size), dst.ctypes.data, int(cap))
+    if rc < 0:
+        raise KanziError(-rc, "knz_splice")
+    return dst[:rc].tobytes()
+
+
+def knz_splice_device(ctx, src, src_off, src_len, pieces, input_size, dst, cap):
+    """kz_knz_splice_device: the same with source s the src_len[s] bytes at device address src + src_off[s] and the result written at
+    device address `dst` (capacity `cap`; knz_splice_bound of the pieces' bits suffices) -> the stream's size.  The payload bits go
+    from the sources to their place in `dst` in one kernel per chunk of pieces; nothing is staged or recoded."""
+    ps, po, pw = _piece_arrays(pieces)
+    so = np.ascontiguousarray(src_off, dtype=np.int64)
+    sl = np.ascontiguousarray(src_len, dtype=np.int64)
+    if len(so) != len(sl):
+        raise ValueError("src_off and src_len differ in length")
+    rc = ctx.lib.kz_knz_splice_device(ctx.h, _ptr(src), _arg(so), _arg(sl), len(so), _arg(ps), _arg(po), _arg(pw), len(ps), int(input_size), _ptr(dst), int(cap))
+    return int(ctx.check(rc))
+
+
+def _decoded_size(index):
+    """(size, known) of an indexed stream under the planners' rule: every block decodes to blockSize bytes except the stream's
+    last, whose length is what the header's size field leaves; known is False when the header carries no size or one that does not
+    fit that rule"""
+    nb, bs, n = len(index["blocks"]), index["blockSize"], index["inputSize"]
+    if nb == 0:
+        return 0, n == 0
+    return n, (nb - 1) * bs < n <= nb * bs
+
+
+def splice_concat(indices):
+    """Plan of the join of whole streams: indices[s] = knz_index of source s -> (pieces, input_size) for knz_splice /
+    knz_splice_device.  input_size is the sum of the sources' header sizes.  The result is the stream the compressor writes for the
+    joined data only if every source but the last holds whole blocks; otherwise it still decodes to the joined data, with short
+    blocks in the middle.  Sizes are taken as "every block blockSize except a stream's last", which holds for the streams
+    kz_compress* wrote and not for ones with short middle blocks or without a size in their header: then input_size is 0 (unknown)."""
+    pieces, total, known = [], 0, True
+    for s, idx in enumerate(indices):
+        pieces += [(s, off, w) for off, w in idx["blocks"]]
+        n, k = _decoded_size(idx)
+        total, known = total + n, known and k
+    return pieces, (total if known else 0)
+
+
+def splice_slice(index, first, count):
+    """Plan of blocks [first, first + count) of one stream as a stream of its own -> (pieces, input_size); the same rule for sizes as
+    splice_concat, 0 (unknown) where it does not hold."""
+    nb, bs = len(index["blocks"]), index["blockSize"]
+    first = max(int(first), 0)
+    last = min(first + max(int(count), 0), nb)
+    pieces = [(0, off, w) for off, w in index["blocks"][first:last]]
+    n, known = _decoded_size(index)
+    if not known:
+        return pieces, 0
+    return pieces, max(min(last * bs, n) - first * bs, 0)
+
+
+def splice_replace(index, k, other_source, other_index):
+    """Plan of source 0 (index) with its block k replaced by all blocks of source `other_source` (other_index: its knz_index, as a
+    rule one freshly compressed block); k == number of blocks appends -> (pieces, input_size); the same rule for sizes as
+    splice_concat, 0 (unknown) where it does not hold, for instance when a short block comes to lie in the middle."""
+    blocks, bs = index["blocks"], index["blockSize"]
+    k = int(k)
+    if not 0 <= k <= len(blocks):
+        raise IndexError("block %d of %d" % (k, len(blocks)))
+    new = [(int(other_source), off, w) for off, w in other_index["blocks"]]
+    pieces = [(0, off, w) for off, w in blocks[:k]] + new + [(0, off, w) for off, w in blocks[k + 1:]]
+    n, known = _decoded_size(index)
+    m, mknown = _decoded_size(other_index)
+    lens = [min(bs, n - i * bs) for i in range(len(blocks))]
+    olens = [min(bs, m - i * bs) for i in range(len(other_index["blocks"]))]
+    out = lens[:k] + olens + lens[k + 1:]
+    if not (known and mknown) or any(l != bs for l in out[:-1]):
+        return pieces, 0
+    return pieces, sum(out)
 
 
 def usable_cpus():

@@ -48,7 +48,8 @@
   X(KID_EXE_HIST, "k_exe_hist") X(KID_EXE_DECIDE, "k_exe_decide") X(KID_EXE_SIZE, "k_exe_size") X(KID_EXE_VERDICT, "k_exe_verdict") \
   X(KID_EXE_EMIT, "k_exe_emit") X(KID_KNZ_PACK, "k_knz_pack") X(KID_KNZ_WALK, "k_knz_walk") X(KID_KNZ_UNPACK, "k_knz_unpack") \
   X(KID_KNZ_CHECK, "k_knz_check") X(KID_KNZ_GATHER, "k_knz_gather") X(KID_KNZ_PACK_MANY, "k_knz_pack_many") X(KID_KNZ_HEADS, "k_knz_heads") \
-  X(KID_KNZ_WALK_MANY, "k_knz_walk_many") X(KID_KNZ_UNPACK_MANY, "k_knz_unpack_many") X(KID_KNZ_SCATTER, "k_knz_scatter")
+  X(KID_KNZ_WALK_MANY, "k_knz_walk_many") X(KID_KNZ_UNPACK_MANY, "k_knz_unpack_many") X(KID_KNZ_SCATTER, "k_knz_scatter") \
+  X(KID_KNZ_CHECK_MANY, "k_knz_check_many") X(KID_KNZ_SPLICE, "k_knz_splice")
 #define KZ_KERNEL_ENUM(id, name) id,
 #define KZ_KERNEL_NAME(id, name) name,
 enum KzKernelId { KZ_KERNELS(KZ_KERNEL_ENUM) KID_COUNT };
@@ -330,6 +331,11 @@ int kz_knz_pack_many(kz_ctx*, const uint8_t* d_rows, const KnzSeg* d_seg, int ns
 int kz_knz_heads(kz_ctx*, const uint8_t* d_src, const KnzSrc* d_t, int ns, uint8_t* d_heads);
 int kz_knz_walk_many(kz_ctx*, const uint8_t* d_src, const KnzSrc* d_t, int ns, int64_t* d_off, int64_t* d_bits, uint64_t* d_hdr, int64_t* d_res);
 int kz_knz_unpack_many(kz_ctx*, const uint8_t* d_src, const KnzRow* d_t, int nr, int64_t maxBytes, uint8_t* d_rows);
+// splice (kz_knz_splice_device): a piece is the `bits` bits from bit `off` of the stream src[seg .. seg + n), whose header ends at bit
+// hdrEnd; `pay` = the bit offset of its payload in dst (the check does not read it)
+struct KnzPiece { int64_t pay, bits, seg, n, off, hdrEnd; };
+int kz_knz_check_many(kz_ctx*, const uint8_t* d_src, const KnzPiece* d_pc, int np, int32_t* d_bad);
+int kz_knz_splice_launch(kz_ctx*, const uint8_t* d_src, const KnzPiece* d_pc, int np, uint8_t* d_dst, int64_t startBit, int64_t endBit);
 
 // timing helpers
 void kz_stage_begin(kz_ctx*, hipEvent_t* e0);

@@ -2,7 +2,9 @@
 // (K/io/CompressedOutputStream.java:1024-1035) as a copy kernel, its inverse, and the serial walk of the block length
 // prefixes (K/io/CompressedInputStream.java:1127-1129), and the check of a caller's index entries that stands in for the walk in
 // the indexed reads; behind them the same steps for many streams in one launch (a table entry per segment, slot or row, each with
-// its own bounds: kz_compress_many_device / kz_decompress_many_device).  The callers (kz_compress_device / kz_decompress_device / kz_decompress_range_device /
+// its own bounds: kz_compress_many_device / kz_decompress_many_device), and the splice: the pack over pieces whose payload bits lie
+// where they are in their source streams, with the check of every piece against its own source in front of it (kz_knz_splice_device).
+// The callers (kz_compress_device / kz_decompress_device / kz_decompress_range_device /
 // kz_decode_indexed_device / kz_knz_assemble_device / kz_knz_index_device, kz_stream_device.hip) do the bit-offset arithmetic, the stream
 // header and the block-header prechecks on the host; no payload byte leaves the device.
 #include "kz_device.h"
@@ -31,9 +33,14 @@ __device__ __forceinline__ uint4 knz_load128(const u8* p, int sh) {
 }
 __device__ __forceinline__ int knz_lw(int64_t W) { return W < 8 ? 3 : kz_ilog2((u32)(W >> 3)) + 4; }   // the device form of knz_prefix_width (kz_knz_host.h)
 
-// ---- the pack's steps, shared by k_knz_pack and k_knz_pack_many ----
+// ---- the pack's steps, shared by k_knz_pack, k_knz_pack_many and k_knz_splice ----
+// Where a field's payload bits lie: bit k of the payload is bit bit0 + k of base[0 .. lim), and base[0 .. lim) is all that may be
+// read for it.  A packed block's are the bytes of its row's W bits, a spliced piece's lie anywhere in its source's own segment.
+struct KnzPay { const u8* base; int64_t bit0, lim; };
+__device__ __forceinline__ KnzPay knz_payload(const u8* __restrict__ rows, const KnzBlk& b) { return KnzPay{rows + b.src, 0, (b.bits + 7) >> 3}; }
+__device__ __forceinline__ KnzPay knz_payload(const u8* __restrict__ src, const KnzPiece& b) { return KnzPay{src + b.seg, b.off, b.n}; }
 // the last block whose prefix starts at or before pos0 (prefix starts grow with i)
-__device__ __forceinline__ int knz_find_field(const KnzBlk* __restrict__ blk, int nb, int64_t pos0) {
+template <class T> __device__ __forceinline__ int knz_find_field(const T* __restrict__ blk, int nb, int64_t pos0) {
   int a = 0, b = nb;                                                                // invariant: prefix start of blocks < a is <= pos0
   while (a < b) {
     const int m = (a + b) >> 1;
@@ -42,23 +49,36 @@ __device__ __forceinline__ int knz_find_field(const KnzBlk* __restrict__ blk, in
   }
   return a > 0 ? a - 1 : 0;
 }
+// the same among the blocks lo .. hi, for a pos0 whose answer is known to lie there
+template <class T> __device__ __forceinline__ int knz_find_between(const T* __restrict__ blk, int lo, int hi, int64_t pos0) {
+  int a = lo + 1, b = hi + 1;                                                       // invariant: prefix start of block a - 1 is <= pos0
+  while (a < b) {
+    const int m = (a + b) >> 1;
+    if (blk[m].pay - 5 - knz_lw(blk[m].bits) <= pos0) a = m + 1; else b = m;
+  }
+  return a - 1;
+}
+__device__ __forceinline__ int64_t knz_first_lane(int64_t v) {                      // v of the wave's first active lane, wave-uniform
+  return (int64_t)(((u64)(u32)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)v));
+}
 // the 16 bytes [pos0, hiBit) of the destination when they lie inside the payload of block j alone: wide load, wide store at `out`.
-// From the row only aligned words inside the bytes of its W bits are read; false, nothing stored, when the unit is not of that kind.
-__device__ __forceinline__ bool knz_wide_unit(const u8* __restrict__ rows, const KnzBlk* __restrict__ blk, int nb, int j, int64_t pos0, int64_t hiBit, u8* out) {
+// From the row only aligned words inside the bytes of its W bits are read (of a piece: inside its source's segment); false, nothing
+// stored, when the unit is not of that kind.
+template <class T> __device__ __forceinline__ bool knz_wide_unit(const u8* __restrict__ rows, const T* __restrict__ blk, int nb, int j, int64_t pos0, int64_t hiBit, u8* out) {
   if (j >= nb) return false;
   const int64_t pay = blk[j].pay, W = blk[j].bits;
   if (pos0 < pay || hiBit > pay + W) return false;
-  const int64_t k = pos0 - pay;
-  const u8* row = rows + blk[j].src;
-  const u8* p = row + (k >> 3);
+  const KnzPay y = knz_payload(rows, blk[j]);
+  const int64_t k = y.bit0 + (pos0 - pay);
+  const u8* p = y.base + (k >> 3);
   const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
-  if (al < row || al + knz_window(p, (int)(k & 7)) > row + ((W + 7) >> 3)) return false;
+  if (al < y.base || al + knz_window(p, (int)(k & 7)) > y.base + y.lim) return false;
   *(uint4*)out = knz_load128(p, (int)(k & 7));
   return true;
 }
 // the byte that ends at bit bend, composed from bit pos on (acc: the bits in front of pos, already in place) out of whatever fields
-// it holds; j moves to the last field looked at.  From a row only the bytes of its W bits are read.
-__device__ __forceinline__ u8 knz_compose_byte(const u8* __restrict__ rows, const KnzBlk* __restrict__ blk, int nb, int& j, int64_t pos, int64_t bend, u32 acc) {
+// it holds; j moves to the last field looked at.  Of a payload only the bytes that hold its W bits are read.
+template <class T> __device__ __forceinline__ u8 knz_compose_byte(const u8* __restrict__ rows, const T* __restrict__ blk, int nb, int& j, int64_t pos, int64_t bend, u32 acc) {
   while (pos < bend) {
     while (j < nb && pos >= blk[j].pay + blk[j].bits) j++;
     if (j >= nb) break;                                                             // behind the last field: zeros
@@ -72,10 +92,11 @@ __device__ __forceinline__ u8 knz_compose_byte(const u8* __restrict__ rows, cons
       take = (int)(pay - pos) < room ? (int)(pay - pos) : room;
       v = (u32)(field >> (pw - k - take)) & ((1u << take) - 1);
     } else {
-      const int64_t k = pos - pay;
-      const int so = (int)(k & 7);
+      const KnzPay y = knz_payload(rows, blk[j]);
+      const int64_t k = pos - pay, sk = y.bit0 + k;
+      const int so = (int)(sk & 7);
       take = (W - k) < room ? (int)(W - k) : room;
-      const u8* s = rows + blk[j].src + (k >> 3);
+      const u8* s = y.base + (sk >> 3);
       const u32 two = ((u32)s[0] << 8) | (so + take > 8 ? (u32)s[1] : 0u);
       v = (two >> (16 - so - take)) & ((1u << take) - 1);
     }
@@ -109,6 +130,40 @@ __global__ void __launch_bounds__(256) k_knz_pack(const u8* __restrict__ rows, c
       const int64_t bend = (b + 1) << 3;
       const u32 acc = (pos & 7) ? dst[b] & (0xFFu << (8 - (int)(pos & 7))) : 0u;    // only the launch's first byte: see above
       dst[b] = knz_compose_byte(rows, blk, nb, j, pos, bend, acc);
+      pos = bend;
+    }
+  }
+}
+
+// ---- splice: blocks of existing streams -> container, bit to bit ----------------------------------------------------------------
+// k_knz_pack's launch over pieces whose payloads lie where they are in their sources: piece i is the pc[i].bits bits from bit
+// pc[i].off of the stream src[pc[i].seg .. + pc[i].n), at any of the 8 x 8 bit phases of the two sides.  No staging rows: a payload
+// bit is loaded once, from its source, and stored once.  A unit wholly inside one payload is one wide store of aligned 32-bit loads
+// that stay inside the piece's own source segment; units with a prefix or a payload's end in them, and those whose load window
+// would leave the segment, are composed bytewise.  The first byte's high bits are kept as in k_knz_pack.  The caller has checked
+// every piece (k_knz_check_many): [off, off + bits) lies inside its segment.
+// The field search is what a lane of the pack waits for longest (a dozen dependent loads from the table), and the 64 units of a wave
+// lie side by side: the wave searches once for its first and once for its last unit, with wave-uniform arguments, and a lane then
+// only among the pieces between the two, as a rule one or two.
+__global__ void __launch_bounds__(256) k_knz_splice(const u8* __restrict__ src, const KnzPiece* __restrict__ pc, int np, u8* dst, int64_t startBit, int64_t endBit) {
+  const int64_t firstByte = startBit >> 3, lastByte = (endBit + 7) >> 3;           // [firstByte, lastByte) is written
+  const uintptr_t A0 = (uintptr_t)(dst + firstByte) & ~(uintptr_t)15;
+  const int64_t units = (int64_t)(((uintptr_t)(dst + lastByte) - A0 + 15) >> 4);
+  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t ub = (int64_t)(A0 - (uintptr_t)dst) + (u << 4);                   // the unit's first byte as an index into dst (may be < firstByte)
+    const int64_t lo = ub < firstByte ? firstByte : ub, hi = ub + 16 > lastByte ? lastByte : ub + 16;
+    if (lo >= hi) continue;
+    const int64_t pos0 = (lo == firstByte) ? startBit : (lo << 3);
+    const int64_t ub0 = knz_first_lane(ub);                                         // the wave's units: 64 in a row from its first lane's
+    const int jlo = knz_find_field(pc, np, ub0 < firstByte ? startBit : (ub0 << 3));
+    const int jhi = knz_find_field(pc, np, (ub0 + 63 * 16) << 3);
+    int j = knz_find_between(pc, jlo, jhi, pos0);
+    if (hi - lo == 16 && knz_wide_unit(src, pc, np, j, pos0, hi << 3, dst + lo)) continue;
+    int64_t pos = pos0;
+    for (int64_t b = lo; b < hi; b++) {
+      const int64_t bend = (b + 1) << 3;
+      const u32 acc = (pos & 7) ? dst[b] & (0xFFu << (8 - (int)(pos & 7))) : 0u;    // only the launch's first byte
+      dst[b] = knz_compose_byte(src, pc, np, j, pos, bend, acc);
       pos = bend;
     }
   }
@@ -165,25 +220,31 @@ __global__ void k_knz_walk(const u8* __restrict__ src, int64_t n, int64_t startB
 // left aligned, as the walk gives them (0 for a bad entry).  That makes k_knz_unpack and the decoders safe on the entry; it does
 // not prove that the entry lies on the chain of prefixes from hdrEnd.  Nothing outside src[0 .. n) is read: hdrEnd >= 160, so the
 // 39 bits in front of a good off start inside src, and knz_peek64 reads bytes at and behind src[n] as zero.
+__device__ __forceinline__ bool knz_entry_ok(const u8* __restrict__ src, int64_t n, int64_t hdrEnd, int64_t o, int64_t W) {
+  const int64_t nbits = n << 3;
+  if (!(W > 0 && W < (1ll << 34) && o >= hdrEnd + 8 && o >= 39 && o <= nbits && W <= nbits - o)) return false;
+  const u64 x = knz_peek64(src, n, o - 39) >> 25;                                     // the 39 bits in front of o
+  for (int lr = 64 - __clzll((long long)W) < 3 ? 3 : 64 - __clzll((long long)W); lr <= 34; lr++) {
+    if (o - 5 - lr < hdrEnd) break;
+    const u64 f = x & ((1ull << (5 + lr)) - 1);
+    if ((int)(f >> lr) + 3 == lr && (int64_t)(f & ((1ull << lr) - 1)) == W) return true;
+  }
+  return false;
+}
 __global__ void __launch_bounds__(256) k_knz_check(const u8* __restrict__ src, int64_t n, int64_t hdrEnd, const int64_t* __restrict__ off,
                                                    const int64_t* __restrict__ bits, int nb, u64* __restrict__ hdr, int64_t* __restrict__ bad) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nb) return;
-  const int64_t nbits = n << 3, W = bits[i], o = off[i];
-  bool ok = W > 0 && W < (1ll << 34) && o >= hdrEnd + 8 && o >= 39 && o <= nbits && W <= nbits - o;
-  u64 h = 0;
-  if (ok) {
-    const u64 x = knz_peek64(src, n, o - 39) >> 25;                                   // the 39 bits in front of o
-    ok = false;
-    for (int lr = 64 - __clzll((long long)W) < 3 ? 3 : 64 - __clzll((long long)W); lr <= 34; lr++) {
-      if (o - 5 - lr < hdrEnd) break;
-      const u64 f = x & ((1ull << (5 + lr)) - 1);
-      if ((int)(f >> lr) + 3 == lr && (int64_t)(f & ((1ull << lr) - 1)) == W) { ok = true; break; }
-    }
-    if (ok) h = knz_peek64(src, n, o);
-  }
-  hdr[i] = h;
+  const bool ok = knz_entry_ok(src, n, hdrEnd, off[i], bits[i]);
+  hdr[i] = ok ? knz_peek64(src, n, off[i]) : 0;
   bad[i] = ok ? 0 : 1;
+}
+// the same rule for the pieces of a splice, each against its own source: the stream src[pc[i].seg .. + pc[i].n), whose header ends at
+// bit pc[i].hdrEnd.  bad[i] = 0 / 1.  Nothing outside that segment is read, not even a neighbour's bytes in the same buffer.
+__global__ void __launch_bounds__(256) k_knz_check_many(const u8* __restrict__ src, const KnzPiece* __restrict__ pc, int np, int32_t* __restrict__ bad) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= np) return;
+  bad[i] = knz_entry_ok(src + pc[i].seg, pc[i].n, pc[i].hdrEnd, pc[i].off, pc[i].bits) ? 0 : 1;
 }
 
 // ---- unpack: container -> byte-aligned rows ------------------------------------------------------------------------------------
@@ -366,6 +427,20 @@ int kz_knz_check(kz_ctx* ctx, const uint8_t* d_src, int64_t n, int64_t hdrEnd, c
 int kz_knz_unpack(kz_ctx* ctx, const uint8_t* d_src, int64_t n, const int64_t* d_off, const int64_t* d_bits, int nb, int64_t maxBytes, uint8_t* d_rows, int64_t stride) {
   if (nb <= 0) return 0;
   KZ_LAUNCH(ctx, KID_KNZ_UNPACK, k_knz_unpack, knz_unpack_grid(nb, maxBytes), dim3(256), d_src, n, d_off, d_bits, nb, d_rows, stride);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+
+int kz_knz_check_many(kz_ctx* ctx, const uint8_t* d_src, const KnzPiece* d_pc, int np, int32_t* d_bad) {
+  if (np <= 0) return 0;
+  KZ_LAUNCH(ctx, KID_KNZ_CHECK_MANY, k_knz_check_many, dim3((np + 255) / 256), dim3(256), d_src, d_pc, np, d_bad);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_splice_launch(kz_ctx* ctx, const uint8_t* d_src, const KnzPiece* d_pc, int np, uint8_t* d_dst, int64_t startBit, int64_t endBit) {
+  if (endBit <= startBit) return 0;
+  const int64_t units = (((endBit + 7) >> 3) - (startBit >> 3) + 15 + 15) >> 4;
+  KZ_LAUNCH(ctx, KID_KNZ_SPLICE, k_knz_splice, knz_pack_grid(units), dim3(256), d_src, d_pc, np, d_dst, startBit, endBit);
   KZ_HIP(hipGetLastError());
   return 0;
 }

@@ -1,5 +1,6 @@
 // kz_knz_host.h -- the host-only core of the .knz container: bit I/O, the stream header, the chain of block length prefixes, the
-// block-header precheck and the check of an index entry, and the container's rules that every call must share, each written once.
+// block-header precheck and the check of an index entry, the plan of a splice and its host copy, and the container's rules that
+// every call must share, each written once.
 // This is the part that parses untrusted input.  It needs no GPU and no HIP header, so that a plain C++ program can run it under
 // the sanitizers (tools/knz_host_check.cpp); kz_stream.hip and kz_stream_device.hip are its users.
 // Layout: K/io/CompressedOutputStream.java (writeHeader :236-313, ordered block emission :1024-1035, end marker :483-493) and
@@ -9,6 +10,7 @@
 #include <string.h>
 #include <stdio.h>
 #include <algorithm>
+#include <vector>
 #include "../../include/kanzi_hip.h"
 
 struct HostBits {            // MSB-first writer (DefaultOutputBitStream.java:103-205)
@@ -253,4 +255,108 @@ static inline bool knz_check_entry(const uint8_t* src, int64_t n, int64_t hdrEnd
     if ((int)t.get(5) + 3 == lr && (int64_t)t.get(lr) == W) return true;
   }
   return false;
+}
+
+// ---- splice: a new stream out of blocks of existing streams (kz_knz_splice / kz_knz_splice_device) ----
+// The plan of a splice, in the three steps both forms take in this order: the arguments, the sources' headers, and (behind the check
+// of every piece against its own source: knz_check_entry on the host, k_knz_check_many on the device) the layout of the result.
+// Only host arrays and the first bytes of every source are looked at, so the plan is the same code for both forms.
+struct KnzSplice {
+  KnzHeader h;                       // what the sources agree in (source 0's header)
+  uint8_t hdr[32]; int64_t hdrBits;  // the result's stream header
+  int64_t endBit;                    // the bit behind the end marker
+};
+static inline int knz_splice_args(const void* src, const int64_t* srcOff, const int64_t* srcLen, int32_t nSrc, const int32_t* pieceSrc, const int64_t* pieceBitOff,
+                                  const int64_t* pieceBits, int32_t nPieces, int64_t inputSize, const void* dst, int64_t dstCap) {
+  if (!src || !srcOff || !srcLen || nSrc < 1 || nPieces < 0 || (nPieces > 0 && (!pieceSrc || !pieceBitOff || !pieceBits)) || inputSize < 0 || !dst || dstCap < 0)
+    return -KZ_ERR_INVALID_PARAM;
+  for (int s = 0; s < nSrc; s++) if (srcOff[s] < 0 || srcLen[s] < 0) return -KZ_ERR_INVALID_PARAM;
+  for (int i = 0; i < nPieces; i++) if (pieceSrc[i] < 0 || pieceSrc[i] >= nSrc) return -KZ_ERR_INVALID_PARAM;
+  return 0;
+}
+// The header of every source (the first min(26, srcLen[s]) bytes of source s at heads + headOff[s]), each one parsed whether a piece
+// names the source or not, and compared with source 0's; hdrEnd[s] = the bit behind it.  A header's fault is its code from
+// read_stream_header; err (may be null) names the source.
+static inline int knz_splice_sources(const uint8_t* heads, const int64_t* headOff, const int64_t* srcLen, int nSrc, KnzSplice& P, int64_t* hdrEnd, char* err, size_t errCap) {
+  for (int s = 0; s < nSrc; s++) {
+    HostBitsIn bs{heads + headOff[s], (uint64_t)std::min<int64_t>(srcLen[s], 26) * 8, 0, false};
+    KnzHeader h;
+    char why[96] = "";
+    const int rc = read_stream_header(bs, h, why, sizeof(why));
+    if (rc) { if (err) snprintf(err, errCap, "source %d: %s", s, why[0] ? why : "not a stream header"); return rc; }
+    hdrEnd[s] = (int64_t)bs.pos;
+    if (s == 0) { P.h = h; continue; }
+    const char* what = h.transformType != P.h.transformType ? "the transform word" : (h.entropyType != P.h.entropyType ? "the entropy id" :
+                       (h.blockSize != P.h.blockSize ? "the block size" : (h.chkKind != P.h.chkKind ? "the checksum kind" : nullptr)));
+    if (what) { if (err) snprintf(err, errCap, "source %d differs from source 0 in %s", s, what); return -KZ_ERR_INVALID_PARAM; }
+  }
+  return 0;
+}
+static inline int knz_splice_mismatch(int64_t i, char* err, size_t errCap) {
+  if (err) snprintf(err, errCap, "piece %lld does not match its source", (long long)i);
+  return -KZ_ERR_INVALID_PARAM;
+}
+// The result of pieces that passed their checks (0 < W < 2^34): the stream header, pre[i] = the bit where piece i's prefix starts
+// (pre[nPieces] = the end marker's), the end bit.  -KZ_ERR_WRITE_FILE when that is more than dstCap bytes: nothing has been written.
+static inline int knz_splice_layout(const int64_t* pieceBits, int nPieces, int64_t inputSize, int64_t dstCap, KnzSplice& P, int64_t* pre) {
+  HostBits hb{P.hdr, 32, 0, false};
+  write_stream_header(hb, P.h.transformType, (uint32_t)P.h.entropyType, P.h.blockSize, inputSize, P.h.chkKind);
+  P.hdrBits = (int64_t)hb.pos;
+  int64_t pos = P.hdrBits;
+  for (int i = 0; i < nPieces; i++) {
+    pre[i] = pos;
+    pos += 5 + knz_prefix_width((uint64_t)pieceBits[i]) + pieceBits[i];
+    if (pos > (1LL << 62)) return -KZ_ERR_WRITE_FILE;
+  }
+  pre[nPieces] = pos;
+  P.endBit = pos + 8;
+  return ((P.endBit + 7) >> 3) > dstCap ? -KZ_ERR_WRITE_FILE : 0;
+}
+// kz_knz_splice_bound: the longest stream header, 5 + lw + W bits per piece, the end marker
+static inline int64_t knz_splice_bound(const int64_t* pieceBits, int32_t nPieces) {
+  if (nPieces < 0 || (nPieces > 0 && !pieceBits)) return -KZ_ERR_INVALID_PARAM;
+  int64_t bits = 8;
+  for (int i = 0; i < nPieces; i++) {
+    if (pieceBits[i] < 0 || pieceBits[i] >= (1LL << 34)) return -KZ_ERR_INVALID_PARAM;
+    bits += 5 + knz_prefix_width((uint64_t)pieceBits[i]) + pieceBits[i];
+    if (bits > (1LL << 62)) return -KZ_ERR_INVALID_PARAM;
+  }
+  return 26 + ((bits + 7) >> 3);
+}
+// W bits from bit `off` of a stream of n bytes to the writer's position, whatever the two bit phases are.  The caller has checked
+// that [off, off + W) lies inside the stream and that the writer has the room.
+static inline void knz_copy_bits(HostBits& bs, const uint8_t* src, int64_t n, int64_t off, int64_t W) {
+  uint8_t tmp[4096];
+  HostBitsIn in{src, (uint64_t)n * 8, (uint64_t)off, false};
+  while (W > 0) {
+    const int64_t k = std::min<int64_t>(W, (int64_t)sizeof(tmp) * 8);
+    in.getBytes(tmp, (uint64_t)k);
+    bs.putBytes(tmp, (uint64_t)k);
+    W -= k;
+  }
+}
+// kz_knz_splice: the plan, with knz_check_entry on every piece, then per piece its minimal prefix and its payload bits copied from
+// where they lie in their source.  Nothing is written before every check has passed.
+static inline int64_t knz_splice_host(const uint8_t* src, const int64_t* srcOff, const int64_t* srcLen, int32_t nSrc, const int32_t* pieceSrc,
+                                      const int64_t* pieceBitOff, const int64_t* pieceBits, int32_t nPieces, int64_t inputSize, uint8_t* dst, int64_t dstCap) {
+  { const int rc = knz_splice_args(src, srcOff, srcLen, nSrc, pieceSrc, pieceBitOff, pieceBits, nPieces, inputSize, dst, dstCap); if (rc) return rc; }
+  KnzSplice P;
+  std::vector<int64_t> hdrEnd((size_t)nSrc), pre((size_t)nPieces + 1);
+  { const int rc = knz_splice_sources(src, srcOff, srcLen, nSrc, P, hdrEnd.data(), nullptr, 0); if (rc) return rc; }
+  for (int i = 0; i < nPieces; i++) {
+    const int s = pieceSrc[i];
+    if (!knz_check_entry(src + srcOff[s], srcLen[s], hdrEnd[s], pieceBitOff[i], pieceBits[i])) return knz_splice_mismatch(i, nullptr, 0);
+  }
+  { const int rc = knz_splice_layout(pieceBits, nPieces, inputSize, dstCap, P, pre.data()); if (rc) return rc; }
+  HostBits bs{dst, dstCap, 0, false};
+  for (int64_t b = 0; b < (P.hdrBits >> 3); b++) bs.put(P.hdr[b], 8);
+  for (int i = 0; i < nPieces; i++) {
+    const int s = pieceSrc[i];
+    const int lw = knz_prefix_width((uint64_t)pieceBits[i]);
+    bs.put((uint64_t)(lw - 3), 5);
+    bs.put((uint64_t)pieceBits[i], lw);
+    knz_copy_bits(bs, src + srcOff[s], srcLen[s], pieceBitOff[i], pieceBits[i]);
+  }
+  write_end_marker(bs);
+  return bs.overflow ? -KZ_ERR_WRITE_FILE : (int64_t)((bs.pos + 7) >> 3);
 }

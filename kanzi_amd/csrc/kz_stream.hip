@@ -76,6 +76,14 @@ extern "C" int32_t kz_knz_index(const uint8_t* src, int64_t n, uint64_t* transfo
   return nb;
 }
 
+// A new stream out of blocks of existing streams, all in host memory: the plan and the copy are in kz_knz_host.h.
+extern "C" int64_t kz_knz_splice_bound(const int64_t* pieceBits, int32_t nPieces) { return knz_splice_bound(pieceBits, nPieces); }
+extern "C" int64_t kz_knz_splice(const uint8_t* src, const int64_t* srcOff, const int64_t* srcLen, int32_t nSrc,
+                                 const int32_t* pieceSrc, const int64_t* pieceBitOff, const int64_t* pieceBits, int32_t nPieces,
+                                 int64_t inputSize, uint8_t* dst, int64_t dstCap) {
+  return knz_splice_host(src, srcOff, srcLen, nSrc, pieceSrc, pieceBitOff, pieceBits, nPieces, inputSize, dst, dstCap);
+}
+
 // Ordered emission of a batch (CompressedOutputStream.java:1024-1035) at bit granularity.  The serial pass writes,
 // per block, the 5-bit / lw-bit length prefix and the (at most 7 + 7) payload bits that share a byte with a
 // neighbour, skipping the bytes that belong to one payload only; those interiors are then copied (shifted) by a

@@ -1,5 +1,5 @@
 // kz_stream_device.hip -- the .knz container with source and destination in HBM: the same streams as kz_stream.hip's calls write and
-// read, whole, by block range, by index, and many at a time.  The kernels are in kz_knz_gpu.hip; what stays on the host is what
+// read, whole, by block range, by index, and many at a time, and edits them without recoding (the splice).  The kernels are in kz_knz_gpu.hip; what stays on the host is what
 // kz_compress / kz_decompress do there as well and costs nothing: the stream header (kz_knz_host.h, on a copy of at most 26 bytes),
 // the bit-offset arithmetic over results[] (host arrays anyway), and the block checks on the 8 header bytes per block that the walk
 // kernel brings back.  The rules shared with the host-buffer calls are in kz_knz_host.h and kz_knz_stream.h.
@@ -721,4 +721,79 @@ extern "C" int32_t kz_decode_indexed_device(kz_ctx* ctx, const uint8_t* d_src, i
     kz_ktimer_flush(ctx);
   }
   return 0;
+}
+
+
+// =================================================================================================
+// splice: a new stream out of blocks of existing streams, all in HBM (kz_knz_splice_device).  The plan is the host form's
+// (kz_knz_host.h) on the first bytes of every source (k_knz_heads, one copy); every piece is checked against its own source on the
+// device (k_knz_check_many) before the layout is made and the room decided, and only then is anything written: the stream header,
+// and per chunk of pieces one k_knz_splice launch that copies payload bits straight from the sources to their place in d_dst.
+extern "C" int64_t kz_knz_splice_device(kz_ctx* ctx, const uint8_t* d_src, const int64_t* srcOff, const int64_t* srcLen, int32_t nSrc,
+                                        const int32_t* pieceSrc, const int64_t* pieceBitOff, const int64_t* pieceBits, int32_t nPieces,
+                                        int64_t inputSize, uint8_t* d_dst, int64_t dstCap) {
+  if (!ctx) return -KZ_ERR_INVALID_PARAM;
+  { const int rc = knz_splice_args(d_src, srcOff, srcLen, nSrc, pieceSrc, pieceBitOff, pieceBits, nPieces, inputSize, d_dst, dstCap); if (rc) return rc; }
+  KZ_HIP(hipSetDevice(ctx->device));
+  // ---- the first bytes of every source in one table, one copy; the headers are parsed and compared on the host ----
+  KnzSplice P;
+  std::vector<int64_t> hdrEnd((size_t)nSrc), pre((size_t)nPieces + 1);
+  {
+    const size_t tBytes = kz_align((size_t)nSrc * sizeof(KnzSrc), 64), headBytes = (size_t)nSrc * 32;
+    { const int rc = knz_tables(ctx, tBytes + headBytes); if (rc) return rc; }
+    KnzSrc* t = (KnzSrc*)ctx->knzPin.p;
+    for (int s = 0; s < nSrc; s++) t[s] = KnzSrc{srcOff[s], srcLen[s], 0, 0, 0, 0};
+    KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, t, (size_t)nSrc * sizeof(KnzSrc), hipMemcpyHostToDevice, ctx->stream));
+    { const int rc = kz_knz_heads(ctx, d_src, (const KnzSrc*)ctx->knzAux.p, nSrc, ctx->knzAux.p + tBytes); if (rc) return rc; }
+    KZ_HIP(hipMemcpyAsync(ctx->knzPin.p + tBytes, ctx->knzAux.p + tBytes, headBytes, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+    kz_ktimer_flush(ctx);
+    std::vector<int64_t> headOff((size_t)nSrc);
+    for (int s = 0; s < nSrc; s++) headOff[s] = (int64_t)s * 32;
+    const int rc = knz_splice_sources(ctx->knzPin.p + tBytes, headOff.data(), srcLen, nSrc, P, hdrEnd.data(), ctx->err, sizeof(ctx->err));
+    if (rc) return rc;
+  }
+  // ---- chunks of pieces: a table entry per piece (pinned and in HBM), behind it the check's verdicts ----
+  const int CH = (int)std::max<int64_t>(1, std::min<int64_t>(knz_chunk_blocks(ctx, P.h.blockSize), nPieces));
+  const size_t pcBytes = kz_align((size_t)CH * sizeof(KnzPiece), 64);
+  { const int rc = knz_tables(ctx, pcBytes + (size_t)CH * sizeof(int32_t)); if (rc) return rc; }
+  KnzPiece* pc = (KnzPiece*)ctx->knzPin.p;
+  const KnzPiece* d_pc = (const KnzPiece*)ctx->knzAux.p;
+  auto fill = [&](int64_t b0, int cnt, bool placed) {
+    for (int i = 0; i < cnt; i++) {
+      const int64_t k = b0 + i;
+      const int s = pieceSrc[k];
+      pc[i] = KnzPiece{placed ? pre[k] + 5 + knz_prefix_width((uint64_t)pieceBits[k]) : 0, pieceBits[k], srcOff[s], srcLen[s], pieceBitOff[k], hdrEnd[s]};
+    }
+  };
+  for (int64_t b0 = 0; b0 < nPieces; b0 += CH) {                  // every piece against its own source, before a bit is copied
+    const int cnt = (int)std::min<int64_t>(CH, nPieces - b0);
+    fill(b0, cnt, false);
+    const int32_t* bad = (const int32_t*)(ctx->knzPin.p + pcBytes);
+    KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, pc, (size_t)cnt * sizeof(KnzPiece), hipMemcpyHostToDevice, ctx->stream));
+    { const int rc = kz_knz_check_many(ctx, d_src, d_pc, cnt, (int32_t*)(ctx->knzAux.p + pcBytes)); if (rc) return rc; }
+    KZ_HIP(hipMemcpyAsync(ctx->knzPin.p + pcBytes, ctx->knzAux.p + pcBytes, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+    kz_ktimer_flush(ctx);
+    for (int i = 0; i < cnt; i++) if (bad[i]) return knz_splice_mismatch(b0 + i, ctx->err, sizeof(ctx->err));
+  }
+  if (knz_splice_layout(pieceBits, nPieces, inputSize, dstCap, P, pre.data())) {
+    snprintf(ctx->err, sizeof(ctx->err), "kz_knz_splice_device: destination too small");
+    return -KZ_ERR_WRITE_FILE;
+  }
+  // ---- the copy: a launch per chunk owns the bits from its first prefix to the next chunk's (the last: to behind the end marker) ----
+  for (int64_t b0 = 0; b0 < nPieces || b0 == 0; b0 += CH) {
+    const int cnt = (int)std::min<int64_t>(CH, nPieces - b0);
+    fill(b0, cnt, true);
+    if (cnt) KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, pc, (size_t)cnt * sizeof(KnzPiece), hipMemcpyHostToDevice, ctx->stream));
+    const bool last = b0 + cnt >= nPieces;
+    { const int rc = kz_knz_splice_launch(ctx, d_src, d_pc, cnt, d_dst, pre[b0], last ? P.endBit : pre[b0 + cnt]); if (rc) return rc; }
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));                      // the pinned table is the next chunk's
+    kz_ktimer_flush(ctx);
+    if (last) break;
+  }
+  { const int hrc = knz_put_header(ctx, P.hdr, P.hdrBits >> 3, d_dst); if (hrc) return hrc; }
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  return (P.endBit + 7) >> 3;
 }

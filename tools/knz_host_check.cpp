@@ -1,5 +1,5 @@
 // knz_host_check.cpp -- the host-only core of the .knz container (kanzi_amd/csrc/kz_knz_host.h: bit I/O, stream header, prefix chain,
-// block-header precheck, index-entry check) under the sanitizers, on the CPU:
+// block-header precheck, index-entry check, the splice plan and its host copy) under the sanitizers, on the CPU:
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I kanzi_amd/csrc tools/knz_host_check.cpp -o /tmp/knz_host_check && /tmp/knz_host_check
 // Every buffer is a heap allocation of the exact size, so a read or write one byte outside it is reported.
 #include "kz_knz_host.h"
@@ -260,6 +260,151 @@ static void check_rules() {
   CHECK(knz_block_verdict(r, 1024, 0, 10) == -KZ_ERR_CRC_CHECK, "verdict: status first");
 }
 
+// ---- splice: the plan and the host copy on sources and destinations of the exact size ----
+struct SpliceSrc { Buf s; int64_t n, hdrEnd; std::vector<int64_t> off, W; std::vector<Buf> pay; };
+static SpliceSrc splice_stream(const std::vector<uint64_t>& Ws, uint64_t tt, int ent, int bsz, int chk) {
+  SpliceSrc S;
+  const size_t cap = 1 << 16;
+  Buf tmp = buf(cap);
+  HostBits w{tmp.get(), (int64_t)cap, 0, false};
+  write_stream_header(w, tt, (uint32_t)ent, bsz, 4000, chk);
+  S.hdrEnd = (int64_t)w.pos;
+  for (uint64_t W : Ws) {
+    const size_t pb = (size_t)(W + 7) / 8;
+    Buf pay = buf(pb);
+    for (size_t j = 0; j < pb; j++) pay[j] = (uint8_t)rnd();
+    S.off.push_back((int64_t)w.pos + 5 + knz_prefix_width(W));
+    S.W.push_back((int64_t)W);
+    write_block(w, pay.get(), W);
+    S.pay.push_back(std::move(pay));
+  }
+  write_end_marker(w);
+  CHECK(!w.overflow, "splice source built");
+  S.n = (int64_t)((w.pos + 7) >> 3);
+  S.s = buf((size_t)S.n);
+  memcpy(S.s.get(), tmp.get(), (size_t)S.n);
+  return S;
+}
+static void check_splice() {
+  const uint64_t tt = 2ULL << 42;
+  SpliceSrc A = splice_stream({9, 64, 100, 1000, 7, 4096 * 8 + 3, 33}, tt, 1, 1024, 1);
+  SpliceSrc B = splice_stream({801, 15, 8 * 5000}, tt, 1, 1024, 1);
+  // the two sources back to back in one allocation of the exact size
+  const int64_t total = A.n + B.n;
+  Buf both = buf((size_t)total);
+  memcpy(both.get(), A.s.get(), (size_t)A.n);
+  memcpy(both.get() + A.n, B.s.get(), (size_t)B.n);
+  const int64_t srcOff[2] = {0, A.n}, srcLen[2] = {A.n, B.n};
+  const SpliceSrc* S[2] = {&A, &B};
+  // pieces: interleaved, reversed, with repeats, the sources' last blocks among them
+  std::vector<int32_t> ps; std::vector<int64_t> po, pw;
+  const int order[][2] = {{1, 2}, {0, 6}, {0, 0}, {1, 0}, {0, 5}, {0, 5}, {1, 1}, {0, 3}, {0, 4}, {0, 1}, {0, 2}, {1, 2}};
+  for (auto& o : order) { ps.push_back(o[0]); po.push_back(S[o[0]]->off[o[1]]); pw.push_back(S[o[0]]->W[o[1]]); }
+  const int np = (int)ps.size();
+  for (int64_t inputSize : {(int64_t)0, (int64_t)70000, (int64_t)1 << 33}) {
+    const int64_t bound = knz_splice_bound(pw.data(), np);
+    Buf want = buf((size_t)bound);
+    HostBits w{want.get(), bound, 0, false};
+    write_stream_header(w, tt, 1, 1024, inputSize, 1);
+    for (auto& o : order) write_block(w, S[o[0]]->pay[o[1]].get(), (uint64_t)S[o[0]]->W[o[1]]);
+    write_end_marker(w);
+    const int64_t size = (int64_t)((w.pos + 7) >> 3);
+    CHECK(!w.overflow && size <= bound, "splice bound %lld, size %lld", (long long)bound, (long long)size);
+    Buf d = buf((size_t)size);                                     // dstCap exact
+    const int64_t rc = knz_splice_host(both.get(), srcOff, srcLen, 2, ps.data(), po.data(), pw.data(), np, inputSize, d.get(), size);
+    CHECK(rc == size && memcmp(d.get(), want.get(), (size_t)size) == 0, "splice of %d pieces: rc %lld, want %lld", np, (long long)rc, (long long)size);
+    Buf e = buf((size_t)size - 1), poison = buf((size_t)size - 1);  // one byte less: refused, nothing written
+    CHECK(knz_splice_host(both.get(), srcOff, srcLen, 2, ps.data(), po.data(), pw.data(), np, inputSize, e.get(), size - 1) == -KZ_ERR_WRITE_FILE &&
+          memcmp(e.get(), poison.get(), (size_t)size - 1) == 0, "splice into a destination one byte short");
+  }
+  // no pieces: header and end marker
+  {
+    Buf d = buf(21);
+    CHECK(knz_splice_host(both.get(), srcOff, srcLen, 2, nullptr, nullptr, nullptr, 0, 0, d.get(), 21) == 21 && d[20] == 0, "splice of no pieces");
+    CHECK(knz_splice_host(both.get(), srcOff, srcLen, 2, nullptr, nullptr, nullptr, 0, 0, d.get(), 20) == -KZ_ERR_WRITE_FILE, "splice of no pieces, short");
+  }
+  // refusals: dst stays poisoned
+  const int64_t cap = knz_splice_bound(pw.data(), np);
+  Buf d = buf((size_t)cap), poison = buf((size_t)cap);
+  auto run = [&](const uint8_t* src, const int64_t* so, const int64_t* sl, int ns, const int32_t* s, const int64_t* o, const int64_t* w_, int n, int64_t isz, uint8_t* dst, int64_t c) {
+    const int64_t rc = knz_splice_host(src, so, sl, ns, s, o, w_, n, isz, dst, c);
+    CHECK(memcmp(d.get(), poison.get(), (size_t)cap) == 0, "a refused splice wrote to dst (rc %lld)", (long long)rc);
+    return rc;
+  };
+  CHECK(run(nullptr, srcOff, srcLen, 2, ps.data(), po.data(), pw.data(), np, 0, d.get(), cap) == -KZ_ERR_INVALID_PARAM, "null src");
+  CHECK(run(both.get(), nullptr, srcLen, 2, ps.data(), po.data(), pw.data(), np, 0, d.get(), cap) == -KZ_ERR_INVALID_PARAM, "null srcOff");
+  CHECK(run(both.get(), srcOff, srcLen, 0, ps.data(), po.data(), pw.data(), np, 0, d.get(), cap) == -KZ_ERR_INVALID_PARAM, "nSrc 0");
+  CHECK(run(both.get(), srcOff, srcLen, 2, ps.data(), po.data(), pw.data(), -1, 0, d.get(), cap) == -KZ_ERR_INVALID_PARAM, "nPieces -1");
+  CHECK(run(both.get(), srcOff, srcLen, 2, nullptr, po.data(), pw.data(), np, 0, d.get(), cap) == -KZ_ERR_INVALID_PARAM, "null pieceSrc");
+  CHECK(run(both.get(), srcOff, srcLen, 2, ps.data(), po.data(), pw.data(), np, -1, d.get(), cap) == -KZ_ERR_INVALID_PARAM, "inputSize -1");
+  CHECK(run(both.get(), srcOff, srcLen, 2, ps.data(), po.data(), pw.data(), np, 0, nullptr, cap) == -KZ_ERR_INVALID_PARAM, "null dst");
+  { const int64_t bad[2] = {0, -1}; CHECK(run(both.get(), srcOff, bad, 2, ps.data(), po.data(), pw.data(), np, 0, d.get(), cap) == -KZ_ERR_INVALID_PARAM, "negative srcLen"); }
+  for (int32_t v : {-1, 2}) { std::vector<int32_t> b = ps; b[3] = v; CHECK(run(both.get(), srcOff, srcLen, 2, b.data(), po.data(), pw.data(), np, 0, d.get(), cap) == -KZ_ERR_INVALID_PARAM, "pieceSrc %d", v); }
+  // a piece named with the other source, shifted, lengthened, with W out of range
+  { std::vector<int32_t> b = ps; b[0] = 0; CHECK(run(both.get(), srcOff, srcLen, 2, b.data(), po.data(), pw.data(), np, 0, d.get(), cap) == -KZ_ERR_INVALID_PARAM, "piece of the other source"); }
+  for (int dlt : {-1, 1}) {
+    std::vector<int64_t> o = po; o[np - 1] += dlt;
+    CHECK(run(both.get(), srcOff, srcLen, 2, ps.data(), o.data(), pw.data(), np, 0, d.get(), cap) == -KZ_ERR_INVALID_PARAM, "piece off %+d", dlt);
+    std::vector<int64_t> w_ = pw; w_[np - 1] += dlt;
+    CHECK(run(both.get(), srcOff, srcLen, 2, ps.data(), po.data(), w_.data(), np, 0, d.get(), cap) == -KZ_ERR_INVALID_PARAM, "piece W %+d", dlt);
+  }
+  for (int64_t v : {(int64_t)0, (int64_t)-5, (int64_t)1 << 34, INT64_MAX}) {
+    std::vector<int64_t> w_ = pw; w_[2] = v;
+    CHECK(run(both.get(), srcOff, srcLen, 2, ps.data(), po.data(), w_.data(), np, 0, d.get(), cap) == -KZ_ERR_INVALID_PARAM, "piece W %lld", (long long)v);
+    std::vector<int64_t> o = po; o[2] = v;
+    CHECK(run(both.get(), srcOff, srcLen, 2, ps.data(), o.data(), pw.data(), np, 0, d.get(), cap) == -KZ_ERR_INVALID_PARAM, "piece off %lld", (long long)v);
+  }
+  // a bad header in a source that no piece names; sources that disagree in each of the four
+  {
+    std::vector<int32_t> onlyA; std::vector<int64_t> oA, wA;
+    for (int i = 0; i < np; i++) if (ps[i] == 0) { onlyA.push_back(0); oA.push_back(po[i]); wA.push_back(pw[i]); }
+    Buf bad = buf((size_t)total);
+    memcpy(bad.get(), both.get(), (size_t)total);
+    bad[A.n] ^= 0x40;
+    CHECK(run(bad.get(), srcOff, srcLen, 2, onlyA.data(), oA.data(), wA.data(), (int)onlyA.size(), 0, d.get(), cap) == -KZ_ERR_INVALID_FILE, "magic of an unnamed source");
+    memcpy(bad.get(), both.get(), (size_t)total);
+    bad[A.n + 19] ^= 1;
+    CHECK(run(bad.get(), srcOff, srcLen, 2, onlyA.data(), oA.data(), wA.data(), (int)onlyA.size(), 0, d.get(), cap) == -KZ_ERR_CRC_CHECK, "header checksum of an unnamed source");
+    const int64_t shortLen[2] = {A.n, 10};
+    CHECK(run(both.get(), srcOff, shortLen, 2, onlyA.data(), oA.data(), wA.data(), (int)onlyA.size(), 0, d.get(), cap) < 0, "a source of 10 bytes");
+    struct { uint64_t tt; int ent, bsz, chk; const char* what; } other[] = {{3ULL << 42, 1, 1024, 1, "the transform word"}, {tt, 2, 1024, 1, "the entropy id"},
+                                                                           {tt, 1, 2048, 1, "the block size"}, {tt, 1, 1024, 2, "the checksum kind"}};
+    for (auto& o : other) {
+      SpliceSrc C = splice_stream({801, 15}, o.tt, o.ent, o.bsz, o.chk);
+      Buf two = buf((size_t)(A.n + C.n));
+      memcpy(two.get(), A.s.get(), (size_t)A.n);
+      memcpy(two.get() + A.n, C.s.get(), (size_t)C.n);
+      const int64_t so[2] = {0, A.n}, sl[2] = {A.n, C.n};
+      CHECK(run(two.get(), so, sl, 2, onlyA.data(), oA.data(), wA.data(), (int)onlyA.size(), 0, d.get(), cap) == -KZ_ERR_INVALID_PARAM, "sources that differ in %s", o.what);
+      KnzSplice P; int64_t he[2]; char err[128] = "";
+      CHECK(knz_splice_sources(two.get(), so, sl, 2, P, he, err, sizeof(err)) == -KZ_ERR_INVALID_PARAM && strstr(err, "source 1 differs from source 0 in") && strstr(err, o.what), "text: %s", err);
+    }
+  }
+  // a source cut inside a prefix and inside a payload, at every byte: the pieces in front of the cut are spliced, a piece that the cut
+  // touches is refused, and nothing is read behind the cut (the source is a heap buffer of the cut's size)
+  for (int64_t cut = A.hdrEnd / 8; cut < A.n; cut += (cut < 200 ? 1 : 97)) {
+    Buf c = buf((size_t)cut);
+    memcpy(c.get(), A.s.get(), (size_t)cut);
+    const int64_t so[1] = {0}, sl[1] = {cut};
+    for (size_t k = 0; k < A.W.size(); k++) {
+      const int32_t one = 0;
+      const bool whole = A.off[k] + A.W[k] <= cut * 8;
+      const int64_t rc = knz_splice_host(c.get(), so, sl, 1, &one, &A.off[k], &A.W[k], 1, 0, d.get(), cap);
+      if (whole) {
+        CHECK(rc > 0, "piece %zu in front of a cut at %lld: %lld", k, (long long)cut, (long long)rc);
+        HostBitsIn in{d.get(), (uint64_t)rc * 8, 160 + 5 + (uint64_t)knz_prefix_width((uint64_t)A.W[k]), false};
+        Buf back = buf((size_t)(A.W[k] + 7) / 8);
+        in.getBytes(back.get(), (uint64_t)A.W[k]);
+        const size_t fullB = (size_t)A.W[k] / 8;
+        CHECK(!in.error && memcmp(back.get(), A.pay[k].get(), fullB) == 0, "payload of piece %zu in front of a cut", k);
+        memset(d.get(), 0xA5, (size_t)cap);
+      } else CHECK(rc == -KZ_ERR_INVALID_PARAM && memcmp(d.get(), poison.get(), (size_t)cap) == 0, "piece %zu behind a cut at %lld: %lld", k, (long long)cut, (long long)rc);
+    }
+  }
+  // the bound's own refusals
+  { const int64_t w1[1] = {-1}, w2[1] = {1LL << 34}; CHECK(knz_splice_bound(w1, 1) == -KZ_ERR_INVALID_PARAM && knz_splice_bound(w2, 1) == -KZ_ERR_INVALID_PARAM && knz_splice_bound(nullptr, 1) == -KZ_ERR_INVALID_PARAM && knz_splice_bound(nullptr, 0) == 27, "splice bound refusals"); }
+}
+
 int main() {
   check_prefix_width();
   check_bit_io();
@@ -267,6 +412,7 @@ int main() {
   check_entries();
   check_block_header();
   check_rules();
+  check_splice();
   printf("knz_host_check ok: %ld checks\n", checked);
   return 0;
 }
