@@ -420,6 +420,64 @@ int32_t kz_decode_indexed_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n,
                                  const int64_t* blockBitOff /* host */, const int64_t* blockBits /* host */, int32_t nBlocks,
                                  uint8_t* d_dst, int64_t dstStride, kz_block_result* results /* host */);
 
+/* ---- byte-addressed reads: many ranges of the original data in one call ---------------------------
+ * "Give me bytes [rangeOff[i], rangeOff[i] + rangeLen[i]) of the original data, for nRanges ranges at once", on host memory and on
+ * device memory.  The index (blockBitOff, blockBits, nIndex) is the WHOLE stream's, exactly as kz_knz_index / kz_knz_index_device
+ * return it.  Block k holds the original bytes [B[k], B[k + 1]), B = blockByteOff, a table of nIndex + 1 entries.  With blockByteOff
+ * == NULL, B[k] = k * blockSize (the stream header's block size): the last index block is the only one that may be short, and its
+ * decoded length defines the end of data.  A table says where every block starts, so a stream with short blocks in the middle (what
+ * kz_knz_splice[_device] makes of the N streams of a many-stream call, whose input sizes the caller knows) is byte-addressable too;
+ * B[nIndex] is then the end of data.
+ *
+ * Ranges may come in any order, overlap and repeat.  A range is cut at the end of data as a slice is: got[i] is the number of bytes
+ * delivered, possibly 0; a range that starts at or behind the end decodes nothing (without a table, a range that starts inside the
+ * last block's blockSize bytes has that block decoded to learn where the data ends).  A range's end is never computed: one whose
+ * rangeOff + rangeLen leaves int64 reaches the end of data.  The destination is packed by REQUESTED length: range i owns the slot
+ * dst[D[i] .. D[i] + rangeLen[i]) with D[i] = the sum of rangeLen[j] for j < i.
+ *
+ * Each distinct block that some range touches is decoded once, in ascending block order, whatever the order of the ranges; blocks
+ * that no range touches are neither decoded nor checked, and their index entries are not looked at.  Only the decoded blocks are
+ * verified: block k's decoded length must be B[k + 1] - B[k] (without a table: blockSize for every block but the last), else every
+ * range that touches it gets got[i] = -KZ_ERR_INVALID_FILE.  The index is the caller's and is not trusted: every entry the call
+ * uses gets the indexed reads' check against the stream (above; k_knz_check on the device) before anything is unpacked.
+ *
+ *   addresses   src / d_src and dst / d_dst: any address, any alignment; they must not overlap.  blockBitOff, blockBits,
+ *               blockByteOff, rangeOff, rangeLen and got are host arrays in both calls.
+ *   read        nothing outside src[0 .. n), and of that only the stream header and the blocks that ranges touch.
+ *   written     nothing outside dst[0 .. D[nRanges]), and nothing outside the slots at all.  Of slot i the first got[i] bytes are
+ *               specified; the rest of a cut range's slot is untouched; the slot of a failed range (got[i] < 0) is unspecified.
+ *               got[0 .. nRanges) is written whenever the call returns a size.
+ *   returns     D[nRanges], or a negative code for a fault of the call, in this order: -KZ_ERR_INVALID_PARAM for bad arguments
+ *               (null pointers, a negative n, nIndex, nRanges, dstCap, rangeOff[i] or rangeLen[i]); the stream header's code as
+ *               from kz_decompress; -KZ_ERR_INVALID_PARAM for a table without B[0] == 0 and 1 <= B[k + 1] - B[k] <= blockSize,
+ *               before anything but the stream header is read from src; -KZ_ERR_WRITE_FILE for D[nRanges] > dstCap, decided from
+ *               the arguments before anything is written; nRanges == 0 returns 0 here, after the header checks;
+ *               -KZ_ERR_INVALID_PARAM for the first used entry, in block order, that does not match the stream (kz_last_error:
+ *               "index entry %d does not match the stream"; dst untouched); -KZ_ERR_DEVICE.  A block's own fault (its header
+ *               precheck, the staging-row bound, its decode, its checksum, its length) goes to got[i] of the ranges that touch
+ *               it, as that block's status (of several failing blocks: the first in block order); all other ranges are delivered.
+ *               The transform word, entropy id, block size and checksum kind come from the stream header; the context's checksum
+ *               setting is the stream's for the call and restored after it.
+ *   chunks      the distinct blocks go in chunks of kz_compress_device's size (KZ_STREAM_CHUNK=<blocks> overrides) into the
+ *               context's staging rows, blockSize apart.  A segment is one range cut with one block; after each chunk its
+ *               segments are copied to their places: memcpy on the host, on the device one k_knz_read launch per 2^20 segments of
+ *               the chunk, which spreads the 16-byte destination units of all its segments over the lanes (a 64-byte record
+ *               costs 4 or 5 lanes, not a workgroup).  A range that lies across a chunk seam is completed by two launches on the
+ *               same stream.  The segment table lives in the context's grow-only table buffers: 32 bytes per segment x the
+ *               segments of one launch (32 MiB at the most), pinned and in HBM.  Host memory proportional to the number of
+ *               segments of the whole call (about 50 bytes each) and to nRanges is used besides.
+ *   cost        a record costs the decode of its whole block, whatever its length: stores of small records choose small blocks.
+ *   stream      the calls are synchronous and run on the context's stream.
+ */
+int64_t kz_read_bytes(kz_ctx* ctx, const uint8_t* src, int64_t n,
+                      const int64_t* blockBitOff, const int64_t* blockBits, const int64_t* blockByteOff /* NULL or nIndex + 1 entries */, int32_t nIndex,
+                      const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges,
+                      uint8_t* dst, int64_t dstCap, int64_t* got);
+int64_t kz_read_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n,
+                             const int64_t* blockBitOff /* host */, const int64_t* blockBits /* host */, const int64_t* blockByteOff /* host: NULL or nIndex + 1 entries */, int32_t nIndex,
+                             const int64_t* rangeOff /* host */, const int64_t* rangeLen /* host */, int32_t nRanges,
+                             uint8_t* d_dst, int64_t dstCap, int64_t* got /* host, out */);
+
 /* ---- splice: a new .knz stream out of blocks of existing ones, without recoding -------------------
  * Blocks are independent of one another, and a stream is its header, then per block 5 + lw prefix bits and W payload bits, then the
  * end marker (:1024-1035, :483-493): a stream made of blocks taken from existing streams is a bit-granular copy.  One call joins the

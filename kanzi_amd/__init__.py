@@ -121,6 +121,8 @@ def load_library():
         "kz_decompress_range_device": (c.c_int64, [vp, u8p, c.c_int64, c.c_int64, c.c_int64, u8p, c.c_int64]),
         "kz_decode_indexed": (c.c_int32, [vp, u8p, c.c_int64, i64p, i64p, c.c_int32, u8p, c.c_int64, vp]),
         "kz_decode_indexed_device": (c.c_int32, [vp, u8p, c.c_int64, i64p, i64p, c.c_int32, u8p, c.c_int64, vp]),
+        "kz_read_bytes": (c.c_int64, [vp, u8p, c.c_int64, i64p, i64p, i64p, c.c_int32, i64p, i64p, c.c_int32, u8p, c.c_int64, i64p]),
+        "kz_read_bytes_device": (c.c_int64, [vp, u8p, c.c_int64, i64p, i64p, i64p, c.c_int32, i64p, i64p, c.c_int32, u8p, c.c_int64, i64p]),
         "kz_knz_splice_bound": (c.c_int64, [i64p, c.c_int32]),
         "kz_knz_splice": (c.c_int64, [u8p, i64p, i64p, c.c_int32, i32p, i64p, i64p, c.c_int32, c.c_int64, u8p, c.c_int64]),
         "kz_knz_splice_device": (c.c_int64, [vp, u8p, i64p, i64p, c.c_int32, i32p, i64p, i64p, c.c_int32, c.c_int64, u8p, c.c_int64]),
@@ -154,6 +156,7 @@ ABI_SYMBOLS = ["kz_abi_version", "kz_ctx_create", "kz_ctx_destroy", "kz_last_err
                "kz_compress_device", "kz_decompress_device", "kz_knz_assemble_device", "kz_knz_index_device",
                "kz_compress_many_bound", "kz_compress_many_device", "kz_decompress_many_device",
                "kz_decompress_range", "kz_decompress_range_device", "kz_decode_indexed", "kz_decode_indexed_device",
+               "kz_read_bytes", "kz_read_bytes_device",
                "kz_knz_splice_bound", "kz_knz_splice", "kz_knz_splice_device",
                "kz_set_timing", "kz_get_stage_count", "kz_get_stage_ms", "kz_get_stage_alg_bytes", "kz_reset_timing",
                "kz_set_kernel_timing", "kz_get_kernel_count", "kz_get_kernel_name", "kz_get_kernel_ms", "kz_get_kernel_max_ms",
@@ -1047,13 +1050,70 @@ def decode_indexed_device(ctx, src, n, offsets, bits, dst, stride):
     return _indexed(ctx.lib.kz_decode_indexed_device, ctx, _ptr(src), n, offsets, bits, _ptr(dst), stride)
 
 
+# ---- byte-addressed reads: many ranges of the original data in one call (kz_read_bytes / kz_read_bytes_device) ----
+def block_byte_offsets(input_sizes, block_size):
+    """The blockByteOff table of a splice_concat of streams that kz_compress* wrote for inputs of the given sizes: every stream's
+    blocks are block_size bytes but its last -> [0, ..., sum(input_sizes)], one entry more than the joined stream has blocks."""
+    bs, out = int(block_size), [0]
+    for n in input_sizes:
+        n = int(n)
+        if n < 0 or bs < 1:
+            raise ValueError("sizes must not be negative")
+        out += [out[-1] + min((k + 1) * bs, n) for k in range((n + bs - 1) // bs)]
+    return out
+
+
+def _read_arrays(index, offsets, sizes, byte_offsets):
+    blocks = index["blocks"] if isinstance(index, dict) else list(index)
+    off = np.ascontiguousarray([b[0] for b in blocks], dtype=np.int64)
+    w = np.ascontiguousarray([b[1] for b in blocks], dtype=np.int64)
+    ro = np.ascontiguousarray(offsets, dtype=np.int64)
+    rl = np.ascontiguousarray(sizes, dtype=np.int64)
+    if len(ro) != len(rl):
+        raise ValueError("offsets and sizes differ in length")
+    tab = None
+    if byte_offsets is not None:
+        tab = np.ascontiguousarray(byte_offsets, dtype=np.int64)
+        if len(tab) != len(off) + 1:
+            raise ValueError("byte_offsets needs one entry more than the index has blocks")
+    return off, w, tab, ro, rl, np.zeros(max(len(ro), 1), dtype=np.int64)
+
+
+def read_bytes(ctx, data, index, offsets, sizes, byte_offsets=None):
+    """kz_read_bytes: bytes [offsets[i], offsets[i] + sizes[i]) of the original data of the .knz bytes `data`, for all i in one call
+    -> (list of bytes, got).  index: knz_index(data) or its "blocks"; byte_offsets: where every block starts in the original data
+    (block_byte_offsets), None for a stream whose blocks are all blockSize but the last.  A range is cut at the end of data;
+    got[i] is its length, or the negative status of a block it touches (its entry in the list is then None)."""
+    data = bytes(data)
+    off, w, tab, ro, rl, got = _read_arrays(index, offsets, sizes, byte_offsets)
+    src = np.frombuffer(data + b"\0" * 16, dtype=np.uint8)
+    cap = int(rl.sum()) if len(rl) and int(rl.min()) >= 0 else 0
+    dst = np.zeros(max(cap, 1), dtype=np.uint8)
+    ctx.check(ctx.lib.kz_read_bytes(ctx.h, src.ctypes.data, len(data), _arg(off), _arg(w), None if tab is None else tab.ctypes.data, len(off),
+                                    _arg(ro), _arg(rl), len(ro), dst.ctypes.data, cap, got.ctypes.data))
+    at = np.concatenate(([0], np.cumsum(rl)))
+    got = [int(g) for g in got[:len(ro)]]
+    return [dst[at[i]:at[i] + g].tobytes() if g >= 0 else None for i, g in enumerate(got)], got
+
+
+def read_bytes_device(ctx, src, n, index, offsets, sizes, dst, cap, byte_offsets=None):
+    """kz_read_bytes_device: the same with the stream at device address `src` (n bytes); range i goes to device address
+    dst + sum(sizes[:i]) (capacity `cap` >= sum(sizes)) -> got."""
+    off, w, tab, ro, rl, got = _read_arrays(index, offsets, sizes, byte_offsets)
+    ctx.check(ctx.lib.kz_read_bytes_device(ctx.h, _ptr(src), int(n), _arg(off), _arg(w), None if tab is None else tab.ctypes.data, len(off),
+                                           _arg(ro), _arg(rl), len(ro), _ptr(dst), int(cap), got.ctypes.data))
+    return [int(g) for g in got[:len(ro)]]
+
+
 class KnzReader:
     """Random access to a .knz stream held as bytes or as a torch.uint8 device tensor: the index is built once (knz_index /
     knz_index_device, the one serial walk), every read after that goes through the indexed call and costs the same wherever its
-    blocks lie.  Reads of a device stream return device tensors, reads of bytes return bytes."""
+    blocks lie.  Reads of a device stream return device tensors, reads of bytes return bytes.  byte_offsets (block_byte_offsets)
+    says where every block starts in the original data, for read_many on a stream with short blocks in the middle."""
 
-    def __init__(self, ctx, knz):
+    def __init__(self, ctx, knz, byte_offsets=None):
         self.ctx = ctx
+        self.byte_offsets = None if byte_offsets is None else [int(b) for b in byte_offsets]
         self.device = not isinstance(knz, (bytes, bytearray, memoryview))
         if self.device:
             import torch
@@ -1117,6 +1177,32 @@ class KnzReader:
         if self.device:
             return flat[lo:max(hi, lo)].clone()
         return flat[lo:max(hi, lo)].tobytes()
+
+    def read_many(self, offsets, sizes):
+        """bytes [offsets[i], offsets[i] + sizes[i]) of the original data for all i, in one byte-addressed call (read_bytes /
+        read_bytes_device): every covering block is decoded once -> a list of bytes, or of views into one packed device tensor.
+        Each is cut at the end of data, as a slice is.  A range that touches a block that fails raises KanziError with that
+        block's code."""
+        offsets, sizes = [int(o) for o in offsets], [int(s) for s in sizes]
+        if any(o < 0 for o in offsets) or any(s < 0 for s in sizes):
+            raise ValueError("offset and size must not be negative")
+        if self.device:
+            import torch
+            total = sum(sizes)
+            out = torch.empty(max(total, 1), dtype=torch.uint8, device=self.src.device)
+            got = read_bytes_device(self.ctx, self.src.data_ptr(), self.src.numel(), self.blocks, offsets, sizes, out.data_ptr(), total, self.byte_offsets)
+        else:
+            parts, got = read_bytes(self.ctx, self.src, self.blocks, offsets, sizes, self.byte_offsets)
+        for i, g in enumerate(got):
+            if g < 0:
+                raise KanziError(-g, "range %d" % i)
+        if not self.device:
+            return parts
+        res, at = [], 0
+        for s, g in zip(sizes, got):
+            res.append(out[at:at + g])
+            at += s
+        return res
 
 
 # ---- splice: a new .knz stream out of blocks of existing ones, without recoding (kz_knz_splice / kz_knz_splice_device) ----

@@ -49,7 +49,7 @@
   X(KID_EXE_EMIT, "k_exe_emit") X(KID_KNZ_PACK, "k_knz_pack") X(KID_KNZ_WALK, "k_knz_walk") X(KID_KNZ_UNPACK, "k_knz_unpack") \
   X(KID_KNZ_CHECK, "k_knz_check") X(KID_KNZ_GATHER, "k_knz_gather") X(KID_KNZ_PACK_MANY, "k_knz_pack_many") X(KID_KNZ_HEADS, "k_knz_heads") \
   X(KID_KNZ_WALK_MANY, "k_knz_walk_many") X(KID_KNZ_UNPACK_MANY, "k_knz_unpack_many") X(KID_KNZ_SCATTER, "k_knz_scatter") \
-  X(KID_KNZ_CHECK_MANY, "k_knz_check_many") X(KID_KNZ_SPLICE, "k_knz_splice")
+  X(KID_KNZ_CHECK_MANY, "k_knz_check_many") X(KID_KNZ_SPLICE, "k_knz_splice") X(KID_KNZ_READ, "k_knz_read")
 #define KZ_KERNEL_ENUM(id, name) id,
 #define KZ_KERNEL_NAME(id, name) name,
 enum KzKernelId { KZ_KERNELS(KZ_KERNEL_ENUM) KID_COUNT };
@@ -77,6 +77,7 @@ struct kz_switches {
   int hostInvStaged = -1;        // KZ_HOST_INV_STAGED: -1 unset
   int streamChunk = 0;           // KZ_STREAM_CHUNK (0: default)
   int streamSerial = 0;          // KZ_STREAM_SERIAL
+  int readScatter = 0;           // KZ_READ_SCATTER: kz_read_bytes_device copies its segments with k_knz_scatter (tools/knz_read_probe.py's yardstick)
   int bwtTrie = -1, bwtTrieWin = -1, bwtBuckets = -1, bwtDmax = -1, bwtRetire = -1;   // KZ_BWT_TRIE / _TRIEWIN / _BUCKETS / _DMAX / _RETIRE (-1 unset)
   int bwtLazyRank = -1;         // KZ_BWT_LAZYRANK=0: round 0 stores every rank (A/B; see k_tr_sort)
   int bwtTrace = 0;              // KZ_BWT_TRACE
@@ -336,6 +337,10 @@ int kz_knz_unpack_many(kz_ctx*, const uint8_t* d_src, const KnzRow* d_t, int nr,
 struct KnzPiece { int64_t pay, bits, seg, n, off, hdrEnd; };
 int kz_knz_check_many(kz_ctx*, const uint8_t* d_src, const KnzPiece* d_pc, int np, int32_t* d_bad);
 int kz_knz_splice_launch(kz_ctx*, const uint8_t* d_src, const KnzPiece* d_pc, int np, uint8_t* d_dst, int64_t startBit, int64_t endBit);
+// byte-addressed reads (kz_read_bytes_device): ns segments (kz_knz_host.h) of rows `stride` apart, rowLen bytes of each the block's,
+// to their places in d_dst; the launch owns the destination units [unitBase, unitBase + units), d_seg[0].unit0 == unitBase
+struct KnzReadSeg;
+int kz_knz_read(kz_ctx*, const uint8_t* d_rows, int64_t stride, int rowLen, const KnzReadSeg* d_seg, int ns, uint8_t* d_dst, int64_t unitBase, int64_t units);
 
 // timing helpers
 void kz_stage_begin(kz_ctx*, hipEvent_t* e0);

@@ -3,12 +3,14 @@
 // prefixes (K/io/CompressedInputStream.java:1127-1129), and the check of a caller's index entries that stands in for the walk in
 // the indexed reads; behind them the same steps for many streams in one launch (a table entry per segment, slot or row, each with
 // its own bounds: kz_compress_many_device / kz_decompress_many_device), and the splice: the pack over pieces whose payload bits lie
-// where they are in their source streams, with the check of every piece against its own source in front of it (kz_knz_splice_device).
+// where they are in their source streams, with the check of every piece against its own source in front of it (kz_knz_splice_device);
+// and the copy of the byte-addressed reads: many (range x block) segments of decoded rows to their places in one launch (k_knz_read).
 // The callers (kz_compress_device / kz_decompress_device / kz_decompress_range_device /
 // kz_decode_indexed_device / kz_knz_assemble_device / kz_knz_index_device, kz_stream_device.hip) do the bit-offset arithmetic, the stream
 // header and the block-header prechecks on the host; no payload byte leaves the device.
 #include "kz_device.h"
 #include "kz_internal.h"
+#include "kz_knz_host.h"
 #include <algorithm>
 
 typedef uint8_t u8;
@@ -330,6 +332,49 @@ __device__ __forceinline__ void knz_ragged(const u8* __restrict__ from, const Kn
 __global__ void __launch_bounds__(256) k_knz_gather(const u8* __restrict__ src, const KnzCopy* __restrict__ t, int nr, u8* __restrict__ rows) { knz_ragged(src, t, nr, rows); }
 __global__ void __launch_bounds__(256) k_knz_scatter(const u8* __restrict__ rows, const KnzCopy* __restrict__ t, int nr, u8* __restrict__ dst) { knz_ragged(rows, t, nr, dst); }
 
+// ---- read: segments of decoded rows -> their places in dst (kz_read_bytes_device) -------------------------------------------------
+// Segment j (kz_knz_host.h: KnzReadSeg) is seg[j].len bytes from byte seg[j].off of the row rows + seg[j].slot * stride (rowLen bytes
+// of it are the block's) to dst + seg[j].dst, any alignment on both sides; from a few bytes to a whole block each, up to a million
+// of them.  No workgroup per segment: the launch's work is the 16-byte aligned destination units of all its segments, one segment
+// after the other (seg[j].unit0 = the first of segment j, a prefix sum that grows strictly with j; the launch owns units
+// [unitBase, unitBase + units), seg[0].unit0 == unitBase).  A lane takes a unit, finds its segment by binary search on unit0 and does
+// what knz_ragged does for a unit: a unit wholly inside the segment whose aligned load window stays inside the row is one wide
+// store, any other unit goes bytewise, the segment's own bytes only.  A unit of memory that two segments share is visited once per
+// segment, so every byte has one writer and no lane writes a byte that is not its segment's.  A segment whose len was cut after
+// unit0 was summed (knz_read_settle) has units with nothing in them: they are skipped.
+// The 64 units of a wave lie side by side and in one segment or a few neighbours: the wave searches once for its first and once for
+// its last unit with wave-uniform arguments, a lane then only between the two (k_knz_splice's scheme).
+__device__ __forceinline__ int knz_read_find(const KnzReadSeg* __restrict__ seg, int lo, int hi, int64_t u) {   // the last j in lo .. hi with unit0 <= u (seg[lo]'s is)
+  int a = lo + 1, b = hi + 1;
+  while (a < b) { const int m = (a + b) >> 1; if (seg[m].unit0 <= u) a = m + 1; else b = m; }
+  return a - 1;
+}
+__global__ void __launch_bounds__(256) k_knz_read(const u8* __restrict__ rows, int64_t stride, int rowLen, const KnzReadSeg* __restrict__ seg, int ns,
+                                                  u8* __restrict__ dst, int64_t unitBase, int64_t units) {
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < units; v += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t u = unitBase + v;
+    const int64_t u0 = knz_first_lane(u);                                             // the wave's units: at most 64 in a row from its first lane's
+    const int jlo = knz_read_find(seg, 0, ns - 1, u0);
+    int jhi = jlo;                                                                    // (every segment has a unit: 63 units on are at most 63 segments on)
+    if (jlo + 1 < ns && seg[jlo + 1].unit0 <= u0 + 63) jhi = knz_read_find(seg, jlo + 1, jlo + 63 < ns - 1 ? jlo + 63 : ns - 1, u0 + 63);
+    const int j = knz_read_find(seg, jlo, jhi, u);
+    const KnzReadSeg g = seg[j];
+    u8* d = dst + g.dst;
+    const uintptr_t A0 = (uintptr_t)d & ~(uintptr_t)15;
+    const int64_t ub = (int64_t)(A0 - (uintptr_t)d) + ((u - g.unit0) << 4);           // the unit's first byte as an index into the segment (may be < 0)
+    const int64_t lo = ub < 0 ? 0 : ub, hi = ub + 16 > g.len ? g.len : ub + 16;
+    if (lo >= hi) continue;
+    const u8* row = rows + (int64_t)g.slot * stride;
+    const u8* s = row + g.off;
+    if (hi - lo == 16) {
+      const u8* p = s + lo;
+      const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
+      if (al >= row && al + knz_window(p, 0) <= row + rowLen) { *(uint4*)(d + lo) = knz_load128(p, 0); continue; }
+    }
+    for (int64_t b = lo; b < hi; b++) d[b] = s[b];
+  }
+}
+
 // ---- pack: the blocks of many streams -> their slots -----------------------------------------------------------------------------
 // k_knz_pack's scheme over the slots of a group.  Stream s owns bytes [0, (endBit + 7) / 8) of its slot dst + seg[s].dst: the stream
 // header (seg[s].hdr, a whole number of bytes), the fields of blk[blk0 .. blk0 + nblk) (pay counted from the slot's first bit), zeros
@@ -482,6 +527,12 @@ int kz_knz_walk_many(kz_ctx* ctx, const uint8_t* d_src, const KnzSrc* d_t, int n
 int kz_knz_unpack_many(kz_ctx* ctx, const uint8_t* d_src, const KnzRow* d_t, int nr, int64_t maxBytes, uint8_t* d_rows) {
   if (nr <= 0) return 0;
   KZ_LAUNCH(ctx, KID_KNZ_UNPACK_MANY, k_knz_unpack_many, knz_unpack_grid(nr, maxBytes), dim3(256), d_src, d_t, nr, d_rows);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_read(kz_ctx* ctx, const uint8_t* d_rows, int64_t stride, int rowLen, const KnzReadSeg* d_seg, int ns, uint8_t* d_dst, int64_t unitBase, int64_t units) {
+  if (ns <= 0 || units <= 0) return 0;
+  KZ_LAUNCH(ctx, KID_KNZ_READ, k_knz_read, knz_pack_grid(units), dim3(256), d_rows, stride, rowLen, d_seg, ns, d_dst, unitBase, units);
   KZ_HIP(hipGetLastError());
   return 0;
 }

@@ -1,8 +1,8 @@
 // kz_knz_host.h -- the host-only core of the .knz container: bit I/O, the stream header, the chain of block length prefixes, the
-// block-header precheck and the check of an index entry, the plan of a splice and its host copy, and the container's rules that
-// every call must share, each written once.
+// block-header precheck and the check of an index entry, the plan of a splice and its host copy, the plan of a byte-addressed read,
+// and the container's rules that every call must share, each written once.
 // This is the part that parses untrusted input.  It needs no GPU and no HIP header, so that a plain C++ program can run it under
-// the sanitizers (tools/knz_host_check.cpp); kz_stream.hip and kz_stream_device.hip are its users.
+// the sanitizers (tools/knz_host_check.cpp, tools/knz_read_check.cpp); kz_stream.hip and kz_stream_device.hip are its users.
 // Layout: K/io/CompressedOutputStream.java (writeHeader :236-313, ordered block emission :1024-1035, end marker :483-493) and
 // K/io/CompressedInputStream.java (readHeader :359-515, block length prefix :1127-1129).
 #pragma once
@@ -359,4 +359,121 @@ static inline int64_t knz_splice_host(const uint8_t* src, const int64_t* srcOff,
   }
   write_end_marker(bs);
   return bs.overflow ? -KZ_ERR_WRITE_FILE : (int64_t)((bs.pos + 7) >> 3);
+}
+
+// ---- byte-addressed reads: many ranges of the original data in one call (kz_read_bytes / kz_read_bytes_device) ----
+// The plan of such a call, from host arrays alone, so that both forms share it: block k of the index holds the original bytes
+// [B[k], B[k + 1]), B = the caller's table or k * blockSize; range i owns dst[D[i], D[i] + rangeLen[i]), D = the running sum of the
+// requested lengths.  A segment is one range cut with one block.  All sums are formed so that no int64 overflows: a range's end is
+// never computed, its length is cut to what lies in front of the end of data instead.
+struct KnzReadSeg {          // 32 bytes: the entry of k_knz_read's table
+  int64_t dst;               // byte offset in dst
+  int64_t unit0;             // the segment's first 16-byte aligned destination unit among the units of its chunk (prefix sum)
+  int32_t slot;              // the block's row among the rows of its chunk
+  int32_t off;               // byte offset in the block
+  int32_t len;               // bytes (> 0 in the plan; knz_read_settle cuts it to what the block decoded to)
+  int32_t range;             // the owning range
+};
+struct KnzReadPlan {
+  int64_t end;                         // the end of data as the arguments give it: B[nIndex], or nIndex * blockSize without a table
+  std::vector<int32_t> blocks;         // the distinct covering blocks, ascending; chunk c = blocks[c * CH .. (c + 1) * CH)
+  std::vector<KnzReadSeg> segs;        // chunk by chunk; inside a chunk by dst, which is by range and then by block
+  std::vector<int64_t> first;          // chunk c owns segs[first[c] .. first[c + 1])
+  std::vector<int64_t> units;          // units[c] = the destination units of chunk c: what unit0 sums up to
+};
+// 16-byte aligned units of memory that len > 0 bytes from an address with (address mod 16) == phase touch
+static inline int64_t knz_read_units(int64_t phase, int64_t len) { return (phase + len + 15) >> 4; }
+static inline int knz_read_args(const void* src, int64_t n, const int64_t* blockBitOff, const int64_t* blockBits, int32_t nIndex, const int64_t* rangeOff,
+                                const int64_t* rangeLen, int32_t nRanges, const void* dst, int64_t dstCap, const int64_t* got) {
+  if (!src || n < 0 || nIndex < 0 || nRanges < 0 || dstCap < 0 || (nIndex > 0 && (!blockBitOff || !blockBits))) return -KZ_ERR_INVALID_PARAM;
+  if (nRanges > 0 && (!rangeOff || !rangeLen || !dst || !got)) return -KZ_ERR_INVALID_PARAM;
+  for (int32_t i = 0; i < nRanges; i++) if (rangeOff[i] < 0 || rangeLen[i] < 0) return -KZ_ERR_INVALID_PARAM;
+  return 0;
+}
+// a caller's table of nIndex + 1 byte offsets: B[0] == 0 and 1 <= B[k + 1] - B[k] <= blockSize (B[k] >= 0 by induction, so the
+// difference of an ascending pair cannot overflow)
+static inline int knz_read_table(const int64_t* B, int32_t nIndex, int32_t blockSize) {
+  if (!B) return 0;
+  if (B[0] != 0) return -KZ_ERR_INVALID_PARAM;
+  for (int32_t k = 0; k < nIndex; k++) if (B[k + 1] <= B[k] || B[k + 1] - B[k] > blockSize) return -KZ_ERR_INVALID_PARAM;
+  return 0;
+}
+// D[nRanges], or -KZ_ERR_WRITE_FILE when it is more than dstCap (a sum that leaves int64 is)
+static inline int64_t knz_read_total(const int64_t* rangeLen, int32_t nRanges, int64_t dstCap) {
+  int64_t D = 0;
+  for (int32_t i = 0; i < nRanges; i++) {
+    if (rangeLen[i] > dstCap - D) return -KZ_ERR_WRITE_FILE;
+    D += rangeLen[i];
+  }
+  return D;
+}
+// the decoded length block k must have: B[k + 1] - B[k]; without a table blockSize, and -1 (any length up to blockSize) for the last
+static inline int64_t knz_read_block_len(const int64_t* B, int32_t nIndex, int32_t blockSize, int32_t k) {
+  if (B) return B[k + 1] - B[k];
+  return k == nIndex - 1 ? -1 : blockSize;
+}
+// The plan.  The arguments have passed knz_read_args and knz_read_table; CH >= 1 = blocks per chunk; dstPhase = dst's address mod
+// 16 (the host form passes 0: unit0 is the kernel's).  Ranges of no bytes and ranges that start at or behind P.end have no segment.
+static inline void knz_read_plan(const int64_t* B, int32_t nIndex, int32_t blockSize, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges,
+                                 int CH, int dstPhase, KnzReadPlan& P) {
+  P.end = B ? B[nIndex] : (int64_t)nIndex * blockSize;
+  P.blocks.clear(); P.segs.clear(); P.first.assign(1, 0); P.units.clear();
+  std::vector<KnzReadSeg> all;                                     // in range order: by dst
+  std::vector<int32_t> blk;                                        // the block of all[i]
+  int64_t D = 0;
+  for (int32_t i = 0; i < nRanges; i++) {
+    const int64_t o = rangeOff[i];
+    int64_t left = o < P.end ? std::min<int64_t>(rangeLen[i], P.end - o) : 0, at = o, d = D;
+    D += rangeLen[i];                                              // (<= dstCap: knz_read_total)
+    if (left <= 0) continue;
+    int64_t k = B ? (std::upper_bound(B, B + nIndex + 1, o) - B) - 1 : o / blockSize;   // the block that holds byte o
+    for (; left > 0; k++) {
+      const int64_t b0 = B ? B[k] : k * blockSize, b1 = B ? B[k + 1] : b0 + blockSize;
+      const int64_t len = std::min<int64_t>(left, b1 - at);
+      all.push_back(KnzReadSeg{d, 0, 0, (int32_t)(at - b0), (int32_t)len, i});
+      blk.push_back((int32_t)k);
+      at += len; d += len; left -= len;
+    }
+  }
+  P.blocks = blk;
+  std::sort(P.blocks.begin(), P.blocks.end());
+  P.blocks.erase(std::unique(P.blocks.begin(), P.blocks.end()), P.blocks.end());
+  const int64_t nChunks = ((int64_t)P.blocks.size() + CH - 1) / CH;
+  P.first.assign((size_t)nChunks + 1, 0);
+  P.units.assign((size_t)nChunks, 0);
+  std::vector<int32_t> rank(all.size());                           // the block's place among the distinct blocks
+  for (size_t i = 0; i < all.size(); i++) {
+    rank[i] = (int32_t)(std::lower_bound(P.blocks.begin(), P.blocks.end(), blk[i]) - P.blocks.begin());
+    P.first[(size_t)(rank[i] / CH) + 1]++;
+  }
+  for (int64_t c = 0; c < nChunks; c++) P.first[(size_t)c + 1] += P.first[(size_t)c];
+  std::vector<int64_t> fill(P.first.begin(), P.first.end() - 1);
+  P.segs.resize(all.size());
+  for (size_t i = 0; i < all.size(); i++) {                        // a stable split by chunk: dst order stays inside every chunk
+    const int64_t c = rank[i] / CH;
+    KnzReadSeg s = all[i];
+    s.slot = rank[i] % CH;
+    s.unit0 = P.units[(size_t)c];
+    P.units[(size_t)c] += knz_read_units((dstPhase + s.dst) & 15, s.len);
+    P.segs[(size_t)fill[(size_t)c]++] = s;
+  }
+}
+// After chunk c has been decoded (res[j]: the result of its block j, rows of blockSize bytes): the length check of every block, the
+// segments cut to what their blocks hold (a failed block's to nothing; unit0 stays, the kernel skips the units that fall away), and
+// got[]: the bytes delivered, or the status of the first failing block a range touches, in block order.  got[] starts as zeros.
+static inline void knz_read_settle(KnzReadPlan& P, int64_t c, int CH, const int64_t* B, int32_t nIndex, int32_t blockSize, kz_block_result* res, int64_t* got) {
+  const int64_t b0 = c * CH, cnt = std::min<int64_t>(CH, (int64_t)P.blocks.size() - b0);
+  for (int64_t j = 0; j < cnt; j++) {
+    if (res[j].status) continue;
+    const int64_t want = knz_read_block_len(B, nIndex, blockSize, P.blocks[(size_t)(b0 + j)]);
+    if (res[j].length > blockSize) res[j].status = -KZ_ERR_PROCESS_BLOCK;
+    else if (want >= 0 && res[j].length != want) res[j].status = -KZ_ERR_INVALID_FILE;
+  }
+  for (int64_t i = P.first[(size_t)c]; i < P.first[(size_t)c + 1]; i++) {
+    KnzReadSeg& s = P.segs[(size_t)i];
+    const kz_block_result& r = res[s.slot];
+    s.len = r.status ? 0 : (int32_t)std::max<int64_t>(0, std::min<int64_t>(s.len, (int64_t)r.length - s.off));
+    if (got[s.range] < 0) continue;
+    if (r.status) got[s.range] = r.status; else got[s.range] += s.len;
+  }
 }

@@ -438,3 +438,67 @@ extern "C" int32_t kz_decode_indexed(kz_ctx* ctx, const uint8_t* src, int64_t n,
   }
   return 0;
 }
+
+// Byte-addressed read: many ranges [off, off + len) of the original data in one call.  The plan (kz_knz_host.h) names the distinct
+// covering blocks and the range x block segments, chunk by chunk; the steps are the indexed read's: every entry the plan uses is
+// checked against the stream before anything is decoded, then per chunk the prechecks, the decode into host rows, and a memcpy per
+// segment out of those rows.  kz_read_bytes_device (kz_stream_device.hip) is the same call on device memory.
+extern "C" int64_t kz_read_bytes(kz_ctx* ctx, const uint8_t* src, int64_t n, const int64_t* blockBitOff, const int64_t* blockBits, const int64_t* blockByteOff,
+                                 int32_t nIndex, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges, uint8_t* dst, int64_t dstCap, int64_t* got) {
+  if (!ctx) return -KZ_ERR_INVALID_PARAM;
+  { const int rc = knz_read_args(src, n, blockBitOff, blockBits, nIndex, rangeOff, rangeLen, nRanges, dst, dstCap, got); if (rc) return rc; }
+  KZ_HIP(hipSetDevice(ctx->device));
+  HostBitsIn bs{src, (uint64_t)n * 8, 0, false};
+  KnzHeader h;
+  { const int hrc = read_stream_header(bs, h, ctx->err, sizeof(ctx->err)); if (hrc) return hrc; }
+  const KnzPlan P = knz_plan(ctx, h, n, (int64_t)bs.pos);
+  const int32_t blockSize = h.blockSize;
+  if (knz_read_table(blockByteOff, nIndex, blockSize)) {
+    snprintf(ctx->err, sizeof(ctx->err), "kz_read_bytes: blockByteOff is not a table of block starts");
+    return -KZ_ERR_INVALID_PARAM;
+  }
+  const int64_t total = knz_read_total(rangeLen, nRanges, dstCap);
+  if (total < 0) { snprintf(ctx->err, sizeof(ctx->err), "kz_read_bytes: destination too small"); return total; }
+  if (nRanges == 0) return 0;
+  const int CH = knz_chunk_blocks(ctx, blockSize);
+  KnzReadPlan R;
+  knz_read_plan(blockByteOff, nIndex, blockSize, rangeOff, rangeLen, nRanges, CH, 0, R);
+  for (int32_t i = 0; i < nRanges; i++) got[i] = 0;
+  const int64_t nb = (int64_t)R.blocks.size();
+  if (nb == 0) return total;
+  for (int64_t i = 0; i < nb; i++) {
+    const int32_t k = R.blocks[(size_t)i];
+    if (!knz_check_entry(src, n, P.hdrEnd, blockBitOff[k], blockBits[k])) return indexed_mismatch(ctx, k);
+  }
+  ChecksumScope chk(ctx, h.chkKind);
+  const int cmax = (int)std::min<int64_t>(CH, nb);
+  std::unique_ptr<uint8_t[]> inbuf(new uint8_t[(size_t)P.iS * cmax]), rows(new uint8_t[(size_t)blockSize * cmax]);
+  std::vector<kz_block_result> res((size_t)cmax);
+  std::vector<int64_t> W((size_t)cmax), off((size_t)cmax);
+  for (int64_t b0 = 0, c = 0; b0 < nb; b0 += CH, c++) {
+    const int cnt = (int)std::min<int64_t>(CH, nb - b0);
+    for (int i = 0; i < cnt; i++) {
+      const int32_t k = R.blocks[(size_t)(b0 + i)];
+      off[i] = blockBitOff[k]; W[i] = blockBits[k];
+      HostBitsIn t = bs; t.pos = (uint64_t)off[i]; t.error = false;
+      const int rc = knz_check_block(t, (uint64_t)W[i], (uint64_t)off[i], t.nbits, P, false);   // (knz_check_entry saw the payload's end)
+      memset(&res[i], 0, sizeof(res[i]));
+      res[i].bits = W[i]; res[i].status = rc;
+    }
+    parallel_blocks(cnt, [&](int i) {
+      if (res[i].status) return;
+      HostBitsIn t = bs; t.pos = (uint64_t)off[i]; t.error = false; t.getBytes(inbuf.get() + (size_t)i * P.iS, (uint64_t)W[i]);
+    });
+    { const int rc = indexed_decode_runs(ctx, P, inbuf.get(), W.data(), cnt, rows.get(), blockSize, res.data(), KZ_MEM_HOST); if (rc) return rc; }
+    knz_read_settle(R, c, CH, blockByteOff, nIndex, blockSize, res.data(), got);
+    const int64_t s0 = R.first[(size_t)c], s1 = R.first[(size_t)c + 1];
+    parallel_blocks((int)std::min<int64_t>(s1 - s0, 64), [&](int q) {                     // the chunk's segments in up to 64 runs
+      const int64_t runs = std::min<int64_t>(s1 - s0, 64);
+      for (int64_t i = s0 + (s1 - s0) * q / runs; i < s0 + (s1 - s0) * (q + 1) / runs; i++) {
+        const KnzReadSeg& g = R.segs[(size_t)i];
+        if (g.len > 0) memcpy(dst + g.dst, rows.get() + (size_t)g.slot * blockSize + g.off, (size_t)g.len);
+      }
+    });
+  }
+  return total;
+}

@@ -797,3 +797,119 @@ extern "C" int64_t kz_knz_splice_device(kz_ctx* ctx, const uint8_t* d_src, const
   kz_ktimer_flush(ctx);
   return (P.endBit + 7) >> 3;
 }
+
+
+// =================================================================================================
+// byte-addressed reads: many ranges [off, off + len) of the original data in one call, stream and destination in HBM
+// (kz_read_bytes_device).  The plan is the host form's (kz_knz_host.h: the distinct covering blocks, and the range x block segments
+// grouped by chunk); the indexed read's steps do the rest: every index entry the plan uses is checked against the stream
+// (k_knz_check) before anything is unpacked, then per chunk of blocks the prechecks, the unpack and the decode into staging rows,
+// and one k_knz_read launch that copies the chunk's segments from the rows to their places in d_dst.
+namespace {
+const int KNZ_READ_LAUNCH = 1 << 20;                               // segments per k_knz_read launch: bounds the table at 32 MiB
+}
+extern "C" int64_t kz_read_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, const int64_t* blockBitOff, const int64_t* blockBits, const int64_t* blockByteOff,
+                                        int32_t nIndex, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges, uint8_t* d_dst, int64_t dstCap, int64_t* got) {
+  if (!ctx) return -KZ_ERR_INVALID_PARAM;
+  { const int rc = knz_read_args(d_src, n, blockBitOff, blockBits, nIndex, rangeOff, rangeLen, nRanges, d_dst, dstCap, got); if (rc) return rc; }
+  KZ_HIP(hipSetDevice(ctx->device));
+  uint8_t hdr[32]; HostBitsIn bs;
+  { const int rc = knz_open(ctx, d_src, n, hdr, bs); if (rc) return rc; }
+  KnzHeader h;
+  { const int hrc = read_stream_header(bs, h, ctx->err, sizeof(ctx->err)); if (hrc) return hrc; }
+  const KnzPlan P = knz_plan(ctx, h, n, (int64_t)bs.pos);
+  const int32_t blockSize = h.blockSize;
+  if (knz_read_table(blockByteOff, nIndex, blockSize)) {
+    snprintf(ctx->err, sizeof(ctx->err), "kz_read_bytes_device: blockByteOff is not a table of block starts");
+    return -KZ_ERR_INVALID_PARAM;
+  }
+  const int64_t total = knz_read_total(rangeLen, nRanges, dstCap);
+  if (total < 0) { snprintf(ctx->err, sizeof(ctx->err), "kz_read_bytes_device: destination too small"); return total; }
+  if (nRanges == 0) return 0;
+  const int CH = knz_chunk_blocks(ctx, blockSize);
+  KnzReadPlan R;
+  knz_read_plan(blockByteOff, nIndex, blockSize, rangeOff, rangeLen, nRanges, CH, (int)((uintptr_t)d_dst & 15), R);
+  for (int32_t i = 0; i < nRanges; i++) got[i] = 0;
+  const int64_t nb = (int64_t)R.blocks.size();
+  if (nb == 0) return total;
+  ChecksumScope chk(ctx, h.chkKind);
+  const int cmax = (int)std::min<int64_t>(CH, nb);
+  int64_t segMax = 0;
+  for (size_t c = 0; c + 1 < R.first.size(); c++) segMax = std::max(segMax, std::min<int64_t>(R.first[c + 1] - R.first[c], KNZ_READ_LAUNCH));
+  // the chunk's tables, pinned and in HBM: 64 spare bytes, then off[cmax], bits[cmax], hdr[cmax], bad[cmax]; the segment table of a
+  // launch (32 bytes per segment) takes their place when the chunk has been decoded
+  { const int rc = knz_tables(ctx, std::max((size_t)cmax * 32, (size_t)segMax * sizeof(KnzReadSeg))); if (rc) return rc; }
+  const KnzTable T(ctx, cmax);
+  // ---- every entry the plan uses against the stream, before anything is unpacked ----
+  std::vector<uint64_t> hdrs((size_t)nb);
+  for (int64_t b0 = 0; b0 < nb; b0 += CH) {
+    const int cnt = (int)std::min<int64_t>(CH, nb - b0);
+    for (int i = 0; i < cnt; i++) { T.off()[i] = blockBitOff[R.blocks[(size_t)(b0 + i)]]; T.bits()[i] = blockBits[R.blocks[(size_t)(b0 + i)]]; }
+    KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+    KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+    { const int rc = kz_knz_check(ctx, d_src, n, P.hdrEnd, T.d_off(), T.d_bits(), cnt, T.d_hdr(), T.d_bad()); if (rc) return rc; }
+    KZ_HIP(hipMemcpyAsync(T.hdr(), T.d_hdr(), (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(hipMemcpyAsync(T.bad(), T.d_bad(), (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+    kz_ktimer_flush(ctx);
+    for (int i = 0; i < cnt; i++) {
+      if (T.bad()[i]) return indexed_mismatch(ctx, R.blocks[(size_t)(b0 + i)]);
+      hdrs[(size_t)(b0 + i)] = T.hdr()[i];
+    }
+  }
+  // ---- chunks of blocks, ascending: prechecks, unpack, decode into staging rows blockSize apart, copy the chunk's segments ----
+  const uint64_t nbits = (uint64_t)n * 8;
+  std::vector<kz_block_result> res((size_t)cmax);
+  std::vector<int64_t> W((size_t)cmax);
+  {
+    int rc = kz_stage_reserve(ctx, ctx->devIn[0], (size_t)cmax * P.iS, false);
+    if (!rc) rc = kz_stage_reserve(ctx, ctx->devOut[0], (size_t)cmax * (size_t)blockSize, false);
+    if (rc) return rc;
+  }
+  for (int64_t b0 = 0, c = 0; b0 < nb; b0 += CH, c++) {
+    const int cnt = (int)std::min<int64_t>(CH, nb - b0);
+    int64_t maxBytes = 0;
+    for (int i = 0; i < cnt; i++) {
+      const int32_t k = R.blocks[(size_t)(b0 + i)];
+      W[i] = blockBits[k];
+      const int rc = knz_check_walked(hdrs[(size_t)(b0 + i)], (uint64_t)W[i], (uint64_t)blockBitOff[k], nbits, P);
+      memset(&res[i], 0, sizeof(res[i]));
+      res[i].bits = W[i]; res[i].status = rc;
+      T.off()[i] = blockBitOff[k];
+      T.bits()[i] = rc ? 0 : W[i];                                  // a row of no bits: nothing of it is unpacked
+      if (!rc) maxBytes = std::max<int64_t>(maxBytes, (W[i] + 7) >> 3);
+    }
+    if (maxBytes > 0) {
+      KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+      KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+      { const int rc = kz_knz_unpack(ctx, d_src, n, T.d_off(), T.d_bits(), cnt, maxBytes, ctx->devIn[0].p, P.iS); if (rc) return rc; }
+      { const int rc = indexed_decode_runs(ctx, P, ctx->devIn[0].p, W.data(), cnt, ctx->devOut[0].p, blockSize, res.data(), KZ_MEM_DEVICE); if (rc) return rc; }
+      KZ_HIP(kz_stream_sync(ctx, ctx->stream));                    // the pinned table becomes the segments'
+      kz_ktimer_flush(ctx);
+    }
+    knz_read_settle(R, c, CH, blockByteOff, nIndex, blockSize, res.data(), got);
+    for (int64_t s0 = R.first[(size_t)c]; s0 < R.first[(size_t)c + 1]; s0 += KNZ_READ_LAUNCH) {
+      const int ns = (int)std::min<int64_t>(KNZ_READ_LAUNCH, R.first[(size_t)c + 1] - s0);
+      const int64_t uEnd = s0 + ns < R.first[(size_t)c + 1] ? R.segs[(size_t)(s0 + ns)].unit0 : R.units[(size_t)c];
+      if (ctx->sw.readScatter) {                                   // the yardstick: the same segments through the ragged copy, a workgroup column each
+        KnzCopy* t = (KnzCopy*)(ctx->knzPin.p + 64);
+        int64_t maxLen = 0;
+        for (int i = 0; i < ns; i++) {
+          const KnzReadSeg& g = R.segs[(size_t)(s0 + i)];
+          t[i] = KnzCopy{(int64_t)g.slot * blockSize + g.off, g.dst, g.len};
+          maxLen = std::max<int64_t>(maxLen, g.len);
+        }
+        KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + 64, t, (size_t)ns * sizeof(KnzCopy), hipMemcpyHostToDevice, ctx->stream));
+        { const int rc = kz_knz_scatter(ctx, ctx->devOut[0].p, (const KnzCopy*)(ctx->knzAux.p + 64), ns, maxLen, d_dst); if (rc) return rc; }
+      } else {
+        memcpy(ctx->knzPin.p + 64, &R.segs[(size_t)s0], (size_t)ns * sizeof(KnzReadSeg));
+        KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + 64, ctx->knzPin.p + 64, (size_t)ns * sizeof(KnzReadSeg), hipMemcpyHostToDevice, ctx->stream));
+        const int rc = kz_knz_read(ctx, ctx->devOut[0].p, blockSize, blockSize, (const KnzReadSeg*)(ctx->knzAux.p + 64), ns, d_dst, R.segs[(size_t)s0].unit0, uEnd - R.segs[(size_t)s0].unit0);
+        if (rc) return rc;
+      }
+      KZ_HIP(kz_stream_sync(ctx, ctx->stream));                    // the pinned table is the next launch's
+      kz_ktimer_flush(ctx);
+    }
+  }
+  return total;
+}
