@@ -478,6 +478,84 @@ int64_t kz_read_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n,
                              const int64_t* rangeOff /* host */, const int64_t* rangeLen /* host */, int32_t nRanges,
                              uint8_t* d_dst, int64_t dstCap, int64_t* got /* host, out */);
 
+/* ---- byte-addressed writes: many ranges of the original data replaced in one call ------------------
+ * "Replace bytes [rangeOff[i], rangeOff[i] + rangeLen[i]) of the original data by these new bytes, for nRanges ranges at once, and
+ * give me the new stream", on host memory and on device memory.  The result is a NEW stream in a separate buffer, as with the splice:
+ * every block that no range touches is copied bit for bit and not decoded, every touched block is decoded once, patched and encoded
+ * once with the chain of the stream's own header.  The index (blockBitOff, blockBits, nIndex) and the table blockByteOff mean what
+ * they mean for kz_read_bytes: the index is the WHOLE stream's, block k holds the original bytes [B[k], B[k + 1]), B = blockByteOff
+ * or, with NULL, B[k] = k * blockSize with only the last block allowed to be short.
+ *
+ * The new bytes are packed by length, like the reads' destination: range i brings data[D[i] .. D[i] + rangeLen[i]), D[i] = the sum
+ * of rangeLen[j] for j < i, and dataLen must equal D[nRanges].  Ranges may come in any order, overlap and repeat; the result is what
+ * applying them one after the other in argument order gives: THE LATER RANGE WINS.  Zero-length ranges are legal and touch nothing.
+ * A write never changes the length of the data or the number of blocks: a range must lie wholly inside the data, and no sum may
+ * overflow (a range's end is formed only after rangeLen[i] <= end - rangeOff[i] has been seen).  A range that ends behind B[nIndex]
+ * (without a table: behind nIndex * blockSize) is refused before anything but the stream header is read; without a table, one that
+ * ends behind the real end of a short last block is refused with the same code once that block has been decoded.  Appending stays
+ * splice_replace at the block count (kz_knz_splice).
+ *
+ * A block that some SURVIVING byte touches is "touched" (a range buried whole under later ones touches nothing).  If the surviving
+ * new bytes cover all of [B[k], B[k + 1]) and a table gave that length, block k is neither decoded nor checked and its index entry
+ * is not looked at: overwriting a damaged block with a table repairs the stream.  Without a table every touched block is decoded
+ * (the last one to learn its length).  Every other touched block gets the indexed reads' check of its entry, the block-header
+ * precheck, the unpack and the decode exactly as in kz_read_bytes, and its decoded length must be B[k + 1] - B[k].  Untouched blocks
+ * are copied verbatim after the splice's check of a piece against its source, which gives memory safety only: a damaged untouched
+ * block stays damaged and does not fail the call.
+ *
+ * Transform word, entropy id, block size and checksum kind come from the stream header; the context's checksum and block-size
+ * settings are the stream's for the call and restored after it.  Every chain kz_compress_device takes is taken (TEXT / UTF heads
+ * included), and block checksums are computed from the patched bytes.  The result is, byte for byte, kz_knz_assemble of the header's
+ * parameters and its own inputSize, the old payload bits of untouched blocks, and what kz_encode_blocks gives for the patched bytes
+ * of touched ones.  newBitOff / newBits (both or neither NULL, nIndex entries each) receive the new stream's index: what
+ * kz_knz_index of the result returns.  kz_write_bytes_bound returns a dstCap that always suffices: the longest stream header, per
+ * block 5 + 34 prefix bits and max(blockBits[k], 8 * kz_max_block_stream_bytes(blockSize)) payload bits, the end marker, in bytes;
+ * it uses host arrays only and needs no context.
+ *
+ *   addresses   src / d_src, data / d_data and dst / d_dst: any address, any alignment; dst overlaps neither of the others.
+ *               blockBitOff, blockBits, blockByteOff, rangeOff, rangeLen, newBitOff and newBits are host arrays in both calls.
+ *   read        nothing outside src[0 .. n) and data[0 .. dataLen); of src the stream header, the 39 bits in front of every used
+ *               entry, the payloads of the decoded blocks and of the kept ones.
+ *   written     nothing outside dst[0 .. dstCap).  dst is untouched by every refusal that is decided before the first block is
+ *               decoded (arguments, header, table, ranges behind the data, index entries); after that dst[0 .. dstCap) is unspecified
+ *               on failure.  On success dst[0 .. size) is the stream, the spare bits of its last byte zero; dst[size .. dstCap) is
+ *               untouched by the host form and unspecified for the device form.  dst need not be zeroed.
+ *   returns     the new stream's size, or a negative code.  The call is all or nothing; there is no per-range status.  In this
+ *               order: -KZ_ERR_INVALID_PARAM for bad arguments (null pointers, negative sizes, dataLen != D[nRanges], only one of
+ *               newBitOff / newBits); the stream header's code as from kz_decompress; -KZ_ERR_INVALID_PARAM for a bad table and for
+ *               a range behind the data (kz_last_error: "range %d ends behind the data"); -KZ_ERR_INVALID_PARAM for the first used
+ *               index entry, in block order, that does not match the stream ("index entry %d does not match the stream"); a
+ *               touched block's own fault (precheck, staging bound, decode, checksum, length) as that block's code, of several
+ *               failing blocks the first in block order ("block %d: ..."); -KZ_ERR_WRITE_FILE when the stream outgrows dstCap,
+ *               decided from the bit arithmetic before the chunk that would cross it is written; -KZ_ERR_DEVICE.  nRanges == 0, or a
+ *               call in which no byte survives, returns a bit-exact copy of the stream (header, all blocks, end marker) for a
+ *               stream whose header is the one this library writes for its parameters.
+ *   chunks      the touched blocks go in ascending order in chunks of kz_compress_device's size (KZ_STREAM_CHUNK=<blocks>
+ *               overrides) through staging rows blockSize apart: unpack and decode, the patch (memcpy on the host; on the device
+ *               k_knz_write, one launch per 2^20 segments, which spreads the 16-byte units of the ROW side of all its segments over
+ *               the lanes: a 64-byte record costs 4 or 5 lanes, not a workgroup), one batched encode, then one copy in k_knz_splice's
+ *               manner of every kept block since the previous chunk's last touched block and of the chunk's recoded blocks, in
+ *               launches of at most one chunk's pieces; a chunk's first bit is wherever the previous one's last bit ended.  After
+ *               the last chunk come the kept tail and the end marker.  Segments are disjoint, so no order between lanes, launches
+ *               or segments decides anything.  Tables live in the context's grow-only buffers (32 bytes per segment of one launch,
+ *               48 per piece of one launch); row staging is bounded by one chunk.  Host memory proportional to nRanges (about 60
+ *               bytes per range and per segment) and to the touched blocks (8 bytes each) is used besides.
+ *   cost        the touched blocks' decode and encode, and a bit copy of the rest; nothing that is decoded grows with the
+ *               untouched blocks.
+ *   stream      the calls are synchronous and run on the context's stream.
+ */
+int64_t kz_write_bytes_bound(const int64_t* blockBits, int32_t nIndex, int32_t blockSize);
+int64_t kz_write_bytes(kz_ctx* ctx, const uint8_t* src, int64_t n,
+                       const int64_t* blockBitOff, const int64_t* blockBits, const int64_t* blockByteOff /* NULL or nIndex + 1 entries */, int32_t nIndex,
+                       const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges,
+                       const uint8_t* data, int64_t dataLen,
+                       uint8_t* dst, int64_t dstCap, int64_t* newBitOff, int64_t* newBits /* nIndex entries each, both or neither NULL */);
+int64_t kz_write_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n,
+                              const int64_t* blockBitOff /* host */, const int64_t* blockBits /* host */, const int64_t* blockByteOff /* host: NULL or nIndex + 1 entries */, int32_t nIndex,
+                              const int64_t* rangeOff /* host */, const int64_t* rangeLen /* host */, int32_t nRanges,
+                              const uint8_t* d_data, int64_t dataLen,
+                              uint8_t* d_dst, int64_t dstCap, int64_t* newBitOff /* host, out */, int64_t* newBits /* host, out */);
+
 /* ---- splice: a new .knz stream out of blocks of existing ones, without recoding -------------------
  * Blocks are independent of one another, and a stream is its header, then per block 5 + lw prefix bits and W payload bits, then the
  * end marker (:1024-1035, :483-493): a stream made of blocks taken from existing streams is a bit-granular copy.  One call joins the

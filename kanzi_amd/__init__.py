@@ -123,6 +123,9 @@ def load_library():
         "kz_decode_indexed_device": (c.c_int32, [vp, u8p, c.c_int64, i64p, i64p, c.c_int32, u8p, c.c_int64, vp]),
         "kz_read_bytes": (c.c_int64, [vp, u8p, c.c_int64, i64p, i64p, i64p, c.c_int32, i64p, i64p, c.c_int32, u8p, c.c_int64, i64p]),
         "kz_read_bytes_device": (c.c_int64, [vp, u8p, c.c_int64, i64p, i64p, i64p, c.c_int32, i64p, i64p, c.c_int32, u8p, c.c_int64, i64p]),
+        "kz_write_bytes_bound": (c.c_int64, [i64p, c.c_int32, c.c_int32]),
+        "kz_write_bytes": (c.c_int64, [vp, u8p, c.c_int64, i64p, i64p, i64p, c.c_int32, i64p, i64p, c.c_int32, u8p, c.c_int64, u8p, c.c_int64, i64p, i64p]),
+        "kz_write_bytes_device": (c.c_int64, [vp, u8p, c.c_int64, i64p, i64p, i64p, c.c_int32, i64p, i64p, c.c_int32, u8p, c.c_int64, u8p, c.c_int64, i64p, i64p]),
         "kz_knz_splice_bound": (c.c_int64, [i64p, c.c_int32]),
         "kz_knz_splice": (c.c_int64, [u8p, i64p, i64p, c.c_int32, i32p, i64p, i64p, c.c_int32, c.c_int64, u8p, c.c_int64]),
         "kz_knz_splice_device": (c.c_int64, [vp, u8p, i64p, i64p, c.c_int32, i32p, i64p, i64p, c.c_int32, c.c_int64, u8p, c.c_int64]),
@@ -157,6 +160,7 @@ ABI_SYMBOLS = ["kz_abi_version", "kz_ctx_create", "kz_ctx_destroy", "kz_last_err
                "kz_compress_many_bound", "kz_compress_many_device", "kz_decompress_many_device",
                "kz_decompress_range", "kz_decompress_range_device", "kz_decode_indexed", "kz_decode_indexed_device",
                "kz_read_bytes", "kz_read_bytes_device",
+               "kz_write_bytes_bound", "kz_write_bytes", "kz_write_bytes_device",
                "kz_knz_splice_bound", "kz_knz_splice", "kz_knz_splice_device",
                "kz_set_timing", "kz_get_stage_count", "kz_get_stage_ms", "kz_get_stage_alg_bytes", "kz_reset_timing",
                "kz_set_kernel_timing", "kz_get_kernel_count", "kz_get_kernel_name", "kz_get_kernel_ms", "kz_get_kernel_max_ms",
@@ -1105,6 +1109,50 @@ def read_bytes_device(ctx, src, n, index, offsets, sizes, dst, cap, byte_offsets
     return [int(g) for g in got[:len(ro)]]
 
 
+# ---- byte-addressed writes: many ranges of the original data replaced in one call (kz_write_bytes / kz_write_bytes_device) ----
+def write_bytes_bound(index_bits, block_size):
+    """kz_write_bytes_bound: a capacity that suffices for any write to a stream whose blocks have `index_bits` bits each."""
+    b = np.ascontiguousarray(index_bits, dtype=np.int64)
+    rc = int(load_library().kz_write_bytes_bound(b.ctypes.data if len(b) else None, len(b), int(block_size)))
+    if rc < 0:
+        raise KanziError(-rc, "write_bytes_bound")
+    return rc
+
+
+def _write_arrays(index, offsets, sizes, byte_offsets):
+    off, w, tab, ro, rl, _ = _read_arrays(index, offsets, sizes, byte_offsets)
+    new_off, new_w = np.zeros(max(len(off), 1), dtype=np.int64), np.zeros(max(len(off), 1), dtype=np.int64)
+    return off, w, tab, ro, rl, new_off, new_w
+
+
+def write_bytes(ctx, data, index, offsets, payloads, byte_offsets=None):
+    """kz_write_bytes: the .knz bytes `data` with bytes [offsets[i], offsets[i] + len(payloads[i])) of its original data replaced by
+    payloads[i], for all i in one call; where ranges overlap the later one wins -> (new stream, new index as knz_index names its
+    blocks).  index: knz_index(data) or its "blocks"; byte_offsets: as for read_bytes.  Untouched blocks are copied bit for bit,
+    touched ones are decoded, patched and encoded once; the data keeps its length."""
+    data = bytes(data)
+    payloads = [bytes(p) for p in payloads]
+    off, w, tab, ro, rl, new_off, new_w = _write_arrays(index, offsets, [len(p) for p in payloads], byte_offsets)
+    src = np.frombuffer(data + b"\0" * 16, dtype=np.uint8)
+    new = np.frombuffer(b"".join(payloads) + b"\0", dtype=np.uint8)
+    cap = write_bytes_bound(np.clip(w, 0, (1 << 34) - 1), knz_index(data)["blockSize"])
+    dst = np.zeros(max(cap, 1), dtype=np.uint8)
+    rc = ctx.check(ctx.lib.kz_write_bytes(ctx.h, src.ctypes.data, len(data), _arg(off), _arg(w), None if tab is None else tab.ctypes.data, len(off),
+                                          _arg(ro), _arg(rl), len(ro), new.ctypes.data, len(new) - 1, dst.ctypes.data, cap, new_off.ctypes.data, new_w.ctypes.data))
+    return dst[:rc].tobytes(), [(int(o), int(b)) for o, b in zip(new_off[:len(off)], new_w[:len(off)])]
+
+
+def write_bytes_device(ctx, src, n, index, offsets, sizes, data, dst, cap, byte_offsets=None):
+    """kz_write_bytes_device: the same with the stream at device address `src` (n bytes), range i's new bytes at device address
+    data + sum(sizes[:i]) and the new stream written at device address `dst` (capacity `cap`; write_bytes_bound suffices)
+    -> (the new stream's size, new index)."""
+    off, w, tab, ro, rl, new_off, new_w = _write_arrays(index, offsets, sizes, byte_offsets)
+    rc = ctx.check(ctx.lib.kz_write_bytes_device(ctx.h, _ptr(src), int(n), _arg(off), _arg(w), None if tab is None else tab.ctypes.data, len(off),
+                                                 _arg(ro), _arg(rl), len(ro), _ptr(data), int(rl.sum()) if len(rl) else 0, _ptr(dst), int(cap),
+                                                 new_off.ctypes.data, new_w.ctypes.data))
+    return int(rc), [(int(o), int(b)) for o, b in zip(new_off[:len(off)], new_w[:len(off)])]
+
+
 class KnzReader:
     """Random access to a .knz stream held as bytes or as a torch.uint8 device tensor: the index is built once (knz_index /
     knz_index_device, the one serial walk), every read after that goes through the indexed call and costs the same wherever its
@@ -1203,6 +1251,29 @@ class KnzReader:
             res.append(out[at:at + g])
             at += s
         return res
+
+    def write_many(self, offsets, payloads):
+        """the stream with bytes [offsets[i], offsets[i] + len(payloads[i])) of its original data replaced by payloads[i] (bytes, or
+        torch.uint8 tensors for a device stream), in one byte-addressed call (write_bytes / write_bytes_device); where ranges
+        overlap the later one wins -> a new KnzReader on the new stream, with the same byte_offsets.  This reader is unchanged."""
+        offsets = [int(o) for o in offsets]
+        if len(offsets) != len(payloads):
+            raise ValueError("offsets and payloads differ in length")
+        if any(o < 0 for o in offsets):
+            raise ValueError("offset must not be negative")
+        if not self.device:
+            new, _ = write_bytes(self.ctx, self.src, self.blocks, offsets, payloads, self.byte_offsets)
+            return KnzReader(self.ctx, new, self.byte_offsets)
+        import torch
+        dev = self.src.device
+        parts = [_byte_view(p).to(dev) if isinstance(p, torch.Tensor) else torch.from_numpy(np.frombuffer(bytes(p), dtype=np.uint8).copy()).to(dev) for p in payloads]
+        sizes = [int(p.numel()) for p in parts]
+        data = torch.cat(parts) if sum(sizes) else torch.zeros(1, dtype=torch.uint8, device=dev)
+        cap = write_bytes_bound([b[1] for b in self.blocks], self.block_size)
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()                 # the call runs on the context's own stream
+        size, _ = write_bytes_device(self.ctx, self.src.data_ptr(), self.src.numel(), self.blocks, offsets, sizes, data.data_ptr(), out.data_ptr(), cap, self.byte_offsets)
+        return KnzReader(self.ctx, out[:size], self.byte_offsets)
 
 
 # ---- splice: a new .knz stream out of blocks of existing ones, without recoding (kz_knz_splice / kz_knz_splice_device) ----

@@ -69,6 +69,7 @@ void kz_switches_read(kz_switches& s) {
   s.streamChunk = num("KZ_STREAM_CHUNK", 0);
   s.streamSerial = flag("KZ_STREAM_SERIAL");
   s.readScatter = flag("KZ_READ_SCATTER");
+  s.writeGather = flag("KZ_WRITE_GATHER");
   s.bwtTrie = num("KZ_BWT_TRIE", -1); s.bwtTrieWin = num("KZ_BWT_TRIEWIN", -1); s.bwtBuckets = num("KZ_BWT_BUCKETS", -1);
   s.bwtDmax = num("KZ_BWT_DMAX", -1); s.bwtRetire = num("KZ_BWT_RETIRE", -1); s.bwtLazyRank = num("KZ_BWT_LAZYRANK", -1);
   s.bwtTrace = flag("KZ_BWT_TRACE");

@@ -49,7 +49,7 @@
   X(KID_EXE_EMIT, "k_exe_emit") X(KID_KNZ_PACK, "k_knz_pack") X(KID_KNZ_WALK, "k_knz_walk") X(KID_KNZ_UNPACK, "k_knz_unpack") \
   X(KID_KNZ_CHECK, "k_knz_check") X(KID_KNZ_GATHER, "k_knz_gather") X(KID_KNZ_PACK_MANY, "k_knz_pack_many") X(KID_KNZ_HEADS, "k_knz_heads") \
   X(KID_KNZ_WALK_MANY, "k_knz_walk_many") X(KID_KNZ_UNPACK_MANY, "k_knz_unpack_many") X(KID_KNZ_SCATTER, "k_knz_scatter") \
-  X(KID_KNZ_CHECK_MANY, "k_knz_check_many") X(KID_KNZ_SPLICE, "k_knz_splice") X(KID_KNZ_READ, "k_knz_read")
+  X(KID_KNZ_CHECK_MANY, "k_knz_check_many") X(KID_KNZ_SPLICE, "k_knz_splice") X(KID_KNZ_READ, "k_knz_read") X(KID_KNZ_WRITE, "k_knz_write")
 #define KZ_KERNEL_ENUM(id, name) id,
 #define KZ_KERNEL_NAME(id, name) name,
 enum KzKernelId { KZ_KERNELS(KZ_KERNEL_ENUM) KID_COUNT };
@@ -78,6 +78,7 @@ struct kz_switches {
   int streamChunk = 0;           // KZ_STREAM_CHUNK (0: default)
   int streamSerial = 0;          // KZ_STREAM_SERIAL
   int readScatter = 0;           // KZ_READ_SCATTER: kz_read_bytes_device copies its segments with k_knz_scatter (tools/knz_read_probe.py's yardstick)
+  int writeGather = 0;           // KZ_WRITE_GATHER: kz_write_bytes_device patches its rows with k_knz_gather (tools/knz_write_probe.py's yardstick)
   int bwtTrie = -1, bwtTrieWin = -1, bwtBuckets = -1, bwtDmax = -1, bwtRetire = -1;   // KZ_BWT_TRIE / _TRIEWIN / _BUCKETS / _DMAX / _RETIRE (-1 unset)
   int bwtLazyRank = -1;         // KZ_BWT_LAZYRANK=0: round 0 stores every rank (A/B; see k_tr_sort)
   int bwtTrace = 0;              // KZ_BWT_TRACE
@@ -341,6 +342,10 @@ int kz_knz_splice_launch(kz_ctx*, const uint8_t* d_src, const KnzPiece* d_pc, in
 // to their places in d_dst; the launch owns the destination units [unitBase, unitBase + units), d_seg[0].unit0 == unitBase
 struct KnzReadSeg;
 int kz_knz_read(kz_ctx*, const uint8_t* d_rows, int64_t stride, int rowLen, const KnzReadSeg* d_seg, int ns, uint8_t* d_dst, int64_t unitBase, int64_t units);
+// byte-addressed writes (kz_write_bytes_device): ns segments (kz_knz_host.h) of d_data[0 .. dataLen) to their places in rows `stride`
+// apart; the launch owns the row units [unitBase, unitBase + units), d_seg[0].unit0 == unitBase
+struct KnzWriteSeg;
+int kz_knz_write(kz_ctx*, const uint8_t* d_data, int64_t dataLen, const KnzWriteSeg* d_seg, int ns, uint8_t* d_rows, int64_t stride, int64_t unitBase, int64_t units);
 
 // timing helpers
 void kz_stage_begin(kz_ctx*, hipEvent_t* e0);

@@ -4,7 +4,8 @@
 // the indexed reads; behind them the same steps for many streams in one launch (a table entry per segment, slot or row, each with
 // its own bounds: kz_compress_many_device / kz_decompress_many_device), and the splice: the pack over pieces whose payload bits lie
 // where they are in their source streams, with the check of every piece against its own source in front of it (kz_knz_splice_device);
-// and the copy of the byte-addressed reads: many (range x block) segments of decoded rows to their places in one launch (k_knz_read).
+// and the copy of the byte-addressed reads: many (range x block) segments of decoded rows to their places in one launch (k_knz_read),
+// with its mirror image for the byte-addressed writes: segments of new bytes into decoded rows (k_knz_write).
 // The callers (kz_compress_device / kz_decompress_device / kz_decompress_range_device /
 // kz_decode_indexed_device / kz_knz_assemble_device / kz_knz_index_device, kz_stream_device.hip) do the bit-offset arithmetic, the stream
 // header and the block-header prechecks on the host; no payload byte leaves the device.
@@ -344,7 +345,7 @@ __global__ void __launch_bounds__(256) k_knz_scatter(const u8* __restrict__ rows
 // unit0 was summed (knz_read_settle) has units with nothing in them: they are skipped.
 // The 64 units of a wave lie side by side and in one segment or a few neighbours: the wave searches once for its first and once for
 // its last unit with wave-uniform arguments, a lane then only between the two (k_knz_splice's scheme).
-__device__ __forceinline__ int knz_read_find(const KnzReadSeg* __restrict__ seg, int lo, int hi, int64_t u) {   // the last j in lo .. hi with unit0 <= u (seg[lo]'s is)
+template <class T> __device__ __forceinline__ int knz_read_find(const T* __restrict__ seg, int lo, int hi, int64_t u) {   // the last j in lo .. hi with unit0 <= u (seg[lo]'s is)
   int a = lo + 1, b = hi + 1;
   while (a < b) { const int m = (a + b) >> 1; if (seg[m].unit0 <= u) a = m + 1; else b = m; }
   return a - 1;
@@ -370,6 +371,40 @@ __global__ void __launch_bounds__(256) k_knz_read(const u8* __restrict__ rows, i
       const u8* p = s + lo;
       const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
       if (al >= row && al + knz_window(p, 0) <= row + rowLen) { *(uint4*)(d + lo) = knz_load128(p, 0); continue; }
+    }
+    for (int64_t b = lo; b < hi; b++) d[b] = s[b];
+  }
+}
+
+// ---- write: segments of the caller's new bytes -> their places in decoded rows (kz_write_bytes_device) ------------------------------
+// k_knz_read's mirror image.  Segment j (kz_knz_host.h: KnzWriteSeg) is seg[j].len bytes from data + seg[j].src (any alignment) to
+// byte seg[j].off of the row rows + seg[j].slot * stride (rows 16-byte aligned, stride a multiple of 16).  The launch's work is the
+// 16-byte aligned units of the ROW side of all its segments, one segment after the other (seg[j].unit0, the launch owns
+// [unitBase, unitBase + units), seg[0].unit0 == unitBase); a lane finds its segment with the read's wave-narrowed search.  A unit
+// wholly inside its segment is one wide store of aligned 32-bit loads, if that load window stays inside data[0 .. dataLen); any other
+// unit goes bytewise, the segment's own bytes only.  The plan made the segments disjoint (the later range has already won there), so
+// every byte of a row has one writer and no order between lanes, launches or segments is needed; bytes of a row that no segment
+// covers keep what the decode left in them.
+__global__ void __launch_bounds__(256) k_knz_write(const u8* __restrict__ data, int64_t dataLen, const KnzWriteSeg* __restrict__ seg, int ns,
+                                                   u8* __restrict__ rows, int64_t stride, int64_t unitBase, int64_t units) {
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < units; v += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t u = unitBase + v;
+    const int64_t u0 = knz_first_lane(u);                                             // the wave's units: at most 64 in a row from its first lane's
+    const int jlo = knz_read_find(seg, 0, ns - 1, u0);
+    int jhi = jlo;                                                                    // (every segment has a unit: 63 units on are at most 63 segments on)
+    if (jlo + 1 < ns && seg[jlo + 1].unit0 <= u0 + 63) jhi = knz_read_find(seg, jlo + 1, jlo + 63 < ns - 1 ? jlo + 63 : ns - 1, u0 + 63);
+    const int j = knz_read_find(seg, jlo, jhi, u);
+    const KnzWriteSeg g = seg[j];
+    u8* d = rows + (int64_t)g.slot * stride + g.off;
+    const uintptr_t A0 = (uintptr_t)d & ~(uintptr_t)15;
+    const int64_t ub = (int64_t)(A0 - (uintptr_t)d) + ((u - g.unit0) << 4);           // the unit's first byte as an index into the segment (may be < 0)
+    const int64_t lo = ub < 0 ? 0 : ub, hi = ub + 16 > g.len ? g.len : ub + 16;
+    if (lo >= hi) continue;
+    const u8* s = data + g.src;
+    if (hi - lo == 16) {
+      const u8* p = s + lo;
+      const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
+      if (al >= data && al + knz_window(p, 0) <= data + dataLen) { *(uint4*)(d + lo) = knz_load128(p, 0); continue; }
     }
     for (int64_t b = lo; b < hi; b++) d[b] = s[b];
   }
@@ -533,6 +568,12 @@ int kz_knz_unpack_many(kz_ctx* ctx, const uint8_t* d_src, const KnzRow* d_t, int
 int kz_knz_read(kz_ctx* ctx, const uint8_t* d_rows, int64_t stride, int rowLen, const KnzReadSeg* d_seg, int ns, uint8_t* d_dst, int64_t unitBase, int64_t units) {
   if (ns <= 0 || units <= 0) return 0;
   KZ_LAUNCH(ctx, KID_KNZ_READ, k_knz_read, knz_pack_grid(units), dim3(256), d_rows, stride, rowLen, d_seg, ns, d_dst, unitBase, units);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_write(kz_ctx* ctx, const uint8_t* d_data, int64_t dataLen, const KnzWriteSeg* d_seg, int ns, uint8_t* d_rows, int64_t stride, int64_t unitBase, int64_t units) {
+  if (ns <= 0 || units <= 0) return 0;
+  KZ_LAUNCH(ctx, KID_KNZ_WRITE, k_knz_write, knz_pack_grid(units), dim3(256), d_data, dataLen, d_seg, ns, d_rows, stride, unitBase, units);
   KZ_HIP(hipGetLastError());
   return 0;
 }

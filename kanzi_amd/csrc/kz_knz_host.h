@@ -1,8 +1,8 @@
 // kz_knz_host.h -- the host-only core of the .knz container: bit I/O, the stream header, the chain of block length prefixes, the
-// block-header precheck and the check of an index entry, the plan of a splice and its host copy, the plan of a byte-addressed read,
-// and the container's rules that every call must share, each written once.
+// block-header precheck and the check of an index entry, the plan of a splice and its host copy, the plan of a byte-addressed read
+// and that of a byte-addressed write, and the container's rules that every call must share, each written once.
 // This is the part that parses untrusted input.  It needs no GPU and no HIP header, so that a plain C++ program can run it under
-// the sanitizers (tools/knz_host_check.cpp, tools/knz_read_check.cpp); kz_stream.hip and kz_stream_device.hip are its users.
+// the sanitizers (tools/knz_host_check.cpp, tools/knz_read_check.cpp, tools/knz_write_check.cpp); kz_stream.hip and kz_stream_device.hip are its users.
 // Layout: K/io/CompressedOutputStream.java (writeHeader :236-313, ordered block emission :1024-1035, end marker :483-493) and
 // K/io/CompressedInputStream.java (readHeader :359-515, block length prefix :1127-1129).
 #pragma once
@@ -476,4 +476,156 @@ static inline void knz_read_settle(KnzReadPlan& P, int64_t c, int CH, const int6
     if (got[s.range] < 0) continue;
     if (r.status) got[s.range] = r.status; else got[s.range] += s.len;
   }
+}
+
+// ---- byte-addressed writes: many ranges of the original data replaced in one call (kz_write_bytes / kz_write_bytes_device) ----
+// The plan of such a call, from host arrays alone, so that both forms share it.  Blocks and their starts B are the read's; range i
+// brings data[D[i], D[i] + rangeLen[i]), D = the running sum of the lengths.  Ranges may overlap in any way and the later one in
+// argument order wins: the plan turns them into disjoint SURVIVING segments, each one piece of one range cut with one block, so that
+// every byte of the data has at most one segment (the last range that covers it) and the copy needs no order.  A range lies wholly
+// inside the data, which is checked as len <= end - off before any off + len is formed: no int64 sum overflows.
+struct KnzWriteSeg {         // 32 bytes: the entry of k_knz_write's table
+  int64_t src;               // byte offset in data
+  int64_t unit0;             // the segment's first 16-byte aligned row unit among the units of its chunk (prefix sum)
+  int32_t slot;              // the block's row among the rows of its chunk
+  int32_t off;               // byte offset in the block
+  int32_t len;               // bytes (> 0)
+  int32_t range;             // the owning range
+};
+struct KnzWritePlan {
+  int64_t end;                         // the end of data as the arguments give it: B[nIndex], or nIndex * blockSize without a table
+  std::vector<int32_t> blocks;         // the touched blocks, ascending; chunk c = blocks[c * CH .. (c + 1) * CH)
+  std::vector<uint8_t> covered;        // covered[i]: blocks[i] is wholly overwritten and a table gave its length: no decode, no check
+  std::vector<KnzWriteSeg> segs;       // ascending by place in the data, that is by block and by offset in it: chunk by chunk
+  std::vector<int64_t> first;          // chunk c owns segs[first[c] .. first[c + 1])
+  std::vector<int64_t> units;          // units[c] = the row units of chunk c: what unit0 sums up to
+  std::vector<int64_t> cuts;           // launch l copies segs[cuts[l] .. cuts[l + 1]): at most `launch` segments, of one chunk
+};
+// dataLen == D[nRanges] included; newBitOff / newBits: both or neither
+static inline int knz_write_args(const void* src, int64_t n, const int64_t* blockBitOff, const int64_t* blockBits, int32_t nIndex, const int64_t* rangeOff,
+                                 const int64_t* rangeLen, int32_t nRanges, const void* data, int64_t dataLen, const void* dst, int64_t dstCap,
+                                 const int64_t* newBitOff, const int64_t* newBits) {
+  if (!src || n < 0 || nIndex < 0 || nRanges < 0 || dataLen < 0 || !dst || dstCap < 0 || (nIndex > 0 && (!blockBitOff || !blockBits))) return -KZ_ERR_INVALID_PARAM;
+  if ((nRanges > 0 && (!rangeOff || !rangeLen)) || (dataLen > 0 && !data) || (!newBitOff != !newBits)) return -KZ_ERR_INVALID_PARAM;
+  int64_t D = 0;
+  for (int32_t i = 0; i < nRanges; i++) {
+    if (rangeOff[i] < 0 || rangeLen[i] < 0 || rangeLen[i] > dataLen - D) return -KZ_ERR_INVALID_PARAM;
+    D += rangeLen[i];
+  }
+  return D == dataLen ? 0 : -KZ_ERR_INVALID_PARAM;
+}
+// kz_write_bytes_bound: the longest stream header, per block 5 + 34 prefix bits and the longer of its own payload and a recoded
+// block's bound, the end marker
+static inline int64_t knz_write_bound(const int64_t* blockBits, int32_t nIndex, int32_t blockSize) {
+  if (nIndex < 0 || (nIndex > 0 && !blockBits) || !knz_block_size_ok(blockSize)) return -KZ_ERR_INVALID_PARAM;
+  const int64_t rec = 8 * (((int64_t)blockSize + (blockSize >> 3) + 1024 + 255) / 256 * 256);   // kz_max_block_stream_bytes, restated: no library here
+  int64_t bits = 8;
+  for (int32_t k = 0; k < nIndex; k++) {
+    if (blockBits[k] < 0 || blockBits[k] >= (1LL << 34)) return -KZ_ERR_INVALID_PARAM;
+    bits += 5 + 34 + std::max<int64_t>(blockBits[k], rec);
+    if (bits > (1LL << 62)) return -KZ_ERR_INVALID_PARAM;
+  }
+  return 26 + ((bits + 7) >> 3);
+}
+static inline int knz_write_behind(int32_t i, char* err, size_t errCap) {
+  if (err) snprintf(err, errCap, "range %d ends behind the data", (int)i);
+  return -KZ_ERR_INVALID_PARAM;
+}
+// The plan.  The arguments have passed knz_write_args and knz_read_table; CH >= 1 = touched blocks per chunk, launch >= 1 = segments
+// per launch.  Returns -1, or the first range that ends behind P.end (nothing else of P is then filled).
+// Later wins by a sort and a sweep, O(nRanges log nRanges): the ranges' starts and ends in ascending order cut the data into at most
+// 2 nRanges elementary intervals; over each the owner is the highest range among those open there (a heap of the open ranges, closed
+// ones dropped when they come to the top).  Neighbours of one owner are joined, then each piece is cut with the blocks.
+static inline int32_t knz_write_plan(const int64_t* B, int32_t nIndex, int32_t blockSize, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges,
+                                     int CH, int64_t launch, KnzWritePlan& P) {
+  P.end = B ? B[nIndex] : (int64_t)nIndex * blockSize;
+  P.blocks.clear(); P.covered.clear(); P.segs.clear(); P.first.assign(1, 0); P.units.clear(); P.cuts.assign(1, 0);
+  std::vector<int64_t> D((size_t)nRanges + 1, 0);
+  std::vector<int32_t> open;                                       // the ranges with bytes, by start (ties: by argument order)
+  std::vector<int64_t> pts;
+  for (int32_t i = 0; i < nRanges; i++) {
+    if (rangeOff[i] > P.end || rangeLen[i] > P.end - rangeOff[i]) return i;
+    D[(size_t)i + 1] = D[(size_t)i] + rangeLen[i];
+    if (rangeLen[i] == 0) continue;
+    open.push_back(i);
+    pts.push_back(rangeOff[i]); pts.push_back(rangeOff[i] + rangeLen[i]);          // (<= P.end: checked above)
+  }
+  std::sort(open.begin(), open.end(), [&](int32_t a, int32_t b) { return rangeOff[a] != rangeOff[b] ? rangeOff[a] < rangeOff[b] : a < b; });
+  std::sort(pts.begin(), pts.end());
+  pts.erase(std::unique(pts.begin(), pts.end()), pts.end());
+  struct Piece { int64_t at, len; int32_t range; };
+  std::vector<Piece> pieces;
+  {
+    std::vector<int32_t> heap;                                     // max-heap of range numbers
+    size_t nx = 0;
+    for (size_t p = 0; p + 1 < pts.size(); p++) {
+      const int64_t a = pts[p], b = pts[p + 1];
+      while (nx < open.size() && rangeOff[open[nx]] == a) { heap.push_back(open[nx++]); std::push_heap(heap.begin(), heap.end()); }
+      while (!heap.empty() && rangeOff[heap.front()] + rangeLen[heap.front()] <= a) { std::pop_heap(heap.begin(), heap.end()); heap.pop_back(); }
+      if (heap.empty()) continue;
+      const int32_t r = heap.front();
+      if (!pieces.empty() && pieces.back().range == r && pieces.back().at + pieces.back().len == a) pieces.back().len += b - a;
+      else pieces.push_back(Piece{a, b - a, r});
+    }
+  }
+  std::vector<int32_t> blk;                                        // the block of segs[i]
+  std::vector<int64_t> have;                                       // surviving bytes per touched block
+  for (const Piece& pc : pieces) {
+    int64_t at = pc.at, left = pc.len;
+    int64_t k = B ? (std::upper_bound(B, B + nIndex + 1, at) - B) - 1 : at / blockSize;   // the block that holds byte `at`
+    for (; left > 0; k++) {
+      const int64_t b0 = B ? B[k] : k * blockSize, b1 = B ? B[k + 1] : b0 + blockSize;
+      const int64_t len = std::min<int64_t>(left, b1 - at);
+      if (P.blocks.empty() || P.blocks.back() != (int32_t)k) { P.blocks.push_back((int32_t)k); have.push_back(0); }
+      have.back() += len;
+      P.segs.push_back(KnzWriteSeg{D[(size_t)pc.range] + (at - rangeOff[pc.range]), 0, (int32_t)((int64_t)(P.blocks.size() - 1) % CH), (int32_t)(at - b0), (int32_t)len, pc.range});
+      blk.push_back((int32_t)(P.blocks.size() - 1));
+      at += len; left -= len;
+    }
+  }
+  P.covered.resize(P.blocks.size());
+  for (size_t i = 0; i < P.blocks.size(); i++) P.covered[i] = (B && have[i] == B[P.blocks[i] + 1] - B[P.blocks[i]]) ? 1 : 0;
+  const int64_t nChunks = ((int64_t)P.blocks.size() + CH - 1) / CH;
+  P.first.assign((size_t)nChunks + 1, 0);
+  P.units.assign((size_t)nChunks, 0);
+  for (size_t i = 0; i < P.segs.size(); i++) {                     // (already chunk by chunk: blocks ascend with the segments)
+    const int64_t c = blk[i] / CH;
+    P.first[(size_t)c + 1] = (int64_t)i + 1;
+    P.segs[i].unit0 = P.units[(size_t)c];
+    P.units[(size_t)c] += knz_read_units(P.segs[i].off & 15, P.segs[i].len);       // rows start on a 16-byte boundary, blockSize apart
+  }
+  for (int64_t c = 0; c < nChunks; c++)
+    for (int64_t s = P.first[(size_t)c]; s < P.first[(size_t)c + 1];) {
+      s += std::min<int64_t>(launch, P.first[(size_t)c + 1] - s);
+      P.cuts.push_back(s);
+    }
+  return -1;
+}
+// After chunk c has been decoded (res[j]: the result of its block j; the caller gave a wholly covered block status 0 and the table's
+// length): the length check of every block as knz_read_settle makes it, and, without a table, the segments against the real end of a
+// short last block.  lens[j] = the bytes of row j when the chunk is patched.  Returns 0, or the code of the first failing block in
+// block order with its text in err ("block %d: ..."; a range across the end of the last block: knz_write_behind's).
+static inline int knz_write_settle(const KnzWritePlan& P, int64_t c, int CH, const int64_t* B, int32_t nIndex, int32_t blockSize, kz_block_result* res, int32_t* lens,
+                                   char* err, size_t errCap) {
+  const int64_t b0 = c * CH, cnt = std::min<int64_t>(CH, (int64_t)P.blocks.size() - b0);
+  for (int64_t j = 0; j < cnt; j++) {
+    const int32_t k = P.blocks[(size_t)(b0 + j)];
+    const int64_t want = knz_read_block_len(B, nIndex, blockSize, k);
+    const char* why = "its decode failed";
+    if (!res[j].status) {
+      if (res[j].length > blockSize) { res[j].status = -KZ_ERR_PROCESS_BLOCK; why = "decodes to more than the block size"; }
+      else if (want >= 0 && res[j].length != want) { res[j].status = -KZ_ERR_INVALID_FILE; why = "decodes to another length than its place in the data"; }
+    }
+    if (res[j].status) {
+      if (err) snprintf(err, errCap, "block %d: %s (%d)", (int)k, why, (int)res[j].status);
+      return res[j].status;
+    }
+    lens[j] = res[j].length;
+  }
+  if (!B)
+    for (int64_t i = P.first[(size_t)c]; i < P.first[(size_t)c + 1]; i++) {
+      const KnzWriteSeg& s = P.segs[(size_t)i];
+      if ((int64_t)s.off + s.len > lens[s.slot]) return knz_write_behind(s.range, err, errCap);
+    }
+  return 0;
 }

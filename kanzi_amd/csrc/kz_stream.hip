@@ -502,3 +502,122 @@ extern "C" int64_t kz_read_bytes(kz_ctx* ctx, const uint8_t* src, int64_t n, con
   }
   return total;
 }
+
+// Byte-addressed write: many ranges [off, off + len) of the original data replaced by new bytes in one call, the result a new stream.
+// The plan (kz_knz_host.h) resolves "the later range wins" into disjoint segments and names the touched blocks and which of them are
+// wholly covered; every entry the call uses is checked against the stream before anything is decoded, then per chunk of touched
+// blocks the read's steps up to the decode into host rows, a memcpy per segment into those rows, one batched encode of the rows, and
+// the splice's bit copy of every kept block since the previous chunk with the recoded ones.  kz_write_bytes_device
+// (kz_stream_device.hip) is the same call on device memory, and this one is its reference.
+extern "C" int64_t kz_write_bytes_bound(const int64_t* blockBits, int32_t nIndex, int32_t blockSize) { return knz_write_bound(blockBits, nIndex, blockSize); }
+extern "C" int64_t kz_write_bytes(kz_ctx* ctx, const uint8_t* src, int64_t n, const int64_t* blockBitOff, const int64_t* blockBits, const int64_t* blockByteOff,
+                                  int32_t nIndex, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges, const uint8_t* data, int64_t dataLen,
+                                  uint8_t* dst, int64_t dstCap, int64_t* newBitOff, int64_t* newBits) {
+  if (!ctx) return -KZ_ERR_INVALID_PARAM;
+  { const int rc = knz_write_args(src, n, blockBitOff, blockBits, nIndex, rangeOff, rangeLen, nRanges, data, dataLen, dst, dstCap, newBitOff, newBits); if (rc) return rc; }
+  KZ_HIP(hipSetDevice(ctx->device));
+  HostBitsIn bs{src, (uint64_t)n * 8, 0, false};
+  KnzHeader h;
+  { const int hrc = read_stream_header(bs, h, ctx->err, sizeof(ctx->err)); if (hrc) return hrc; }
+  const KnzPlan P = knz_plan(ctx, h, n, (int64_t)bs.pos);
+  const int32_t blockSize = h.blockSize;
+  if (knz_read_table(blockByteOff, nIndex, blockSize)) {
+    snprintf(ctx->err, sizeof(ctx->err), "kz_write_bytes: blockByteOff is not a table of block starts");
+    return -KZ_ERR_INVALID_PARAM;
+  }
+  const int CH = knz_chunk_blocks(ctx, blockSize);
+  KnzWritePlan R;
+  { const int32_t bad = knz_write_plan(blockByteOff, nIndex, blockSize, rangeOff, rangeLen, nRanges, CH, INT64_MAX, R); if (bad >= 0) return knz_write_behind(bad, ctx->err, sizeof(ctx->err)); }
+  const int64_t nb = (int64_t)R.blocks.size();
+  for (int64_t k = 0, t = 0; k < nIndex; k++) {                   // every entry the call uses: the kept blocks' and the decoded ones'
+    if (t < nb && R.blocks[(size_t)t] == k && R.covered[(size_t)t++]) continue;
+    if (!knz_check_entry(src, n, P.hdrEnd, blockBitOff[k], blockBits[k])) return indexed_mismatch(ctx, k);
+  }
+  ChecksumScope chk(ctx, h.chkKind);
+  BlockSizeScope scope(ctx, blockSize);
+  const int cmax = (int)std::max<int64_t>(1, std::min<int64_t>(CH, nb));
+  const int64_t oS = kz_max_block_stream_bytes(blockSize);
+  std::unique_ptr<uint8_t[]> inbuf, rows, enc;
+  if (nb) { inbuf.reset(new uint8_t[(size_t)P.iS * cmax]); rows.reset(new uint8_t[(size_t)blockSize * cmax]); enc.reset(new uint8_t[(size_t)oS * cmax]); }
+  std::vector<kz_block_result> res((size_t)cmax), eres((size_t)cmax);
+  std::vector<int64_t> W((size_t)cmax), off((size_t)cmax);
+  std::vector<int32_t> lens((size_t)cmax);
+  auto tooSmall = [&]() { snprintf(ctx->err, sizeof(ctx->err), "kz_write_bytes: destination too small"); return (int64_t)-KZ_ERR_WRITE_FILE; };
+  HostBits out{dst, dstCap, 0, false};
+  int64_t pos = 0;                                                // the bit behind what has been laid out (out.pos follows it)
+  {
+    uint8_t nh[32];
+    HostBits hb{nh, 32, 0, false};
+    write_stream_header(hb, h.transformType, (uint32_t)h.entropyType, blockSize, h.inputSize, h.chkKind);
+    pos = (int64_t)hb.pos;
+  }
+  // blocks [k0, k1) behind what has been written, the touched ones t0 .. t1 of the list from the encoder's rows; then tailBits zero
+  // bits.  Decided from the bit arithmetic before a bit of them is written: -KZ_ERR_WRITE_FILE when they do not fit.
+  auto emit = [&](int64_t k0, int64_t k1, int64_t t0, int64_t t1, int tailBits) -> int {
+    int64_t end = pos, t = t0;
+    for (int64_t k = k0; k < k1; k++) {
+      const int64_t w = (t < t1 && R.blocks[(size_t)t] == k) ? eres[(size_t)(t++ - t0)].bits : blockBits[k];
+      end += 5 + knz_prefix_width((uint64_t)w) + w;
+    }
+    if (((end + tailBits + 7) >> 3) > dstCap) return -KZ_ERR_WRITE_FILE;
+    if (out.pos == 0) write_stream_header(out, h.transformType, (uint32_t)h.entropyType, blockSize, h.inputSize, h.chkKind);
+    t = t0;
+    for (int64_t k = k0; k < k1; k++) {
+      const bool rec = t < t1 && R.blocks[(size_t)t] == k;
+      const int64_t w = rec ? eres[(size_t)(t - t0)].bits : blockBits[k];
+      const int lw = knz_prefix_width((uint64_t)w);
+      out.put((uint64_t)(lw - 3), 5);
+      out.put((uint64_t)w, lw);
+      if (newBitOff) { newBitOff[k] = (int64_t)out.pos; newBits[k] = w; }
+      if (rec) out.putBytes(enc.get() + (size_t)(t++ - t0) * oS, (uint64_t)w);
+      else knz_copy_bits(out, src, n, blockBitOff[k], w);
+    }
+    if (tailBits) write_end_marker(out);
+    pos = end + tailBits;
+    return out.overflow ? -KZ_ERR_WRITE_FILE : 0;
+  };
+  int64_t next = 0;                                               // the first block not yet in the new stream
+  for (int64_t b0 = 0, c = 0; b0 < nb; b0 += CH, c++) {
+    const int cnt = (int)std::min<int64_t>(CH, nb - b0);
+    for (int i = 0; i < cnt; i++) {
+      const int32_t k = R.blocks[(size_t)(b0 + i)];
+      memset(&res[i], 0, sizeof(res[i]));
+      if (R.covered[(size_t)(b0 + i)]) { W[i] = 0; off[i] = 0; res[i].status = 1; continue; }         // (1: left out of the decode)
+      off[i] = blockBitOff[k]; W[i] = blockBits[k];
+      HostBitsIn t = bs; t.pos = (uint64_t)off[i]; t.error = false;
+      const int rc = knz_check_block(t, (uint64_t)W[i], (uint64_t)off[i], t.nbits, P, false);         // (knz_check_entry saw the payload's end)
+      res[i].bits = W[i]; res[i].status = rc;
+    }
+    parallel_blocks(cnt, [&](int i) {
+      if (res[i].status) return;
+      HostBitsIn t = bs; t.pos = (uint64_t)off[i]; t.error = false; t.getBytes(inbuf.get() + (size_t)i * P.iS, (uint64_t)W[i]);
+    });
+    { const int rc = indexed_decode_runs(ctx, P, inbuf.get(), W.data(), cnt, rows.get(), blockSize, res.data(), KZ_MEM_HOST); if (rc) return rc; }
+    for (int i = 0; i < cnt; i++)
+      if (R.covered[(size_t)(b0 + i)]) { const int32_t k = R.blocks[(size_t)(b0 + i)]; res[i].status = 0; res[i].length = (int32_t)(blockByteOff[k + 1] - blockByteOff[k]); }
+    { const int rc = knz_write_settle(R, c, CH, blockByteOff, nIndex, blockSize, res.data(), lens.data(), ctx->err, sizeof(ctx->err)); if (rc) return rc; }
+    const int64_t s0 = R.first[(size_t)c], s1 = R.first[(size_t)c + 1];
+    parallel_blocks((int)std::min<int64_t>(s1 - s0, 64), [&](int q) {                     // the chunk's segments in up to 64 runs: disjoint, so in any order
+      const int64_t runs = std::min<int64_t>(s1 - s0, 64);
+      for (int64_t i = s0 + (s1 - s0) * q / runs; i < s0 + (s1 - s0) * (q + 1) / runs; i++) {
+        const KnzWriteSeg& g = R.segs[(size_t)i];
+        memcpy(rows.get() + (size_t)g.slot * blockSize + g.off, data + g.src, (size_t)g.len);
+      }
+    });
+    {
+      const int rc = kz_encode_blocks_pre(ctx, h.transformType, (uint32_t)h.entropyType, blockSize, rows.get(), blockSize, lens.data(), cnt, enc.get(), oS, eres.data(), KZ_MEM_HOST, nullptr);
+      if (rc) return rc;
+      for (int i = 0; i < cnt; i++)
+        if (eres[i].status || eres[i].bits <= 0) {
+          snprintf(ctx->err, sizeof(ctx->err), "block %d: its encode failed (%d)", (int)R.blocks[(size_t)(b0 + i)], (int)eres[i].status);
+          return eres[i].status ? eres[i].status : -KZ_ERR_PROCESS_BLOCK;
+        }
+    }
+    const int64_t k1 = (int64_t)R.blocks[(size_t)(b0 + cnt - 1)] + 1;
+    if (emit(next, k1, b0, b0 + cnt, 0)) return tooSmall();
+    next = k1;
+  }
+  if (emit(next, nIndex, nb, nb, 8)) return tooSmall();            // the kept tail and the end marker
+  return (int64_t)((out.pos + 7) >> 3);
+}
+

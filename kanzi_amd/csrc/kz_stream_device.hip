@@ -1,5 +1,5 @@
 // kz_stream_device.hip -- the .knz container with source and destination in HBM: the same streams as kz_stream.hip's calls write and
-// read, whole, by block range, by index, and many at a time, and edits them without recoding (the splice).  The kernels are in kz_knz_gpu.hip; what stays on the host is what
+// read, whole, by block range, by index, and many at a time, edits them without recoding (the splice), and rewrites byte ranges of their data (kz_write_bytes_device).  The kernels are in kz_knz_gpu.hip; what stays on the host is what
 // kz_compress / kz_decompress do there as well and costs nothing: the stream header (kz_knz_host.h, on a copy of at most 26 bytes),
 // the bit-offset arithmetic over results[] (host arrays anyway), and the block checks on the 8 header bytes per block that the walk
 // kernel brings back.  The rules shared with the host-buffer calls are in kz_knz_host.h and kz_knz_stream.h.
@@ -913,3 +913,210 @@ extern "C" int64_t kz_read_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int64
   }
   return total;
 }
+
+
+// =================================================================================================
+// byte-addressed writes: many ranges [off, off + len) of the original data replaced by new bytes in one call, stream, new bytes and
+// the new stream in HBM (kz_write_bytes_device).  The plan is the host form's (kz_knz_host.h: later wins resolved into disjoint
+// segments, the touched blocks, which of them are wholly covered).  Every index entry the call uses is checked against the stream
+// (k_knz_check) before anything is unpacked; then per chunk of touched blocks the read's steps up to the decode (prechecks, unpack,
+// decode into staging rows), k_knz_write launches that patch the rows, kz_compress_device's batched encode of the rows, and the
+// splice's copy (k_knz_splice) of every kept block since the previous chunk together with the recoded ones.  A piece's payload lies in
+// d_src (kept) or in an encoder row (recoded): the launch's base is d_src, a row is named by its distance from it.
+namespace {
+const int KNZ_WRITE_LAUNCH = 1 << 20;                              // segments per k_knz_write launch: bounds the table at 32 MiB
+}
+extern "C" int64_t kz_write_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, const int64_t* blockBitOff, const int64_t* blockBits, const int64_t* blockByteOff,
+                                         int32_t nIndex, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges, const uint8_t* d_data, int64_t dataLen,
+                                         uint8_t* d_dst, int64_t dstCap, int64_t* newBitOff, int64_t* newBits) {
+  if (!ctx) return -KZ_ERR_INVALID_PARAM;
+  { const int rc = knz_write_args(d_src, n, blockBitOff, blockBits, nIndex, rangeOff, rangeLen, nRanges, d_data, dataLen, d_dst, dstCap, newBitOff, newBits); if (rc) return rc; }
+  KZ_HIP(hipSetDevice(ctx->device));
+  uint8_t hdr[32]; HostBitsIn bs;
+  { const int rc = knz_open(ctx, d_src, n, hdr, bs); if (rc) return rc; }
+  KnzHeader h;
+  { const int hrc = read_stream_header(bs, h, ctx->err, sizeof(ctx->err)); if (hrc) return hrc; }
+  const KnzPlan P = knz_plan(ctx, h, n, (int64_t)bs.pos);
+  const int32_t blockSize = h.blockSize;
+  if (knz_read_table(blockByteOff, nIndex, blockSize)) {
+    snprintf(ctx->err, sizeof(ctx->err), "kz_write_bytes_device: blockByteOff is not a table of block starts");
+    return -KZ_ERR_INVALID_PARAM;
+  }
+  const int CH = knz_chunk_blocks(ctx, blockSize);
+  KnzWritePlan R;
+  { const int32_t bad = knz_write_plan(blockByteOff, nIndex, blockSize, rangeOff, rangeLen, nRanges, CH, KNZ_WRITE_LAUNCH, R); if (bad >= 0) return knz_write_behind(bad, ctx->err, sizeof(ctx->err)); }
+  uint8_t nh[32];                                                  // the new stream's header: the old one's parameters and size
+  HostBits hb{nh, 32, 0, false};
+  write_stream_header(hb, h.transformType, (uint32_t)h.entropyType, blockSize, h.inputSize, h.chkKind);
+  ChecksumScope chk(ctx, h.chkKind);
+  BlockSizeScope scope(ctx, blockSize);
+  const int64_t nb = (int64_t)R.blocks.size();
+  const int cmax = (int)std::max<int64_t>(1, std::min<int64_t>(CH, nb));
+  const int PL = (int)std::max<int64_t>(1, std::min<int64_t>(CH, nIndex));        // entries per check launch, pieces per copy launch: the splice's chunk
+  const int64_t oS = kz_max_block_stream_bytes(blockSize);
+  int64_t segMax = 0;
+  for (size_t l = 0; l + 1 < R.cuts.size(); l++) segMax = std::max(segMax, R.cuts[l + 1] - R.cuts[l]);
+  // the tables, pinned and in HBM, one after the other in the same place: the check's (off, bits, hdr, bad), a chunk's, the segments of
+  // a patch launch, the pieces of a copy launch
+  { const int rc = knz_tables(ctx, std::max(std::max((size_t)std::max(PL, cmax) * 32, (size_t)segMax * sizeof(KnzWriteSeg)), (size_t)PL * sizeof(KnzPiece))); if (rc) return rc; }
+  // ---- every entry the call uses against the stream, before anything is unpacked: the kept blocks' and the decoded ones' ----
+  std::vector<uint64_t> hdrs((size_t)nb);
+  {
+    const KnzTable T(ctx, PL);
+    int64_t ti = 0;                                               // the next touched block
+    for (int64_t k0 = 0; k0 < nIndex; k0 += PL) {
+      const int cnt = (int)std::min<int64_t>(PL, nIndex - k0);
+      int64_t tj = ti;
+      for (int i = 0; i < cnt; i++) {
+        const bool skip = tj < nb && R.blocks[(size_t)tj] == k0 + i && R.covered[(size_t)tj++];       // a wholly covered block's entry is not looked at
+        T.off()[i] = skip ? 0 : blockBitOff[k0 + i]; T.bits()[i] = skip ? 0 : blockBits[k0 + i];
+      }
+      KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+      KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+      { const int rc = kz_knz_check(ctx, d_src, n, P.hdrEnd, T.d_off(), T.d_bits(), cnt, T.d_hdr(), T.d_bad()); if (rc) return rc; }
+      KZ_HIP(hipMemcpyAsync(T.hdr(), T.d_hdr(), (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+      KZ_HIP(hipMemcpyAsync(T.bad(), T.d_bad(), (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+      KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+      kz_ktimer_flush(ctx);
+      for (int i = 0; i < cnt; i++) {
+        const bool touched = ti < nb && R.blocks[(size_t)ti] == k0 + i;
+        if (touched && R.covered[(size_t)ti]) { ti++; continue; }
+        if (T.bad()[i]) return indexed_mismatch(ctx, k0 + i);
+        if (touched) hdrs[(size_t)ti++] = T.hdr()[i];
+      }
+    }
+  }
+  {
+    int rc = kz_stage_reserve(ctx, ctx->devIn[0], (size_t)cmax * P.iS, false);
+    if (!rc) rc = kz_stage_reserve(ctx, ctx->devOut[0], (size_t)cmax * (size_t)blockSize, false);
+    if (!rc) rc = kz_stage_reserve(ctx, ctx->devOut[1], (size_t)cmax * (size_t)oS, false);
+    if (rc) return rc;
+  }
+  uint8_t* rows = ctx->devOut[0].p;
+  uint8_t* enc = ctx->devOut[1].p;
+  if ((uintptr_t)rows & 15) { snprintf(ctx->err, sizeof(ctx->err), "kz_write_bytes_device: staging rows off a 16-byte boundary"); return -KZ_ERR_DEVICE; }   // (unit0 counts on it)
+  auto tooSmall = [&]() { snprintf(ctx->err, sizeof(ctx->err), "kz_write_bytes_device: destination too small"); return (int64_t)-KZ_ERR_WRITE_FILE; };
+  // blocks [k0, k1) of the new stream from bit `pos` on, in launches of PL pieces: the blocks t0 .. of the touched list (ascending) come
+  // from the encoder's rows (eW: their bits), all others from where they lie in d_src; then tailBits zero bits.  The room was checked.
+  int64_t pos = (int64_t)hb.pos;
+  auto emit = [&](int64_t k0, int64_t k1, int64_t t0, int64_t t1, const int64_t* eW, int tailBits) -> int {
+    KnzPiece* pc = (KnzPiece*)(ctx->knzPin.p + 64);
+    int64_t t = t0;
+    for (int64_t a = k0; a < k1 || (a == k0 && tailBits); a += PL) {
+      const int cnt = (int)std::max<int64_t>(0, std::min<int64_t>(PL, k1 - a));
+      const int64_t start = pos;
+      for (int i = 0; i < cnt; i++) {
+        const int64_t k = a + i;
+        const bool rec = t < t1 && R.blocks[(size_t)t] == k;
+        const int64_t W = rec ? eW[t - t0] : blockBits[k];
+        pos += 5 + knz_prefix_width((uint64_t)W);
+        pc[i] = rec ? KnzPiece{pos, W, (int64_t)((intptr_t)(enc + (t - t0) * oS) - (intptr_t)d_src), (W + 7) >> 3, 0, 0}
+                    : KnzPiece{pos, W, 0, n, blockBitOff[k], P.hdrEnd};
+        if (newBitOff) { newBitOff[k] = pos; newBits[k] = W; }
+        pos += W;
+        if (rec) t++;
+      }
+      const bool last = a + cnt >= k1;
+      if (last) pos += tailBits;
+      if (cnt) KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + 64, pc, (size_t)cnt * sizeof(KnzPiece), hipMemcpyHostToDevice, ctx->stream));
+      { const int rc = kz_knz_splice_launch(ctx, d_src, (const KnzPiece*)(ctx->knzAux.p + 64), cnt, d_dst, start, pos); if (rc) return rc; }
+      KZ_HIP(kz_stream_sync(ctx, ctx->stream));                    // the pinned table is the next launch's
+      kz_ktimer_flush(ctx);
+      if (last) break;
+    }
+    return 0;
+  };
+  // the bit behind blocks [k0, k1) laid out from `from`, the touched ones t0 .. with eW bits
+  auto layout = [&](int64_t from, int64_t k0, int64_t k1, int64_t t0, int64_t t1, const int64_t* eW) {
+    int64_t t = t0;
+    for (int64_t k = k0; k < k1; k++) {
+      const bool rec = t < t1 && R.blocks[(size_t)t] == k;
+      const int64_t W = rec ? eW[t++ - t0] : blockBits[k];
+      from += 5 + knz_prefix_width((uint64_t)W) + W;
+    }
+    return from;
+  };
+  // ---- chunks of touched blocks, ascending: prechecks, unpack, decode into rows blockSize apart, patch, encode, copy ----
+  const uint64_t nbits = (uint64_t)n * 8;
+  const KnzTable T(ctx, cmax);
+  std::vector<kz_block_result> res((size_t)cmax), eres((size_t)cmax);
+  std::vector<int64_t> W((size_t)cmax), eW((size_t)cmax);
+  std::vector<int32_t> lens((size_t)cmax);
+  int64_t next = 0;                                               // the first block not yet in the new stream
+  size_t li = 0;                                                  // the next patch launch of the plan
+  for (int64_t b0 = 0, c = 0; b0 < nb; b0 += CH, c++) {
+    const int cnt = (int)std::min<int64_t>(CH, nb - b0);
+    int64_t maxBytes = 0;
+    for (int i = 0; i < cnt; i++) {
+      const int32_t k = R.blocks[(size_t)(b0 + i)];
+      memset(&res[i], 0, sizeof(res[i]));
+      if (R.covered[(size_t)(b0 + i)]) { W[i] = 0; res[i].status = 1; T.off()[i] = 0; T.bits()[i] = 0; continue; }   // (1: left out of the decode)
+      W[i] = blockBits[k];
+      const int rc = knz_check_walked(hdrs[(size_t)(b0 + i)], (uint64_t)W[i], (uint64_t)blockBitOff[k], nbits, P);
+      res[i].bits = W[i]; res[i].status = rc;
+      T.off()[i] = blockBitOff[k];
+      T.bits()[i] = rc ? 0 : W[i];                                  // a row of no bits: nothing of it is unpacked
+      if (!rc) maxBytes = std::max<int64_t>(maxBytes, (W[i] + 7) >> 3);
+    }
+    if (maxBytes > 0) {
+      KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+      KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+      { const int rc = kz_knz_unpack(ctx, d_src, n, T.d_off(), T.d_bits(), cnt, maxBytes, ctx->devIn[0].p, P.iS); if (rc) return rc; }
+      { const int rc = indexed_decode_runs(ctx, P, ctx->devIn[0].p, W.data(), cnt, rows, blockSize, res.data(), KZ_MEM_DEVICE); if (rc) return rc; }
+      KZ_HIP(kz_stream_sync(ctx, ctx->stream));                    // the pinned table becomes the segments'
+      kz_ktimer_flush(ctx);
+    }
+    for (int i = 0; i < cnt; i++)
+      if (R.covered[(size_t)(b0 + i)]) { const int32_t k = R.blocks[(size_t)(b0 + i)]; res[i].status = 0; res[i].length = (int32_t)(blockByteOff[k + 1] - blockByteOff[k]); }
+    { const int rc = knz_write_settle(R, c, CH, blockByteOff, nIndex, blockSize, res.data(), lens.data(), ctx->err, sizeof(ctx->err)); if (rc) return rc; }
+    // ---- the patch: the chunk's segments into the rows ----
+    for (; li + 1 < R.cuts.size() && R.cuts[li] < R.first[(size_t)c + 1]; li++) {   // (a launch's segments are of one chunk)
+      const int64_t s0 = R.cuts[li], s1 = R.cuts[li + 1];
+      const int ns = (int)(s1 - s0);
+      if (ctx->sw.writeGather) {                                   // the yardstick: the same segments through the ragged copy, a workgroup column each
+        KnzCopy* t = (KnzCopy*)(ctx->knzPin.p + 64);
+        int64_t maxLen = 0;
+        for (int i = 0; i < ns; i++) {
+          const KnzWriteSeg& g = R.segs[(size_t)(s0 + i)];
+          t[i] = KnzCopy{g.src, (int64_t)g.slot * blockSize + g.off, g.len};
+          maxLen = std::max<int64_t>(maxLen, g.len);
+        }
+        KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + 64, t, (size_t)ns * sizeof(KnzCopy), hipMemcpyHostToDevice, ctx->stream));
+        { const int rc = kz_knz_gather(ctx, d_data, (const KnzCopy*)(ctx->knzAux.p + 64), ns, maxLen, rows); if (rc) return rc; }
+      } else {
+        memcpy(ctx->knzPin.p + 64, &R.segs[(size_t)s0], (size_t)ns * sizeof(KnzWriteSeg));
+        KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + 64, ctx->knzPin.p + 64, (size_t)ns * sizeof(KnzWriteSeg), hipMemcpyHostToDevice, ctx->stream));
+        const int64_t u0 = R.segs[(size_t)s0].unit0, uEnd = s1 < R.first[(size_t)c + 1] ? R.segs[(size_t)s1].unit0 : R.units[(size_t)c];
+        const int rc = kz_knz_write(ctx, d_data, dataLen, (const KnzWriteSeg*)(ctx->knzAux.p + 64), ns, rows, blockSize, u0, uEnd - u0);
+        if (rc) return rc;
+      }
+      KZ_HIP(kz_stream_sync(ctx, ctx->stream));                    // the pinned table is the next launch's; the encoder takes its input to be complete
+      kz_ktimer_flush(ctx);
+    }
+    // ---- one batched encode of the chunk's rows, with the chain of the stream's header ----
+    {
+      const int rc = kz_encode_blocks_pre(ctx, h.transformType, (uint32_t)h.entropyType, blockSize, rows, blockSize, lens.data(), cnt, enc, oS, eres.data(), KZ_MEM_DEVICE, nullptr);
+      if (rc) return rc;
+      for (int i = 0; i < cnt; i++) {
+        if (eres[i].status || eres[i].bits <= 0) {
+          snprintf(ctx->err, sizeof(ctx->err), "block %d: its encode failed (%d)", (int)R.blocks[(size_t)(b0 + i)], (int)eres[i].status);
+          return eres[i].status ? eres[i].status : -KZ_ERR_PROCESS_BLOCK;
+        }
+        eW[i] = eres[i].bits;
+      }
+    }
+    // ---- the copy: every kept block since the previous chunk, and the chunk's recoded ones, behind the previous chunk's last bit ----
+    const int64_t k1 = (int64_t)R.blocks[(size_t)(b0 + cnt - 1)] + 1;
+    if (((layout(pos, next, k1, b0, b0 + cnt, eW.data()) + 7) >> 3) > dstCap) return tooSmall();
+    { const int rc = emit(next, k1, b0, b0 + cnt, eW.data(), 0); if (rc) return rc; }
+    next = k1;
+  }
+  // ---- the kept tail and the end marker (:491-492) ----
+  if (((layout(pos, next, nIndex, nb, nb, nullptr) + 8 + 7) >> 3) > dstCap) return tooSmall();
+  { const int rc = emit(next, nIndex, nb, nb, nullptr, 8); if (rc) return rc; }
+  { const int hrc = knz_put_header(ctx, nh, (int64_t)(hb.pos >> 3), d_dst); if (hrc) return hrc; }
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  return (pos + 7) >> 3;
+}
+
