@@ -146,7 +146,7 @@ struct kz_ctx {
   hipStream_t copyUp = nullptr, copyDown = nullptr;
   Stage hiAux[2];                  // HBM: per-block lengths / masks of the decoder's host-inverse chunks (kz_api.hip)
   hipStream_t hiStream[2] = {nullptr, nullptr};   // their gather / scatter kernels run beside the main stream's next chunk
-  Stage knzPin, knzAux;            // pinned / HBM: the device stream calls' per-chunk tables (bit offsets, lengths, header bytes; kz_stream.hip)
+  Stage knzPin, knzAux;            // pinned / HBM: the device stream calls' per-chunk tables (bit offsets, lengths, header bytes; kz_stream_device.hip)
   // waits of the context's own thread: 1 = block on an event (hipEventBlockingSync) instead of hipStreamSynchronize's spin loop.
   // Chosen at creation: on when the process is CPU-quota limited (a spinning waiter burns a whole CPU of the quota that the
   // host stages -- or the other ranks of the node -- could use), KZ_BLOCKING_WAITS=0/1 overrides.
@@ -313,7 +313,7 @@ HostPre* kz_host_prestage(kz_ctx* ctx, uint64_t transformType, uint32_t entropyT
                           const int32_t* lengths, int32_t nBlocks, int slotId);   // slotId 0/1: the outputs go to the context's pinned hsOut[slotId]
 void kz_host_pre_free(HostPre* p);
 
-// ---- the .knz container on device memory (kz_knz_gpu.hip); the callers are in kz_stream.hip ----
+// ---- the .knz container on device memory (kz_knz_gpu.hip); the callers are in kz_stream_device.hip ----
 struct KnzBlk { int64_t pay, bits, src; };   // a block in the container: bit offset of its payload in dst, its W, byte offset of its row
 enum { KNZ_WALK_COUNT = 0, KNZ_WALK_END = 1, KNZ_WALK_PREFIX = 2, KNZ_WALK_PAYLOAD = 3 };
 int kz_knz_pack(kz_ctx*, const uint8_t* d_rows, const KnzBlk* d_blk, int nb, uint8_t* d_dst, int64_t startBit, int64_t endBit);

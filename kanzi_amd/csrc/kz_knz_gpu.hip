@@ -6,9 +6,10 @@
 // where they are in their source streams, with the check of every piece against its own source in front of it (kz_knz_splice_device);
 // and the copy of the byte-addressed reads: many (range x block) segments of decoded rows to their places in one launch (k_knz_read),
 // with its mirror image for the byte-addressed writes: segments of new bytes into decoded rows (k_knz_write).
-// The callers (kz_compress_device / kz_decompress_device / kz_decompress_range_device /
-// kz_decode_indexed_device / kz_knz_assemble_device / kz_knz_index_device, kz_stream_device.hip) do the bit-offset arithmetic, the stream
-// header and the block-header prechecks on the host; no payload byte leaves the device.
+// The callers (kz_stream_device.hip: kz_compress_device / kz_decompress_device / kz_decompress_range_device / kz_decode_indexed_device /
+// kz_knz_assemble_device / kz_knz_index_device, the two many-stream calls, kz_knz_splice_device, kz_read_bytes_device and
+// kz_write_bytes_device) do the bit-offset arithmetic, the stream header and the block-header prechecks on the host; no payload byte
+// leaves the device.
 #include "kz_device.h"
 #include "kz_internal.h"
 #include "kz_knz_host.h"
@@ -305,10 +306,25 @@ __global__ void __launch_bounds__(256) k_knz_unpack(const u8* __restrict__ src, 
 // The same four steps with a table entry per segment, slot or row that carries its own bounds: a launch serves every stream of a
 // group, and nothing is read outside a stream's own segment or written outside its own slot, wherever the other streams lie.
 
+// ---- the unit of every byte copy here (k_knz_gather / k_knz_scatter, k_knz_read, k_knz_write) ---------------------------------------
+// One 16-byte aligned unit of the destination side of a copy of len bytes from s to d, any alignment on both sides: ub = the unit's
+// first byte as an index into the range (may be < 0, and ub + 16 may be > len: the unit's bytes outside the range are not touched).
+// A whole unit is one wide store of aligned 32-bit loads if that load window stays inside [wlo, whi), the memory around s that may
+// be read; any other unit goes bytewise, the range's own bytes only.
+__device__ __forceinline__ void knz_copy_unit(u8* __restrict__ d, const u8* __restrict__ s, int64_t len, int64_t ub, const u8* wlo, const u8* whi) {
+  const int64_t lo = ub < 0 ? 0 : ub, hi = ub + 16 > len ? len : ub + 16;
+  if (lo >= hi) return;
+  if (hi - lo == 16) {
+    const u8* p = s + lo;
+    const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
+    if (al >= wlo && al + knz_window(p, 0) <= whi) { *(uint4*)(d + lo) = knz_load128(p, 0); return; }
+  }
+  for (int64_t b = lo; b < hi; b++) d[b] = s[b];
+}
+
 // ---- ragged copy: gather (segments -> encoder rows) and scatter (decoded rows -> slots) -----------------------------------------
 // Entry r: t[r].len bytes from from[t[r].src ..] to to[t[r].dst ..], any alignment on both sides.  Output-centric like the pack: a
-// lane owns one 16-byte aligned unit of the destination range; a whole unit is one wide store of aligned 32-bit loads that stay
-// inside [src, src + len), the units at either end of the range (and those whose load window would leave the source) go bytewise.
+// lane owns one 16-byte aligned unit of the destination range (knz_copy_unit); the loads stay inside [src, src + len).
 __device__ __forceinline__ void knz_ragged(const u8* __restrict__ from, const KnzCopy* __restrict__ t, int nr, u8* __restrict__ to) {
   for (int r = blockIdx.y; r < nr; r += gridDim.y) {
     const int64_t len = t[r].len;
@@ -317,17 +333,8 @@ __device__ __forceinline__ void knz_ragged(const u8* __restrict__ from, const Kn
     u8* d = to + t[r].dst;
     const uintptr_t A0 = (uintptr_t)d & ~(uintptr_t)15;
     const int64_t units = (int64_t)(((uintptr_t)(d + len) - A0 + 15) >> 4);
-    for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
-      const int64_t ub = (int64_t)(A0 - (uintptr_t)d) + (u << 4);                   // the unit's first byte as an index into the range (may be < 0)
-      const int64_t lo = ub < 0 ? 0 : ub, hi = ub + 16 > len ? len : ub + 16;
-      if (lo >= hi) continue;
-      if (hi - lo == 16) {
-        const u8* p = s + lo;
-        const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
-        if (al >= s && al + knz_window(p, 0) <= s + len) { *(uint4*)(d + lo) = knz_load128(p, 0); continue; }
-      }
-      for (int64_t b = lo; b < hi; b++) d[b] = s[b];
-    }
+    for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x)
+      knz_copy_unit(d, s, len, (int64_t)(A0 - (uintptr_t)d) + (u << 4), s, s + len);
   }
 }
 __global__ void __launch_bounds__(256) k_knz_gather(const u8* __restrict__ src, const KnzCopy* __restrict__ t, int nr, u8* __restrict__ rows) { knz_ragged(src, t, nr, rows); }
@@ -338,9 +345,8 @@ __global__ void __launch_bounds__(256) k_knz_scatter(const u8* __restrict__ rows
 // of it are the block's) to dst + seg[j].dst, any alignment on both sides; from a few bytes to a whole block each, up to a million
 // of them.  No workgroup per segment: the launch's work is the 16-byte aligned destination units of all its segments, one segment
 // after the other (seg[j].unit0 = the first of segment j, a prefix sum that grows strictly with j; the launch owns units
-// [unitBase, unitBase + units), seg[0].unit0 == unitBase).  A lane takes a unit, finds its segment by binary search on unit0 and does
-// what knz_ragged does for a unit: a unit wholly inside the segment whose aligned load window stays inside the row is one wide
-// store, any other unit goes bytewise, the segment's own bytes only.  A unit of memory that two segments share is visited once per
+// [unitBase, unitBase + units), seg[0].unit0 == unitBase).  A lane takes a unit, finds its segment by binary search on unit0 and copies
+// the unit (knz_copy_unit) with the row as the window of its aligned loads.  A unit of memory that two segments share is visited once per
 // segment, so every byte has one writer and no lane writes a byte that is not its segment's.  A segment whose len was cut after
 // unit0 was summed (knz_read_settle) has units with nothing in them: they are skipped.
 // The 64 units of a wave lie side by side and in one segment or a few neighbours: the wave searches once for its first and once for
@@ -350,29 +356,25 @@ template <class T> __device__ __forceinline__ int knz_read_find(const T* __restr
   while (a < b) { const int m = (a + b) >> 1; if (seg[m].unit0 <= u) a = m + 1; else b = m; }
   return a - 1;
 }
+// the segment of unit u among seg[0 .. ns), by that scheme: the table's address stays the kernel's argument in all three searches
+template <class T> __device__ __forceinline__ int knz_wave_find(const T* __restrict__ seg, int ns, int64_t u) {
+  const int64_t u0 = knz_first_lane(u);                                               // the wave's units: at most 64 in a row from its first lane's
+  const int jlo = knz_read_find(seg, 0, ns - 1, u0);
+  int jhi = jlo;                                                                      // (every segment has a unit: 63 units on are at most 63 segments on)
+  if (jlo + 1 < ns && seg[jlo + 1].unit0 <= u0 + 63) jhi = knz_read_find(seg, jlo + 1, jlo + 63 < ns - 1 ? jlo + 63 : ns - 1, u0 + 63);
+  return knz_read_find(seg, jlo, jhi, u);
+}
 __global__ void __launch_bounds__(256) k_knz_read(const u8* __restrict__ rows, int64_t stride, int rowLen, const KnzReadSeg* __restrict__ seg, int ns,
                                                   u8* __restrict__ dst, int64_t unitBase, int64_t units) {
   for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < units; v += (int64_t)gridDim.x * blockDim.x) {
     const int64_t u = unitBase + v;
-    const int64_t u0 = knz_first_lane(u);                                             // the wave's units: at most 64 in a row from its first lane's
-    const int jlo = knz_read_find(seg, 0, ns - 1, u0);
-    int jhi = jlo;                                                                    // (every segment has a unit: 63 units on are at most 63 segments on)
-    if (jlo + 1 < ns && seg[jlo + 1].unit0 <= u0 + 63) jhi = knz_read_find(seg, jlo + 1, jlo + 63 < ns - 1 ? jlo + 63 : ns - 1, u0 + 63);
-    const int j = knz_read_find(seg, jlo, jhi, u);
-    const KnzReadSeg g = seg[j];
+    const KnzReadSeg g = seg[knz_wave_find(seg, ns, u)];
     u8* d = dst + g.dst;
     const uintptr_t A0 = (uintptr_t)d & ~(uintptr_t)15;
-    const int64_t ub = (int64_t)(A0 - (uintptr_t)d) + ((u - g.unit0) << 4);           // the unit's first byte as an index into the segment (may be < 0)
-    const int64_t lo = ub < 0 ? 0 : ub, hi = ub + 16 > g.len ? g.len : ub + 16;
-    if (lo >= hi) continue;
+    const int64_t ub = (int64_t)(A0 - (uintptr_t)d) + ((u - g.unit0) << 4);
+    if (ub >= g.len) continue;                                                        // a unit of a segment that was cut: before the row's address is formed
     const u8* row = rows + (int64_t)g.slot * stride;
-    const u8* s = row + g.off;
-    if (hi - lo == 16) {
-      const u8* p = s + lo;
-      const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
-      if (al >= row && al + knz_window(p, 0) <= row + rowLen) { *(uint4*)(d + lo) = knz_load128(p, 0); continue; }
-    }
-    for (int64_t b = lo; b < hi; b++) d[b] = s[b];
+    knz_copy_unit(d, row + g.off, g.len, ub, row, row + rowLen);
   }
 }
 
@@ -380,33 +382,18 @@ __global__ void __launch_bounds__(256) k_knz_read(const u8* __restrict__ rows, i
 // k_knz_read's mirror image.  Segment j (kz_knz_host.h: KnzWriteSeg) is seg[j].len bytes from data + seg[j].src (any alignment) to
 // byte seg[j].off of the row rows + seg[j].slot * stride (rows 16-byte aligned, stride a multiple of 16).  The launch's work is the
 // 16-byte aligned units of the ROW side of all its segments, one segment after the other (seg[j].unit0, the launch owns
-// [unitBase, unitBase + units), seg[0].unit0 == unitBase); a lane finds its segment with the read's wave-narrowed search.  A unit
-// wholly inside its segment is one wide store of aligned 32-bit loads, if that load window stays inside data[0 .. dataLen); any other
-// unit goes bytewise, the segment's own bytes only.  The plan made the segments disjoint (the later range has already won there), so
+// [unitBase, unitBase + units), seg[0].unit0 == unitBase); a lane finds its segment with the read's wave-narrowed search
+// (knz_wave_find) and copies the unit (knz_copy_unit) with data[0 .. dataLen) as the window of its aligned loads.  The plan made the segments disjoint (the later range has already won there), so
 // every byte of a row has one writer and no order between lanes, launches or segments is needed; bytes of a row that no segment
 // covers keep what the decode left in them.
 __global__ void __launch_bounds__(256) k_knz_write(const u8* __restrict__ data, int64_t dataLen, const KnzWriteSeg* __restrict__ seg, int ns,
                                                    u8* __restrict__ rows, int64_t stride, int64_t unitBase, int64_t units) {
   for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < units; v += (int64_t)gridDim.x * blockDim.x) {
     const int64_t u = unitBase + v;
-    const int64_t u0 = knz_first_lane(u);                                             // the wave's units: at most 64 in a row from its first lane's
-    const int jlo = knz_read_find(seg, 0, ns - 1, u0);
-    int jhi = jlo;                                                                    // (every segment has a unit: 63 units on are at most 63 segments on)
-    if (jlo + 1 < ns && seg[jlo + 1].unit0 <= u0 + 63) jhi = knz_read_find(seg, jlo + 1, jlo + 63 < ns - 1 ? jlo + 63 : ns - 1, u0 + 63);
-    const int j = knz_read_find(seg, jlo, jhi, u);
-    const KnzWriteSeg g = seg[j];
+    const KnzWriteSeg g = seg[knz_wave_find(seg, ns, u)];
     u8* d = rows + (int64_t)g.slot * stride + g.off;
     const uintptr_t A0 = (uintptr_t)d & ~(uintptr_t)15;
-    const int64_t ub = (int64_t)(A0 - (uintptr_t)d) + ((u - g.unit0) << 4);           // the unit's first byte as an index into the segment (may be < 0)
-    const int64_t lo = ub < 0 ? 0 : ub, hi = ub + 16 > g.len ? g.len : ub + 16;
-    if (lo >= hi) continue;
-    const u8* s = data + g.src;
-    if (hi - lo == 16) {
-      const u8* p = s + lo;
-      const u8* al = (const u8*)((uintptr_t)p & ~(uintptr_t)3);
-      if (al >= data && al + knz_window(p, 0) <= data + dataLen) { *(uint4*)(d + lo) = knz_load128(p, 0); continue; }
-    }
-    for (int64_t b = lo; b < hi; b++) d[b] = s[b];
+    knz_copy_unit(d, data + g.src, g.len, (int64_t)(A0 - (uintptr_t)d) + ((u - g.unit0) << 4), data, data + dataLen);
   }
 }
 

@@ -407,10 +407,26 @@ static inline int64_t knz_read_total(const int64_t* rangeLen, int32_t nRanges, i
   }
   return D;
 }
-// the decoded length block k must have: B[k + 1] - B[k]; without a table blockSize, and -1 (any length up to blockSize) for the last
-static inline int64_t knz_read_block_len(const int64_t* B, int32_t nIndex, int32_t blockSize, int32_t k) {
-  if (B) return B[k + 1] - B[k];
-  return k == nIndex - 1 ? -1 : blockSize;
+// The check of the length that block k decoded to, for both settles.  It must be B[k + 1] - B[k]; without a table blockSize, and any
+// length up to blockSize for the last.  0, -KZ_ERR_PROCESS_BLOCK (more than a block) or -KZ_ERR_INVALID_FILE (another length).
+static inline int knz_block_len_check(const int64_t* B, int32_t nIndex, int32_t blockSize, int32_t k, int64_t length) {
+  const int64_t want = B ? B[k + 1] - B[k] : (k == nIndex - 1 ? -1 : blockSize);
+  if (length > blockSize) return -KZ_ERR_PROCESS_BLOCK;
+  return want >= 0 && length != want ? -KZ_ERR_INVALID_FILE : 0;
+}
+// the block that holds byte o of the data
+static inline int64_t knz_block_of(const int64_t* B, int32_t nIndex, int32_t blockSize, int64_t o) {
+  return B ? (std::upper_bound(B, B + nIndex + 1, o) - B) - 1 : o / blockSize;
+}
+// The bytes [at, at + left) of the data cut at block ends, k = the block that holds byte `at`: piece(k, off, len) per block, off = the
+// piece's first byte in block k.
+template <class F> static inline void knz_cut_at_blocks(const int64_t* B, int32_t blockSize, int64_t k, int64_t at, int64_t left, F piece) {
+  for (; left > 0; k++) {
+    const int64_t b0 = B ? B[k] : k * blockSize, b1 = B ? B[k + 1] : b0 + blockSize;
+    const int64_t len = std::min<int64_t>(left, b1 - at);
+    piece(k, at - b0, len);
+    at += len; left -= len;
+  }
 }
 // The plan.  The arguments have passed knz_read_args and knz_read_table; CH >= 1 = blocks per chunk; dstPhase = dst's address mod
 // 16 (the host form passes 0: unit0 is the kernel's).  Ranges of no bytes and ranges that start at or behind P.end have no segment.
@@ -423,17 +439,15 @@ static inline void knz_read_plan(const int64_t* B, int32_t nIndex, int32_t block
   int64_t D = 0;
   for (int32_t i = 0; i < nRanges; i++) {
     const int64_t o = rangeOff[i];
-    int64_t left = o < P.end ? std::min<int64_t>(rangeLen[i], P.end - o) : 0, at = o, d = D;
+    const int64_t left = o < P.end ? std::min<int64_t>(rangeLen[i], P.end - o) : 0;
+    int64_t d = D;
     D += rangeLen[i];                                              // (<= dstCap: knz_read_total)
     if (left <= 0) continue;
-    int64_t k = B ? (std::upper_bound(B, B + nIndex + 1, o) - B) - 1 : o / blockSize;   // the block that holds byte o
-    for (; left > 0; k++) {
-      const int64_t b0 = B ? B[k] : k * blockSize, b1 = B ? B[k + 1] : b0 + blockSize;
-      const int64_t len = std::min<int64_t>(left, b1 - at);
-      all.push_back(KnzReadSeg{d, 0, 0, (int32_t)(at - b0), (int32_t)len, i});
+    knz_cut_at_blocks(B, blockSize, knz_block_of(B, nIndex, blockSize, o), o, left, [&](int64_t k, int64_t off, int64_t len) {
+      all.push_back(KnzReadSeg{d, 0, 0, (int32_t)off, (int32_t)len, i});
       blk.push_back((int32_t)k);
-      at += len; d += len; left -= len;
-    }
+      d += len;
+    });
   }
   P.blocks = blk;
   std::sort(P.blocks.begin(), P.blocks.end());
@@ -463,12 +477,8 @@ static inline void knz_read_plan(const int64_t* B, int32_t nIndex, int32_t block
 // got[]: the bytes delivered, or the status of the first failing block a range touches, in block order.  got[] starts as zeros.
 static inline void knz_read_settle(KnzReadPlan& P, int64_t c, int CH, const int64_t* B, int32_t nIndex, int32_t blockSize, kz_block_result* res, int64_t* got) {
   const int64_t b0 = c * CH, cnt = std::min<int64_t>(CH, (int64_t)P.blocks.size() - b0);
-  for (int64_t j = 0; j < cnt; j++) {
-    if (res[j].status) continue;
-    const int64_t want = knz_read_block_len(B, nIndex, blockSize, P.blocks[(size_t)(b0 + j)]);
-    if (res[j].length > blockSize) res[j].status = -KZ_ERR_PROCESS_BLOCK;
-    else if (want >= 0 && res[j].length != want) res[j].status = -KZ_ERR_INVALID_FILE;
-  }
+  for (int64_t j = 0; j < cnt; j++)
+    if (!res[j].status) res[j].status = knz_block_len_check(B, nIndex, blockSize, P.blocks[(size_t)(b0 + j)], res[j].length);
   for (int64_t i = P.first[(size_t)c]; i < P.first[(size_t)c + 1]; i++) {
     KnzReadSeg& s = P.segs[(size_t)i];
     const kz_block_result& r = res[s.slot];
@@ -571,17 +581,14 @@ static inline int32_t knz_write_plan(const int64_t* B, int32_t nIndex, int32_t b
   std::vector<int32_t> blk;                                        // the block of segs[i]
   std::vector<int64_t> have;                                       // surviving bytes per touched block
   for (const Piece& pc : pieces) {
-    int64_t at = pc.at, left = pc.len;
-    int64_t k = B ? (std::upper_bound(B, B + nIndex + 1, at) - B) - 1 : at / blockSize;   // the block that holds byte `at`
-    for (; left > 0; k++) {
-      const int64_t b0 = B ? B[k] : k * blockSize, b1 = B ? B[k + 1] : b0 + blockSize;
-      const int64_t len = std::min<int64_t>(left, b1 - at);
+    int64_t src = D[(size_t)pc.range] + (pc.at - rangeOff[pc.range]);
+    knz_cut_at_blocks(B, blockSize, knz_block_of(B, nIndex, blockSize, pc.at), pc.at, pc.len, [&](int64_t k, int64_t off, int64_t len) {
       if (P.blocks.empty() || P.blocks.back() != (int32_t)k) { P.blocks.push_back((int32_t)k); have.push_back(0); }
       have.back() += len;
-      P.segs.push_back(KnzWriteSeg{D[(size_t)pc.range] + (at - rangeOff[pc.range]), 0, (int32_t)((int64_t)(P.blocks.size() - 1) % CH), (int32_t)(at - b0), (int32_t)len, pc.range});
+      P.segs.push_back(KnzWriteSeg{src, 0, (int32_t)((int64_t)(P.blocks.size() - 1) % CH), (int32_t)off, (int32_t)len, pc.range});
       blk.push_back((int32_t)(P.blocks.size() - 1));
-      at += len; left -= len;
-    }
+      src += len;
+    });
   }
   P.covered.resize(P.blocks.size());
   for (size_t i = 0; i < P.blocks.size(); i++) P.covered[i] = (B && have[i] == B[P.blocks[i] + 1] - B[P.blocks[i]]) ? 1 : 0;
@@ -601,6 +608,16 @@ static inline int32_t knz_write_plan(const int64_t* B, int32_t nIndex, int32_t b
     }
   return -1;
 }
+// The results of the wholly covered blocks among blocks[b0 .. b0 + cnt), which are not decoded: before the chunk's decode status 1
+// (left out of it), behind it (decoded) status 0 and the table's length, as if they had been.
+static inline void knz_write_covered(const KnzWritePlan& P, int64_t b0, int cnt, const int64_t* B, bool decoded, kz_block_result* res) {
+  for (int i = 0; i < cnt; i++) {
+    if (!P.covered[(size_t)(b0 + i)]) continue;
+    const int32_t k = P.blocks[(size_t)(b0 + i)];
+    memset(&res[i], 0, sizeof(res[i]));
+    if (decoded) res[i].length = (int32_t)(B[k + 1] - B[k]); else res[i].status = 1;
+  }
+}
 // After chunk c has been decoded (res[j]: the result of its block j; the caller gave a wholly covered block status 0 and the table's
 // length): the length check of every block as knz_read_settle makes it, and, without a table, the segments against the real end of a
 // short last block.  lens[j] = the bytes of row j when the chunk is patched.  Returns 0, or the code of the first failing block in
@@ -610,11 +627,10 @@ static inline int knz_write_settle(const KnzWritePlan& P, int64_t c, int CH, con
   const int64_t b0 = c * CH, cnt = std::min<int64_t>(CH, (int64_t)P.blocks.size() - b0);
   for (int64_t j = 0; j < cnt; j++) {
     const int32_t k = P.blocks[(size_t)(b0 + j)];
-    const int64_t want = knz_read_block_len(B, nIndex, blockSize, k);
     const char* why = "its decode failed";
     if (!res[j].status) {
-      if (res[j].length > blockSize) { res[j].status = -KZ_ERR_PROCESS_BLOCK; why = "decodes to more than the block size"; }
-      else if (want >= 0 && res[j].length != want) { res[j].status = -KZ_ERR_INVALID_FILE; why = "decodes to another length than its place in the data"; }
+      res[j].status = knz_block_len_check(B, nIndex, blockSize, k, res[j].length);
+      why = res[j].status == -KZ_ERR_PROCESS_BLOCK ? "decodes to more than the block size" : "decodes to another length than its place in the data";
     }
     if (res[j].status) {
       if (err) snprintf(err, errCap, "block %d: %s (%d)", (int)k, why, (int)res[j].status);
@@ -629,3 +645,21 @@ static inline int knz_write_settle(const KnzWritePlan& P, int64_t c, int CH, con
     }
   return 0;
 }
+// The layout of blocks [k0, k1) of the rewritten stream from bit `pos` on.  touched = the plan's blocks (ascending), t = the first of
+// them at or behind k0 (it moves on with the walk), t1 = the end of those that are recoded here; eW[0 ..] = the recoded blocks' bits
+// from touched[t] on.  Every other block keeps its blockBits[k].  Per block, block(k, r, W, pay): r = its place in touched when it is
+// recoded, else -1; W = its bits; pay = the bit where its payload starts, behind its 5 + lw prefix bits.  Returns the bit behind the
+// last block: with a callback that does nothing this is the room decision, made before a bit is written.
+template <class F> static inline int64_t knz_write_walk(const int64_t* blockBits, const int32_t* touched, int64_t k0, int64_t k1, int64_t& t, int64_t t1,
+                                                        const int64_t* eW, int64_t pos, F block) {
+  const int64_t tb = t;
+  for (int64_t k = k0; k < k1; k++) {
+    const bool rec = t < t1 && touched[t] == k;
+    const int64_t W = rec ? eW[t - tb] : blockBits[k];
+    pos += 5 + knz_prefix_width((uint64_t)W);
+    block(k, rec ? t++ : (int64_t)-1, W, pos);
+    pos += W;
+  }
+  return pos;
+}
+static inline void knz_write_walk_only(int64_t, int64_t, int64_t, int64_t) {}

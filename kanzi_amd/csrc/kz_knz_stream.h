@@ -1,5 +1,6 @@
 // kz_knz_stream.h -- what the host-buffer stream calls (kz_stream.hip) and the device-buffer ones (kz_stream_device.hip) share
-// beyond the host-only core: batch and chunk sizes, the plan of a reading call, and the scopes over the context's per-stream entries.
+// beyond the host-only core: batch and chunk sizes, the plan of a reading call, the scopes over the context's per-stream entries, and
+// the host arithmetic of the calls that read a stream by a caller's index.
 #pragma once
 #include "kz_internal.h"
 #include "kz_knz_host.h"
@@ -54,15 +55,45 @@ static void parallel_blocks(int n, F fn, int maxThreads = 32) {
   kz_parallel_for(n, maxThreads, &Thunk::run, (void*)&fn);
 }
 
-// the call that reads an index: the header's and the plan's faults, and a destination row that cannot hold a block
-static inline int indexed_open(kz_ctx* ctx, HostBitsIn& bs, int64_t n, int64_t dstStride, KnzPlan& P) {
+// ---- the steps of the calls that read a stream of n bytes by a caller's index (the indexed read, the byte-addressed read and write),
+//      as far as they are the same arithmetic for host and device memory; the rest is in kz_stream.hip and kz_stream_device.hip ----
+// The open: the stream header from bs (a reader over the stream's first bytes) with its faults and texts, and the plan.
+static inline int knz_open_plan(kz_ctx* ctx, HostBitsIn& bs, int64_t n, KnzPlan& P) {
   KnzHeader h;
   { const int hrc = read_stream_header(bs, h, ctx->err, sizeof(ctx->err)); if (hrc) return hrc; }
-  if (dstStride < h.blockSize) {
-    snprintf(ctx->err, sizeof(ctx->err), "dstStride %lld is less than the stream's block size %d", (long long)dstStride, h.blockSize);
-    return -KZ_ERR_INVALID_PARAM;
-  }
   P = knz_plan(ctx, h, n, (int64_t)bs.pos);
+  return 0;
+}
+// the indexed read's, behind the open: a destination row that cannot hold a block
+static inline int indexed_stride(kz_ctx* ctx, int64_t dstStride, const KnzPlan& P) {
+  if (dstStride >= P.h.blockSize) return 0;
+  snprintf(ctx->err, sizeof(ctx->err), "dstStride %lld is less than the stream's block size %d", (long long)dstStride, P.h.blockSize);
+  return -KZ_ERR_INVALID_PARAM;
+}
+// the byte-addressed calls': a blockByteOff that is no table of block starts, refused in the name of the call
+static inline int knz_table_refusal(kz_ctx* ctx, const char* call, const int64_t* blockByteOff, int32_t nIndex, int32_t blockSize) {
+  if (!knz_read_table(blockByteOff, nIndex, blockSize)) return 0;
+  snprintf(ctx->err, sizeof(ctx->err), "%s: blockByteOff is not a table of block starts", call);
+  return -KZ_ERR_INVALID_PARAM;
+}
+// the byte-addressed calls': (off[i], W[i]) = the index entry of the chunk's block blk[i]; zeros for one that is left out of the
+// decode (leftOut, may be null: the write's wholly covered blocks, whose entries are not looked at)
+static inline void knz_chunk_entries(const int32_t* blk, const uint8_t* leftOut, int cnt, const int64_t* blockBitOff, const int64_t* blockBits, int64_t* off, int64_t* W) {
+  for (int i = 0; i < cnt; i++) {
+    const bool out = leftOut && leftOut[i];
+    off[i] = out ? 0 : blockBitOff[blk[i]]; W[i] = out ? 0 : blockBits[blk[i]];
+  }
+}
+// the byte-addressed write's: eW[i] = the bits of the chunk's recoded block blk[i], or the code and the text of the first whose
+// encode failed
+static inline int knz_recoded_bits(kz_ctx* ctx, const int32_t* blk, const kz_block_result* eres, int cnt, int64_t* eW) {
+  for (int i = 0; i < cnt; i++) {
+    if (eres[i].status || eres[i].bits <= 0) {
+      snprintf(ctx->err, sizeof(ctx->err), "block %d: its encode failed (%d)", (int)blk[i], (int)eres[i].status);
+      return eres[i].status ? eres[i].status : -KZ_ERR_PROCESS_BLOCK;
+    }
+    eW[i] = eres[i].bits;
+  }
   return 0;
 }
 static inline int indexed_mismatch(kz_ctx* ctx, int64_t i) {

@@ -404,6 +404,42 @@ extern "C" int64_t kz_decompress_range(kz_ctx* ctx, const uint8_t* src, int64_t 
   return decompress_host(ctx, src, n, firstBlock, nBlocks, dst, dstCap);
 }
 
+// ---- the calls that read a stream by a caller's index: kz_decode_indexed, kz_read_bytes, kz_write_bytes.  Their steps, each once: the
+//      open (kz_knz_stream.h), every entry the call uses against the stream before anything is decoded, and the decode of a chunk.
+//      kz_stream_device.hip has the same three steps for device memory ----
+// entry(i) for i < count = the number of an entry in the caller's index, or -1 for one that the call does not look at
+template <class F> static int indexed_check_entries(kz_ctx* ctx, const uint8_t* src, int64_t n, const KnzPlan& P, const int64_t* blockBitOff, const int64_t* blockBits,
+                                                    int64_t count, F entry) {
+  for (int64_t i = 0; i < count; i++) {
+    const int64_t k = entry(i);
+    if (k >= 0 && !knz_check_entry(src, n, P.hdrEnd, blockBitOff[k], blockBits[k])) return indexed_mismatch(ctx, k);
+  }
+  return 0;
+}
+// A chunk of cnt entries (off[i], W[i]), bs a reader over the stream: the block-header prechecks into res[], the payloads of those
+// that pass into inbuf (rows P.iS apart), their decode into out rows `stride` apart.  An entry with leftOut[i] (may be null) is not
+// looked at: its res[i] is the caller's, with a status that is not 0.
+static int indexed_chunk(kz_ctx* ctx, const HostBitsIn& bs, const KnzPlan& P, const int64_t* off, const int64_t* W, const uint8_t* leftOut, int cnt,
+                         uint8_t* inbuf, uint8_t* out, int64_t stride, kz_block_result* res) {
+  for (int i = 0; i < cnt; i++) {
+    if (leftOut && leftOut[i]) continue;
+    HostBitsIn t = bs; t.pos = (uint64_t)off[i]; t.error = false;
+    const int rc = knz_check_block(t, (uint64_t)W[i], (uint64_t)off[i], t.nbits, P, false);   // (knz_check_entry saw the payload's end)
+    memset(&res[i], 0, sizeof(res[i]));
+    res[i].bits = W[i]; res[i].status = rc;
+  }
+  parallel_blocks(cnt, [&](int i) {
+    if (res[i].status) return;
+    HostBitsIn t = bs; t.pos = (uint64_t)off[i]; t.error = false; t.getBytes(inbuf + (size_t)i * P.iS, (uint64_t)W[i]);
+  });
+  return indexed_decode_runs(ctx, P, inbuf, W, cnt, out, stride, res, KZ_MEM_HOST);
+}
+// segments [s0, s1) of a chunk in up to 64 runs on the host pool: copy(i) per segment, in any order
+template <class F> static void segment_runs(int64_t s0, int64_t s1, F copy) {
+  const int64_t runs = std::min<int64_t>(s1 - s0, 64);
+  parallel_blocks((int)runs, [&](int q) { for (int64_t i = s0 + (s1 - s0) * q / runs; i < s0 + (s1 - s0) * (q + 1) / runs; i++) copy(i); });
+}
+
 // Indexed read: blocks of a stream by their (bit offset, bit length) pairs, as kz_knz_index / kz_knz_index_device return them, in
 // any order.  No walk: every pair is checked against the stream on its own (knz_check_entry), which makes the call memory safe for
 // any index; it does not prove that a pair lies on the chain of prefixes that starts behind the stream header.
@@ -413,50 +449,34 @@ extern "C" int32_t kz_decode_indexed(kz_ctx* ctx, const uint8_t* src, int64_t n,
   KZ_HIP(hipSetDevice(ctx->device));
   HostBitsIn bs{src, (uint64_t)n * 8, 0, false};
   KnzPlan P;
-  { const int rc = indexed_open(ctx, bs, n, dstStride, P); if (rc) return rc; }
+  { int rc = knz_open_plan(ctx, bs, n, P); if (!rc) rc = indexed_stride(ctx, dstStride, P); if (rc) return rc; }
   if (nBlocks == 0) return 0;
-  for (int64_t i = 0; i < nBlocks; i++) if (!knz_check_entry(src, n, P.hdrEnd, blockBitOff[i], blockBits[i])) return indexed_mismatch(ctx, i);
+  { const int rc = indexed_check_entries(ctx, src, n, P, blockBitOff, blockBits, nBlocks, [](int64_t i) { return i; }); if (rc) return rc; }
   ChecksumScope chk(ctx, P.h.chkKind);
   const int CH = (int)std::min<int64_t>(knz_chunk_blocks(ctx, P.h.blockSize), nBlocks);
   std::unique_ptr<uint8_t[]> inbuf(new uint8_t[(size_t)P.iS * CH]);
   for (int64_t b0 = 0; b0 < nBlocks; b0 += CH) {
     const int cnt = (int)std::min<int64_t>(CH, nBlocks - b0);
-    const int64_t* off = blockBitOff + b0; const int64_t* W = blockBits + b0;
-    kz_block_result* res = results + b0;
-    for (int i = 0; i < cnt; i++) {
-      HostBitsIn t = bs; t.pos = (uint64_t)off[i]; t.error = false;
-      const int rc = knz_check_block(t, (uint64_t)W[i], (uint64_t)off[i], t.nbits, P, false);   // (knz_check_entry saw the payload's end)
-      memset(&res[i], 0, sizeof(res[i]));
-      res[i].bits = W[i]; res[i].status = rc;
-    }
-    parallel_blocks(cnt, [&](int i) {
-      if (res[i].status) return;
-      HostBitsIn t = bs; t.pos = (uint64_t)off[i]; t.error = false; t.getBytes(inbuf.get() + (size_t)i * P.iS, (uint64_t)W[i]);
-    });
-    const int rc = indexed_decode_runs(ctx, P, inbuf.get(), W, cnt, dst + b0 * dstStride, dstStride, res, KZ_MEM_HOST);
+    const int rc = indexed_chunk(ctx, bs, P, blockBitOff + b0, blockBits + b0, nullptr, cnt, inbuf.get(), dst + b0 * dstStride, dstStride, results + b0);
     if (rc) return rc;
   }
   return 0;
 }
 
 // Byte-addressed read: many ranges [off, off + len) of the original data in one call.  The plan (kz_knz_host.h) names the distinct
-// covering blocks and the range x block segments, chunk by chunk; the steps are the indexed read's: every entry the plan uses is
-// checked against the stream before anything is decoded, then per chunk the prechecks, the decode into host rows, and a memcpy per
-// segment out of those rows.  kz_read_bytes_device (kz_stream_device.hip) is the same call on device memory.
+// covering blocks and the range x block segments, chunk by chunk; the shared steps above do the open, the check of every entry the
+// plan uses and the decode of a chunk into host rows; what is the read's own is a memcpy per segment out of those rows.
+// kz_read_bytes_device (kz_stream_device.hip) is the same call on device memory.
 extern "C" int64_t kz_read_bytes(kz_ctx* ctx, const uint8_t* src, int64_t n, const int64_t* blockBitOff, const int64_t* blockBits, const int64_t* blockByteOff,
                                  int32_t nIndex, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges, uint8_t* dst, int64_t dstCap, int64_t* got) {
   if (!ctx) return -KZ_ERR_INVALID_PARAM;
   { const int rc = knz_read_args(src, n, blockBitOff, blockBits, nIndex, rangeOff, rangeLen, nRanges, dst, dstCap, got); if (rc) return rc; }
   KZ_HIP(hipSetDevice(ctx->device));
   HostBitsIn bs{src, (uint64_t)n * 8, 0, false};
-  KnzHeader h;
-  { const int hrc = read_stream_header(bs, h, ctx->err, sizeof(ctx->err)); if (hrc) return hrc; }
-  const KnzPlan P = knz_plan(ctx, h, n, (int64_t)bs.pos);
-  const int32_t blockSize = h.blockSize;
-  if (knz_read_table(blockByteOff, nIndex, blockSize)) {
-    snprintf(ctx->err, sizeof(ctx->err), "kz_read_bytes: blockByteOff is not a table of block starts");
-    return -KZ_ERR_INVALID_PARAM;
-  }
+  KnzPlan P;
+  { const int rc = knz_open_plan(ctx, bs, n, P); if (rc) return rc; }
+  const int32_t blockSize = P.h.blockSize;
+  { const int rc = knz_table_refusal(ctx, "kz_read_bytes", blockByteOff, nIndex, blockSize); if (rc) return rc; }
   const int64_t total = knz_read_total(rangeLen, nRanges, dstCap);
   if (total < 0) { snprintf(ctx->err, sizeof(ctx->err), "kz_read_bytes: destination too small"); return total; }
   if (nRanges == 0) return 0;
@@ -466,38 +486,20 @@ extern "C" int64_t kz_read_bytes(kz_ctx* ctx, const uint8_t* src, int64_t n, con
   for (int32_t i = 0; i < nRanges; i++) got[i] = 0;
   const int64_t nb = (int64_t)R.blocks.size();
   if (nb == 0) return total;
-  for (int64_t i = 0; i < nb; i++) {
-    const int32_t k = R.blocks[(size_t)i];
-    if (!knz_check_entry(src, n, P.hdrEnd, blockBitOff[k], blockBits[k])) return indexed_mismatch(ctx, k);
-  }
-  ChecksumScope chk(ctx, h.chkKind);
+  { const int rc = indexed_check_entries(ctx, src, n, P, blockBitOff, blockBits, nb, [&](int64_t i) { return (int64_t)R.blocks[(size_t)i]; }); if (rc) return rc; }
+  ChecksumScope chk(ctx, P.h.chkKind);
   const int cmax = (int)std::min<int64_t>(CH, nb);
   std::unique_ptr<uint8_t[]> inbuf(new uint8_t[(size_t)P.iS * cmax]), rows(new uint8_t[(size_t)blockSize * cmax]);
   std::vector<kz_block_result> res((size_t)cmax);
   std::vector<int64_t> W((size_t)cmax), off((size_t)cmax);
   for (int64_t b0 = 0, c = 0; b0 < nb; b0 += CH, c++) {
     const int cnt = (int)std::min<int64_t>(CH, nb - b0);
-    for (int i = 0; i < cnt; i++) {
-      const int32_t k = R.blocks[(size_t)(b0 + i)];
-      off[i] = blockBitOff[k]; W[i] = blockBits[k];
-      HostBitsIn t = bs; t.pos = (uint64_t)off[i]; t.error = false;
-      const int rc = knz_check_block(t, (uint64_t)W[i], (uint64_t)off[i], t.nbits, P, false);   // (knz_check_entry saw the payload's end)
-      memset(&res[i], 0, sizeof(res[i]));
-      res[i].bits = W[i]; res[i].status = rc;
-    }
-    parallel_blocks(cnt, [&](int i) {
-      if (res[i].status) return;
-      HostBitsIn t = bs; t.pos = (uint64_t)off[i]; t.error = false; t.getBytes(inbuf.get() + (size_t)i * P.iS, (uint64_t)W[i]);
-    });
-    { const int rc = indexed_decode_runs(ctx, P, inbuf.get(), W.data(), cnt, rows.get(), blockSize, res.data(), KZ_MEM_HOST); if (rc) return rc; }
+    knz_chunk_entries(&R.blocks[(size_t)b0], nullptr, cnt, blockBitOff, blockBits, off.data(), W.data());
+    { const int rc = indexed_chunk(ctx, bs, P, off.data(), W.data(), nullptr, cnt, inbuf.get(), rows.get(), blockSize, res.data()); if (rc) return rc; }
     knz_read_settle(R, c, CH, blockByteOff, nIndex, blockSize, res.data(), got);
-    const int64_t s0 = R.first[(size_t)c], s1 = R.first[(size_t)c + 1];
-    parallel_blocks((int)std::min<int64_t>(s1 - s0, 64), [&](int q) {                     // the chunk's segments in up to 64 runs
-      const int64_t runs = std::min<int64_t>(s1 - s0, 64);
-      for (int64_t i = s0 + (s1 - s0) * q / runs; i < s0 + (s1 - s0) * (q + 1) / runs; i++) {
-        const KnzReadSeg& g = R.segs[(size_t)i];
-        if (g.len > 0) memcpy(dst + g.dst, rows.get() + (size_t)g.slot * blockSize + g.off, (size_t)g.len);
-      }
+    segment_runs(R.first[(size_t)c], R.first[(size_t)c + 1], [&](int64_t i) {
+      const KnzReadSeg& g = R.segs[(size_t)i];
+      if (g.len > 0) memcpy(dst + g.dst, rows.get() + (size_t)g.slot * blockSize + g.off, (size_t)g.len);
     });
   }
   return total;
@@ -505,10 +507,11 @@ extern "C" int64_t kz_read_bytes(kz_ctx* ctx, const uint8_t* src, int64_t n, con
 
 // Byte-addressed write: many ranges [off, off + len) of the original data replaced by new bytes in one call, the result a new stream.
 // The plan (kz_knz_host.h) resolves "the later range wins" into disjoint segments and names the touched blocks and which of them are
-// wholly covered; every entry the call uses is checked against the stream before anything is decoded, then per chunk of touched
-// blocks the read's steps up to the decode into host rows, a memcpy per segment into those rows, one batched encode of the rows, and
-// the splice's bit copy of every kept block since the previous chunk with the recoded ones.  kz_write_bytes_device
-// (kz_stream_device.hip) is the same call on device memory, and this one is its reference.
+// wholly covered.  The shared steps above do the open, the check of every entry the call uses (a wholly covered block's is not looked
+// at) and, per chunk of touched blocks, the decode into host rows; the write's own are a memcpy per segment into those rows, one
+// batched encode of the rows, and the bit copy of every kept block since the previous chunk with the recoded ones, laid out by
+// knz_write_walk (kz_knz_host.h).  kz_write_bytes_device (kz_stream_device.hip) is the same call on device memory, and this one is its
+// reference.
 extern "C" int64_t kz_write_bytes_bound(const int64_t* blockBits, int32_t nIndex, int32_t blockSize) { return knz_write_bound(blockBits, nIndex, blockSize); }
 extern "C" int64_t kz_write_bytes(kz_ctx* ctx, const uint8_t* src, int64_t n, const int64_t* blockBitOff, const int64_t* blockBits, const int64_t* blockByteOff,
                                   int32_t nIndex, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges, const uint8_t* data, int64_t dataLen,
@@ -517,21 +520,20 @@ extern "C" int64_t kz_write_bytes(kz_ctx* ctx, const uint8_t* src, int64_t n, co
   { const int rc = knz_write_args(src, n, blockBitOff, blockBits, nIndex, rangeOff, rangeLen, nRanges, data, dataLen, dst, dstCap, newBitOff, newBits); if (rc) return rc; }
   KZ_HIP(hipSetDevice(ctx->device));
   HostBitsIn bs{src, (uint64_t)n * 8, 0, false};
-  KnzHeader h;
-  { const int hrc = read_stream_header(bs, h, ctx->err, sizeof(ctx->err)); if (hrc) return hrc; }
-  const KnzPlan P = knz_plan(ctx, h, n, (int64_t)bs.pos);
+  KnzPlan P;
+  { const int rc = knz_open_plan(ctx, bs, n, P); if (rc) return rc; }
+  const KnzHeader& h = P.h;
   const int32_t blockSize = h.blockSize;
-  if (knz_read_table(blockByteOff, nIndex, blockSize)) {
-    snprintf(ctx->err, sizeof(ctx->err), "kz_write_bytes: blockByteOff is not a table of block starts");
-    return -KZ_ERR_INVALID_PARAM;
-  }
+  { const int rc = knz_table_refusal(ctx, "kz_write_bytes", blockByteOff, nIndex, blockSize); if (rc) return rc; }
   const int CH = knz_chunk_blocks(ctx, blockSize);
   KnzWritePlan R;
   { const int32_t bad = knz_write_plan(blockByteOff, nIndex, blockSize, rangeOff, rangeLen, nRanges, CH, INT64_MAX, R); if (bad >= 0) return knz_write_behind(bad, ctx->err, sizeof(ctx->err)); }
   const int64_t nb = (int64_t)R.blocks.size();
-  for (int64_t k = 0, t = 0; k < nIndex; k++) {                   // every entry the call uses: the kept blocks' and the decoded ones'
-    if (t < nb && R.blocks[(size_t)t] == k && R.covered[(size_t)t++]) continue;
-    if (!knz_check_entry(src, n, P.hdrEnd, blockBitOff[k], blockBits[k])) return indexed_mismatch(ctx, k);
+  {                                                                // every entry the call uses: the kept blocks' and the decoded ones'
+    int64_t t = 0;
+    const int rc = indexed_check_entries(ctx, src, n, P, blockBitOff, blockBits, nIndex,
+                                         [&](int64_t k) { return (t < nb && R.blocks[(size_t)t] == k && R.covered[(size_t)t++]) ? (int64_t)-1 : k; });
+    if (rc) return rc;
   }
   ChecksumScope chk(ctx, h.chkKind);
   BlockSizeScope scope(ctx, blockSize);
@@ -540,7 +542,7 @@ extern "C" int64_t kz_write_bytes(kz_ctx* ctx, const uint8_t* src, int64_t n, co
   std::unique_ptr<uint8_t[]> inbuf, rows, enc;
   if (nb) { inbuf.reset(new uint8_t[(size_t)P.iS * cmax]); rows.reset(new uint8_t[(size_t)blockSize * cmax]); enc.reset(new uint8_t[(size_t)oS * cmax]); }
   std::vector<kz_block_result> res((size_t)cmax), eres((size_t)cmax);
-  std::vector<int64_t> W((size_t)cmax), off((size_t)cmax);
+  std::vector<int64_t> W((size_t)cmax), off((size_t)cmax), eW((size_t)cmax);
   std::vector<int32_t> lens((size_t)cmax);
   auto tooSmall = [&]() { snprintf(ctx->err, sizeof(ctx->err), "kz_write_bytes: destination too small"); return (int64_t)-KZ_ERR_WRITE_FILE; };
   HostBits out{dst, dstCap, 0, false};
@@ -554,24 +556,19 @@ extern "C" int64_t kz_write_bytes(kz_ctx* ctx, const uint8_t* src, int64_t n, co
   // blocks [k0, k1) behind what has been written, the touched ones t0 .. t1 of the list from the encoder's rows; then tailBits zero
   // bits.  Decided from the bit arithmetic before a bit of them is written: -KZ_ERR_WRITE_FILE when they do not fit.
   auto emit = [&](int64_t k0, int64_t k1, int64_t t0, int64_t t1, int tailBits) -> int {
-    int64_t end = pos, t = t0;
-    for (int64_t k = k0; k < k1; k++) {
-      const int64_t w = (t < t1 && R.blocks[(size_t)t] == k) ? eres[(size_t)(t++ - t0)].bits : blockBits[k];
-      end += 5 + knz_prefix_width((uint64_t)w) + w;
-    }
+    int64_t t = t0;
+    const int64_t end = knz_write_walk(blockBits, R.blocks.data(), k0, k1, t, t1, eW.data(), pos, knz_write_walk_only);
     if (((end + tailBits + 7) >> 3) > dstCap) return -KZ_ERR_WRITE_FILE;
     if (out.pos == 0) write_stream_header(out, h.transformType, (uint32_t)h.entropyType, blockSize, h.inputSize, h.chkKind);
     t = t0;
-    for (int64_t k = k0; k < k1; k++) {
-      const bool rec = t < t1 && R.blocks[(size_t)t] == k;
-      const int64_t w = rec ? eres[(size_t)(t - t0)].bits : blockBits[k];
+    knz_write_walk(blockBits, R.blocks.data(), k0, k1, t, t1, eW.data(), pos, [&](int64_t k, int64_t r, int64_t w, int64_t pay) {
       const int lw = knz_prefix_width((uint64_t)w);
       out.put((uint64_t)(lw - 3), 5);
       out.put((uint64_t)w, lw);
-      if (newBitOff) { newBitOff[k] = (int64_t)out.pos; newBits[k] = w; }
-      if (rec) out.putBytes(enc.get() + (size_t)(t++ - t0) * oS, (uint64_t)w);
+      if (newBitOff) { newBitOff[k] = pay; newBits[k] = w; }
+      if (r >= 0) out.putBytes(enc.get() + (size_t)(r - t0) * oS, (uint64_t)w);
       else knz_copy_bits(out, src, n, blockBitOff[k], w);
-    }
+    });
     if (tailBits) write_end_marker(out);
     pos = end + tailBits;
     return out.overflow ? -KZ_ERR_WRITE_FILE : 0;
@@ -579,39 +576,20 @@ extern "C" int64_t kz_write_bytes(kz_ctx* ctx, const uint8_t* src, int64_t n, co
   int64_t next = 0;                                               // the first block not yet in the new stream
   for (int64_t b0 = 0, c = 0; b0 < nb; b0 += CH, c++) {
     const int cnt = (int)std::min<int64_t>(CH, nb - b0);
-    for (int i = 0; i < cnt; i++) {
-      const int32_t k = R.blocks[(size_t)(b0 + i)];
-      memset(&res[i], 0, sizeof(res[i]));
-      if (R.covered[(size_t)(b0 + i)]) { W[i] = 0; off[i] = 0; res[i].status = 1; continue; }         // (1: left out of the decode)
-      off[i] = blockBitOff[k]; W[i] = blockBits[k];
-      HostBitsIn t = bs; t.pos = (uint64_t)off[i]; t.error = false;
-      const int rc = knz_check_block(t, (uint64_t)W[i], (uint64_t)off[i], t.nbits, P, false);         // (knz_check_entry saw the payload's end)
-      res[i].bits = W[i]; res[i].status = rc;
-    }
-    parallel_blocks(cnt, [&](int i) {
-      if (res[i].status) return;
-      HostBitsIn t = bs; t.pos = (uint64_t)off[i]; t.error = false; t.getBytes(inbuf.get() + (size_t)i * P.iS, (uint64_t)W[i]);
-    });
-    { const int rc = indexed_decode_runs(ctx, P, inbuf.get(), W.data(), cnt, rows.get(), blockSize, res.data(), KZ_MEM_HOST); if (rc) return rc; }
-    for (int i = 0; i < cnt; i++)
-      if (R.covered[(size_t)(b0 + i)]) { const int32_t k = R.blocks[(size_t)(b0 + i)]; res[i].status = 0; res[i].length = (int32_t)(blockByteOff[k + 1] - blockByteOff[k]); }
+    const uint8_t* covered = &R.covered[(size_t)b0];
+    knz_chunk_entries(&R.blocks[(size_t)b0], covered, cnt, blockBitOff, blockBits, off.data(), W.data());
+    knz_write_covered(R, b0, cnt, blockByteOff, false, res.data());
+    { const int rc = indexed_chunk(ctx, bs, P, off.data(), W.data(), covered, cnt, inbuf.get(), rows.get(), blockSize, res.data()); if (rc) return rc; }
+    knz_write_covered(R, b0, cnt, blockByteOff, true, res.data());
     { const int rc = knz_write_settle(R, c, CH, blockByteOff, nIndex, blockSize, res.data(), lens.data(), ctx->err, sizeof(ctx->err)); if (rc) return rc; }
-    const int64_t s0 = R.first[(size_t)c], s1 = R.first[(size_t)c + 1];
-    parallel_blocks((int)std::min<int64_t>(s1 - s0, 64), [&](int q) {                     // the chunk's segments in up to 64 runs: disjoint, so in any order
-      const int64_t runs = std::min<int64_t>(s1 - s0, 64);
-      for (int64_t i = s0 + (s1 - s0) * q / runs; i < s0 + (s1 - s0) * (q + 1) / runs; i++) {
-        const KnzWriteSeg& g = R.segs[(size_t)i];
-        memcpy(rows.get() + (size_t)g.slot * blockSize + g.off, data + g.src, (size_t)g.len);
-      }
+    segment_runs(R.first[(size_t)c], R.first[(size_t)c + 1], [&](int64_t i) {           // disjoint, so in any order
+      const KnzWriteSeg& g = R.segs[(size_t)i];
+      memcpy(rows.get() + (size_t)g.slot * blockSize + g.off, data + g.src, (size_t)g.len);
     });
     {
-      const int rc = kz_encode_blocks_pre(ctx, h.transformType, (uint32_t)h.entropyType, blockSize, rows.get(), blockSize, lens.data(), cnt, enc.get(), oS, eres.data(), KZ_MEM_HOST, nullptr);
+      int rc = kz_encode_blocks_pre(ctx, h.transformType, (uint32_t)h.entropyType, blockSize, rows.get(), blockSize, lens.data(), cnt, enc.get(), oS, eres.data(), KZ_MEM_HOST, nullptr);
+      if (!rc) rc = knz_recoded_bits(ctx, &R.blocks[(size_t)b0], eres.data(), cnt, eW.data());
       if (rc) return rc;
-      for (int i = 0; i < cnt; i++)
-        if (eres[i].status || eres[i].bits <= 0) {
-          snprintf(ctx->err, sizeof(ctx->err), "block %d: its encode failed (%d)", (int)R.blocks[(size_t)(b0 + i)], (int)eres[i].status);
-          return eres[i].status ? eres[i].status : -KZ_ERR_PROCESS_BLOCK;
-        }
     }
     const int64_t k1 = (int64_t)R.blocks[(size_t)(b0 + cnt - 1)] + 1;
     if (emit(next, k1, b0, b0 + cnt, 0)) return tooSmall();
@@ -620,4 +598,3 @@ extern "C" int64_t kz_write_bytes(kz_ctx* ctx, const uint8_t* src, int64_t n, co
   if (emit(next, nIndex, nb, nb, 8)) return tooSmall();            // the kept tail and the end marker
   return (int64_t)((out.pos + 7) >> 3);
 }
-

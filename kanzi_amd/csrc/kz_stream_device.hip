@@ -1,5 +1,6 @@
 // kz_stream_device.hip -- the .knz container with source and destination in HBM: the same streams as kz_stream.hip's calls write and
-// read, whole, by block range, by index, and many at a time, edits them without recoding (the splice), and rewrites byte ranges of their data (kz_write_bytes_device).  The kernels are in kz_knz_gpu.hip; what stays on the host is what
+// read, whole, by block range, by index, and many at a time, edits them without recoding (the splice), and reads and rewrites byte
+// ranges of their data (kz_read_bytes_device, kz_write_bytes_device).  The kernels are in kz_knz_gpu.hip; what stays on the host is what
 // kz_compress / kz_decompress do there as well and costs nothing: the stream header (kz_knz_host.h, on a copy of at most 26 bytes),
 // the bit-offset arithmetic over results[] (host arrays anyway), and the block checks on the 8 header bytes per block that the walk
 // kernel brings back.  The rules shared with the host-buffer calls are in kz_knz_host.h and kz_knz_stream.h.
@@ -76,6 +77,12 @@ int knz_open(kz_ctx* ctx, const uint8_t* d_src, int64_t n, uint8_t* hdr /*32*/, 
   { const int rc = knz_get_header(ctx, d_src, n, hdr, hn); if (rc) return rc; }
   bs = HostBitsIn{hdr, (uint64_t)hn * 8, 0, false};
   return 0;
+}
+// the open of a reading call: the stream header of d_src with its faults and texts, and the plan
+int knz_open_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, KnzPlan& P) {
+  uint8_t hdr[32]; HostBitsIn bs;
+  { const int rc = knz_open(ctx, d_src, n, hdr, bs); if (rc) return rc; }
+  return knz_open_plan(ctx, bs, n, P);
 }
 }  // namespace
 
@@ -205,11 +212,9 @@ extern "C" int32_t kz_knz_index_device(kz_ctx* ctx, const uint8_t* d_src, int64_
 // carry the batch's count of blocks that may still start inside dst: both calls cut a stream at the same block.
 static int64_t decompress_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, int64_t firstBlock, int64_t nBlocks, uint8_t* d_dst, int64_t dstCap) {
   KZ_HIP(hipSetDevice(ctx->device));
-  uint8_t hdr[32]; HostBitsIn bs;
-  { const int rc = knz_open(ctx, d_src, n, hdr, bs); if (rc) return rc; }
-  KnzHeader h;
-  { const int hrc = read_stream_header(bs, h, ctx->err, sizeof(ctx->err)); if (hrc) return hrc; }
-  const KnzPlan P = knz_plan(ctx, h, n, (int64_t)bs.pos);
+  KnzPlan P;
+  { const int rc = knz_open_device(ctx, d_src, n, P); if (rc) return rc; }
+  const KnzHeader& h = P.h;
   const int entropyType = h.entropyType, blockSize = h.blockSize, CH = P.CH;
   const uint64_t tt = h.transformType, nbits = (uint64_t)n * 8;
   const int64_t iS = P.iS;
@@ -664,61 +669,84 @@ extern "C" int32_t kz_decompress_many_device(kz_ctx* ctx, const uint8_t* d_src, 
 // any order.  No walk: every pair is checked against the stream on its own (k_knz_check), which makes the call memory safe for any
 // index and brings the block-header bytes for the prechecks; it does not prove that a pair lies on the chain of prefixes that
 // starts behind the stream header.
+// The indexed read, the byte-addressed read and the byte-addressed write share three steps, each written once here: the open
+// (knz_open_device), the check of every entry the call uses, and the decode of a chunk.  kz_stream.hip has the same three for host memory.
+namespace {
+// What entry i of a call's list is: its number in the caller's index (-1: an entry the call does not look at) and where its
+// block-header word is kept for the prechecks (null: nowhere).
+struct KnzEntry { int64_t k; uint64_t* hdr; };
+// Every entry the call uses against the stream (k_knz_check), T.cap entries per launch, before anything is unpacked: entry(i) for
+// i < count, called once each and in order.  The code and the text of the first entry that does not match, or 0.
+template <class F> int knz_check_entries(kz_ctx* ctx, const KnzTable& T, const uint8_t* d_src, int64_t n, const KnzPlan& P, const int64_t* blockBitOff,
+                                         const int64_t* blockBits, int64_t count, F entry) {
+  std::vector<KnzEntry> e((size_t)T.cap);
+  for (int64_t b0 = 0; b0 < count; b0 += T.cap) {
+    const int cnt = (int)std::min<int64_t>(T.cap, count - b0);
+    for (int i = 0; i < cnt; i++) {
+      e[i] = entry(b0 + i);
+      T.off()[i] = e[i].k < 0 ? 0 : blockBitOff[e[i].k]; T.bits()[i] = e[i].k < 0 ? 0 : blockBits[e[i].k];
+    }
+    KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+    KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+    { const int rc = kz_knz_check(ctx, d_src, n, P.hdrEnd, T.d_off(), T.d_bits(), cnt, T.d_hdr(), T.d_bad()); if (rc) return rc; }
+    KZ_HIP(hipMemcpyAsync(T.hdr(), T.d_hdr(), (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(hipMemcpyAsync(T.bad(), T.d_bad(), (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));                      // the pinned table is the next launch's
+    kz_ktimer_flush(ctx);
+    for (int i = 0; i < cnt; i++) {
+      if (e[i].k < 0) continue;
+      if (T.bad()[i]) return indexed_mismatch(ctx, e[i].k);
+      if (e[i].hdr) *e[i].hdr = T.hdr()[i];
+    }
+  }
+  return 0;
+}
+// A chunk of cnt <= T.cap entries (off[i], W[i]) with their block-header words hdrs[i]: the prechecks on the host into res[], the
+// unpack of the entries that pass into staging rows (ctx->devIn[0], P.iS apart), their decode into rows `stride` apart at d_out.  An
+// entry with leftOut[i] (may be null) is not looked at: its res[i] is the caller's, with a status that is not 0.  A chunk in which
+// nothing passes launches nothing.
+int knz_chunk_decode(kz_ctx* ctx, const KnzTable& T, const uint8_t* d_src, int64_t n, const KnzPlan& P, const int64_t* off, const int64_t* W, const uint64_t* hdrs,
+                     const uint8_t* leftOut, int cnt, uint8_t* d_out, int64_t stride, kz_block_result* res) {
+  int64_t maxBytes = 0;
+  for (int i = 0; i < cnt; i++) {
+    T.off()[i] = off[i];
+    T.bits()[i] = 0;                                                // a row of no bits: nothing of it is unpacked
+    if (leftOut && leftOut[i]) continue;
+    const int rc = knz_check_walked(hdrs[i], (uint64_t)W[i], (uint64_t)off[i], (uint64_t)n * 8, P);
+    memset(&res[i], 0, sizeof(res[i]));
+    res[i].bits = W[i]; res[i].status = rc;
+    if (!rc) { T.bits()[i] = W[i]; maxBytes = std::max<int64_t>(maxBytes, (W[i] + 7) >> 3); }
+  }
+  if (maxBytes == 0) return 0;
+  KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+  KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+  { const int rc = kz_stage_reserve(ctx, ctx->devIn[0], (size_t)cnt * P.iS, false); if (rc) return rc; }
+  { const int rc = kz_knz_unpack(ctx, d_src, n, T.d_off(), T.d_bits(), cnt, maxBytes, ctx->devIn[0].p, P.iS); if (rc) return rc; }
+  { const int rc = indexed_decode_runs(ctx, P, ctx->devIn[0].p, W, cnt, d_out, stride, res, KZ_MEM_DEVICE); if (rc) return rc; }
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));                        // the pinned table is the caller's again
+  kz_ktimer_flush(ctx);
+  return 0;
+}
+}  // namespace
+
 extern "C" int32_t kz_decode_indexed_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, const int64_t* blockBitOff, const int64_t* blockBits, int32_t nBlocks,
                                             uint8_t* d_dst, int64_t dstStride, kz_block_result* results) {
   if (!ctx || !d_src || n < 0 || nBlocks < 0 || (nBlocks > 0 && (!blockBitOff || !blockBits || !d_dst || !results))) return -KZ_ERR_INVALID_PARAM;
   KZ_HIP(hipSetDevice(ctx->device));
-  uint8_t hdr[32]; HostBitsIn bs;
-  { const int rc = knz_open(ctx, d_src, n, hdr, bs); if (rc) return rc; }
   KnzPlan P;
-  { const int rc = indexed_open(ctx, bs, n, dstStride, P); if (rc) return rc; }
+  { int rc = knz_open_device(ctx, d_src, n, P); if (!rc) rc = indexed_stride(ctx, dstStride, P); if (rc) return rc; }
   if (nBlocks == 0) return 0;
   ChecksumScope chk(ctx, P.h.chkKind);
   const int CH = (int)std::min<int64_t>(knz_chunk_blocks(ctx, P.h.blockSize), nBlocks);
   // the chunk's tables, pinned and in HBM: 64 spare bytes, then off[CH], bits[CH], hdr[CH], bad[CH]
   { const int rc = knz_tables(ctx, (size_t)CH * 32); if (rc) return rc; }
   const KnzTable T(ctx, CH);
-  // ---- every entry against the stream, before anything is unpacked; the block-header bytes stay on the host for the second pass ----
-  std::vector<uint64_t> hdrs((size_t)nBlocks);
+  std::vector<uint64_t> hdrs((size_t)nBlocks);                     // the block-header bytes stay on the host for the chunks' prechecks
+  { const int rc = knz_check_entries(ctx, T, d_src, n, P, blockBitOff, blockBits, nBlocks, [&](int64_t i) { return KnzEntry{i, &hdrs[(size_t)i]}; }); if (rc) return rc; }
   for (int64_t b0 = 0; b0 < nBlocks; b0 += CH) {
     const int cnt = (int)std::min<int64_t>(CH, nBlocks - b0);
-    memcpy(T.off(), blockBitOff + b0, (size_t)cnt * 8);
-    memcpy(T.bits(), blockBits + b0, (size_t)cnt * 8);
-    KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-    KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-    { const int rc = kz_knz_check(ctx, d_src, n, P.hdrEnd, T.d_off(), T.d_bits(), cnt, T.d_hdr(), T.d_bad()); if (rc) return rc; }
-    KZ_HIP(hipMemcpyAsync(T.hdr(), T.d_hdr(), (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
-    KZ_HIP(hipMemcpyAsync(T.bad(), T.d_bad(), (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
-    KZ_HIP(kz_stream_sync(ctx, ctx->stream));
-    kz_ktimer_flush(ctx);
-    for (int i = 0; i < cnt; i++) {
-      if (T.bad()[i]) return indexed_mismatch(ctx, b0 + i);
-      hdrs[(size_t)(b0 + i)] = T.hdr()[i];
-    }
-  }
-  // ---- chunks: prechecks on the host, unpack the entries that pass into staging rows, decode them into their rows of d_dst ----
-  const uint64_t nbits = (uint64_t)n * 8;
-  for (int64_t b0 = 0; b0 < nBlocks; b0 += CH) {
-    const int cnt = (int)std::min<int64_t>(CH, nBlocks - b0);
-    kz_block_result* res = results + b0;
-    int64_t maxBytes = 0;
-    for (int i = 0; i < cnt; i++) {
-      const int64_t W = blockBits[b0 + i];
-      const int rc = knz_check_walked(hdrs[(size_t)(b0 + i)], (uint64_t)W, (uint64_t)blockBitOff[b0 + i], nbits, P);
-      memset(&res[i], 0, sizeof(res[i]));
-      res[i].bits = W; res[i].status = rc;
-      T.off()[i] = blockBitOff[b0 + i];
-      T.bits()[i] = rc ? 0 : W;                                     // a row of no bits: nothing of it is unpacked
-      if (!rc) maxBytes = std::max<int64_t>(maxBytes, (W + 7) >> 3);
-    }
-    if (maxBytes == 0) continue;
-    KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-    KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-    { const int rc = kz_stage_reserve(ctx, ctx->devIn[0], (size_t)cnt * P.iS, false); if (rc) return rc; }
-    { const int rc = kz_knz_unpack(ctx, d_src, n, T.d_off(), T.d_bits(), cnt, maxBytes, ctx->devIn[0].p, P.iS); if (rc) return rc; }
-    { const int rc = indexed_decode_runs(ctx, P, ctx->devIn[0].p, blockBits + b0, cnt, d_dst + b0 * dstStride, dstStride, res, KZ_MEM_DEVICE); if (rc) return rc; }
-    KZ_HIP(kz_stream_sync(ctx, ctx->stream));                      // the pinned table is the next chunk's
-    kz_ktimer_flush(ctx);
+    const int rc = knz_chunk_decode(ctx, T, d_src, n, P, blockBitOff + b0, blockBits + b0, &hdrs[(size_t)b0], nullptr, cnt, d_dst + b0 * dstStride, dstStride, results + b0);
+    if (rc) return rc;
   }
   return 0;
 }
@@ -802,9 +830,9 @@ extern "C" int64_t kz_knz_splice_device(kz_ctx* ctx, const uint8_t* d_src, const
 // =================================================================================================
 // byte-addressed reads: many ranges [off, off + len) of the original data in one call, stream and destination in HBM
 // (kz_read_bytes_device).  The plan is the host form's (kz_knz_host.h: the distinct covering blocks, and the range x block segments
-// grouped by chunk); the indexed read's steps do the rest: every index entry the plan uses is checked against the stream
-// (k_knz_check) before anything is unpacked, then per chunk of blocks the prechecks, the unpack and the decode into staging rows,
-// and one k_knz_read launch that copies the chunk's segments from the rows to their places in d_dst.
+// grouped by chunk); the shared steps of the indexed calls (above the indexed read) do the open, the check of every index entry the
+// plan uses and, per chunk of blocks, the decode into staging rows; the read's own is one k_knz_read launch that copies the chunk's
+// segments from the rows to their places in d_dst.
 namespace {
 const int KNZ_READ_LAUNCH = 1 << 20;                               // segments per k_knz_read launch: bounds the table at 32 MiB
 }
@@ -813,16 +841,10 @@ extern "C" int64_t kz_read_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int64
   if (!ctx) return -KZ_ERR_INVALID_PARAM;
   { const int rc = knz_read_args(d_src, n, blockBitOff, blockBits, nIndex, rangeOff, rangeLen, nRanges, d_dst, dstCap, got); if (rc) return rc; }
   KZ_HIP(hipSetDevice(ctx->device));
-  uint8_t hdr[32]; HostBitsIn bs;
-  { const int rc = knz_open(ctx, d_src, n, hdr, bs); if (rc) return rc; }
-  KnzHeader h;
-  { const int hrc = read_stream_header(bs, h, ctx->err, sizeof(ctx->err)); if (hrc) return hrc; }
-  const KnzPlan P = knz_plan(ctx, h, n, (int64_t)bs.pos);
-  const int32_t blockSize = h.blockSize;
-  if (knz_read_table(blockByteOff, nIndex, blockSize)) {
-    snprintf(ctx->err, sizeof(ctx->err), "kz_read_bytes_device: blockByteOff is not a table of block starts");
-    return -KZ_ERR_INVALID_PARAM;
-  }
+  KnzPlan P;
+  { const int rc = knz_open_device(ctx, d_src, n, P); if (rc) return rc; }
+  const int32_t blockSize = P.h.blockSize;
+  { const int rc = knz_table_refusal(ctx, "kz_read_bytes_device", blockByteOff, nIndex, blockSize); if (rc) return rc; }
   const int64_t total = knz_read_total(rangeLen, nRanges, dstCap);
   if (total < 0) { snprintf(ctx->err, sizeof(ctx->err), "kz_read_bytes_device: destination too small"); return total; }
   if (nRanges == 0) return 0;
@@ -832,7 +854,7 @@ extern "C" int64_t kz_read_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int64
   for (int32_t i = 0; i < nRanges; i++) got[i] = 0;
   const int64_t nb = (int64_t)R.blocks.size();
   if (nb == 0) return total;
-  ChecksumScope chk(ctx, h.chkKind);
+  ChecksumScope chk(ctx, P.h.chkKind);
   const int cmax = (int)std::min<int64_t>(CH, nb);
   int64_t segMax = 0;
   for (size_t c = 0; c + 1 < R.first.size(); c++) segMax = std::max(segMax, std::min<int64_t>(R.first[c + 1] - R.first[c], KNZ_READ_LAUNCH));
@@ -840,53 +862,17 @@ extern "C" int64_t kz_read_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int64
   // launch (32 bytes per segment) takes their place when the chunk has been decoded
   { const int rc = knz_tables(ctx, std::max((size_t)cmax * 32, (size_t)segMax * sizeof(KnzReadSeg))); if (rc) return rc; }
   const KnzTable T(ctx, cmax);
-  // ---- every entry the plan uses against the stream, before anything is unpacked ----
   std::vector<uint64_t> hdrs((size_t)nb);
-  for (int64_t b0 = 0; b0 < nb; b0 += CH) {
-    const int cnt = (int)std::min<int64_t>(CH, nb - b0);
-    for (int i = 0; i < cnt; i++) { T.off()[i] = blockBitOff[R.blocks[(size_t)(b0 + i)]]; T.bits()[i] = blockBits[R.blocks[(size_t)(b0 + i)]]; }
-    KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-    KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-    { const int rc = kz_knz_check(ctx, d_src, n, P.hdrEnd, T.d_off(), T.d_bits(), cnt, T.d_hdr(), T.d_bad()); if (rc) return rc; }
-    KZ_HIP(hipMemcpyAsync(T.hdr(), T.d_hdr(), (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
-    KZ_HIP(hipMemcpyAsync(T.bad(), T.d_bad(), (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
-    KZ_HIP(kz_stream_sync(ctx, ctx->stream));
-    kz_ktimer_flush(ctx);
-    for (int i = 0; i < cnt; i++) {
-      if (T.bad()[i]) return indexed_mismatch(ctx, R.blocks[(size_t)(b0 + i)]);
-      hdrs[(size_t)(b0 + i)] = T.hdr()[i];
-    }
-  }
-  // ---- chunks of blocks, ascending: prechecks, unpack, decode into staging rows blockSize apart, copy the chunk's segments ----
-  const uint64_t nbits = (uint64_t)n * 8;
+  { const int rc = knz_check_entries(ctx, T, d_src, n, P, blockBitOff, blockBits, nb, [&](int64_t i) { return KnzEntry{R.blocks[(size_t)i], &hdrs[(size_t)i]}; }); if (rc) return rc; }
+  // ---- chunks of blocks, ascending: the decode into staging rows blockSize apart, then the copy of the chunk's segments ----
   std::vector<kz_block_result> res((size_t)cmax);
-  std::vector<int64_t> W((size_t)cmax);
-  {
-    int rc = kz_stage_reserve(ctx, ctx->devIn[0], (size_t)cmax * P.iS, false);
-    if (!rc) rc = kz_stage_reserve(ctx, ctx->devOut[0], (size_t)cmax * (size_t)blockSize, false);
-    if (rc) return rc;
-  }
+  std::vector<int64_t> W((size_t)cmax), off((size_t)cmax);
+  { const int rc = kz_stage_reserve(ctx, ctx->devOut[0], (size_t)cmax * (size_t)blockSize, false); if (rc) return rc; }
   for (int64_t b0 = 0, c = 0; b0 < nb; b0 += CH, c++) {
     const int cnt = (int)std::min<int64_t>(CH, nb - b0);
-    int64_t maxBytes = 0;
-    for (int i = 0; i < cnt; i++) {
-      const int32_t k = R.blocks[(size_t)(b0 + i)];
-      W[i] = blockBits[k];
-      const int rc = knz_check_walked(hdrs[(size_t)(b0 + i)], (uint64_t)W[i], (uint64_t)blockBitOff[k], nbits, P);
-      memset(&res[i], 0, sizeof(res[i]));
-      res[i].bits = W[i]; res[i].status = rc;
-      T.off()[i] = blockBitOff[k];
-      T.bits()[i] = rc ? 0 : W[i];                                  // a row of no bits: nothing of it is unpacked
-      if (!rc) maxBytes = std::max<int64_t>(maxBytes, (W[i] + 7) >> 3);
-    }
-    if (maxBytes > 0) {
-      KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-      KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-      { const int rc = kz_knz_unpack(ctx, d_src, n, T.d_off(), T.d_bits(), cnt, maxBytes, ctx->devIn[0].p, P.iS); if (rc) return rc; }
-      { const int rc = indexed_decode_runs(ctx, P, ctx->devIn[0].p, W.data(), cnt, ctx->devOut[0].p, blockSize, res.data(), KZ_MEM_DEVICE); if (rc) return rc; }
-      KZ_HIP(kz_stream_sync(ctx, ctx->stream));                    // the pinned table becomes the segments'
-      kz_ktimer_flush(ctx);
-    }
+    knz_chunk_entries(&R.blocks[(size_t)b0], nullptr, cnt, blockBitOff, blockBits, off.data(), W.data());
+    // (behind it the pinned table becomes the segments')
+    { const int rc = knz_chunk_decode(ctx, T, d_src, n, P, off.data(), W.data(), &hdrs[(size_t)b0], nullptr, cnt, ctx->devOut[0].p, blockSize, res.data()); if (rc) return rc; }
     knz_read_settle(R, c, CH, blockByteOff, nIndex, blockSize, res.data(), got);
     for (int64_t s0 = R.first[(size_t)c]; s0 < R.first[(size_t)c + 1]; s0 += KNZ_READ_LAUNCH) {
       const int ns = (int)std::min<int64_t>(KNZ_READ_LAUNCH, R.first[(size_t)c + 1] - s0);
@@ -918,10 +904,11 @@ extern "C" int64_t kz_read_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int64
 // =================================================================================================
 // byte-addressed writes: many ranges [off, off + len) of the original data replaced by new bytes in one call, stream, new bytes and
 // the new stream in HBM (kz_write_bytes_device).  The plan is the host form's (kz_knz_host.h: later wins resolved into disjoint
-// segments, the touched blocks, which of them are wholly covered).  Every index entry the call uses is checked against the stream
-// (k_knz_check) before anything is unpacked; then per chunk of touched blocks the read's steps up to the decode (prechecks, unpack,
-// decode into staging rows), k_knz_write launches that patch the rows, kz_compress_device's batched encode of the rows, and the
-// splice's copy (k_knz_splice) of every kept block since the previous chunk together with the recoded ones.  A piece's payload lies in
+// segments, the touched blocks, which of them are wholly covered).  The shared steps of the indexed calls (above the indexed read) do
+// the open, the check of every index entry the call uses (a wholly covered block's is not looked at) and, per chunk of touched
+// blocks, the decode into staging rows; the write's own are k_knz_write launches that patch the rows, kz_compress_device's batched
+// encode of the rows, and the splice's copy (k_knz_splice) of every kept block since the previous chunk together with the recoded
+// ones, laid out by knz_write_walk (kz_knz_host.h).  A piece's payload lies in
 // d_src (kept) or in an encoder row (recoded): the launch's base is d_src, a row is named by its distance from it.
 namespace {
 const int KNZ_WRITE_LAUNCH = 1 << 20;                              // segments per k_knz_write launch: bounds the table at 32 MiB
@@ -932,16 +919,11 @@ extern "C" int64_t kz_write_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int6
   if (!ctx) return -KZ_ERR_INVALID_PARAM;
   { const int rc = knz_write_args(d_src, n, blockBitOff, blockBits, nIndex, rangeOff, rangeLen, nRanges, d_data, dataLen, d_dst, dstCap, newBitOff, newBits); if (rc) return rc; }
   KZ_HIP(hipSetDevice(ctx->device));
-  uint8_t hdr[32]; HostBitsIn bs;
-  { const int rc = knz_open(ctx, d_src, n, hdr, bs); if (rc) return rc; }
-  KnzHeader h;
-  { const int hrc = read_stream_header(bs, h, ctx->err, sizeof(ctx->err)); if (hrc) return hrc; }
-  const KnzPlan P = knz_plan(ctx, h, n, (int64_t)bs.pos);
+  KnzPlan P;
+  { const int rc = knz_open_device(ctx, d_src, n, P); if (rc) return rc; }
+  const KnzHeader& h = P.h;
   const int32_t blockSize = h.blockSize;
-  if (knz_read_table(blockByteOff, nIndex, blockSize)) {
-    snprintf(ctx->err, sizeof(ctx->err), "kz_write_bytes_device: blockByteOff is not a table of block starts");
-    return -KZ_ERR_INVALID_PARAM;
-  }
+  { const int rc = knz_table_refusal(ctx, "kz_write_bytes_device", blockByteOff, nIndex, blockSize); if (rc) return rc; }
   const int CH = knz_chunk_blocks(ctx, blockSize);
   KnzWritePlan R;
   { const int32_t bad = knz_write_plan(blockByteOff, nIndex, blockSize, rangeOff, rangeLen, nRanges, CH, KNZ_WRITE_LAUNCH, R); if (bad >= 0) return knz_write_behind(bad, ctx->err, sizeof(ctx->err)); }
@@ -962,33 +944,16 @@ extern "C" int64_t kz_write_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int6
   // ---- every entry the call uses against the stream, before anything is unpacked: the kept blocks' and the decoded ones' ----
   std::vector<uint64_t> hdrs((size_t)nb);
   {
-    const KnzTable T(ctx, PL);
     int64_t ti = 0;                                               // the next touched block
-    for (int64_t k0 = 0; k0 < nIndex; k0 += PL) {
-      const int cnt = (int)std::min<int64_t>(PL, nIndex - k0);
-      int64_t tj = ti;
-      for (int i = 0; i < cnt; i++) {
-        const bool skip = tj < nb && R.blocks[(size_t)tj] == k0 + i && R.covered[(size_t)tj++];       // a wholly covered block's entry is not looked at
-        T.off()[i] = skip ? 0 : blockBitOff[k0 + i]; T.bits()[i] = skip ? 0 : blockBits[k0 + i];
-      }
-      KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-      KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-      { const int rc = kz_knz_check(ctx, d_src, n, P.hdrEnd, T.d_off(), T.d_bits(), cnt, T.d_hdr(), T.d_bad()); if (rc) return rc; }
-      KZ_HIP(hipMemcpyAsync(T.hdr(), T.d_hdr(), (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
-      KZ_HIP(hipMemcpyAsync(T.bad(), T.d_bad(), (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
-      KZ_HIP(kz_stream_sync(ctx, ctx->stream));
-      kz_ktimer_flush(ctx);
-      for (int i = 0; i < cnt; i++) {
-        const bool touched = ti < nb && R.blocks[(size_t)ti] == k0 + i;
-        if (touched && R.covered[(size_t)ti]) { ti++; continue; }
-        if (T.bad()[i]) return indexed_mismatch(ctx, k0 + i);
-        if (touched) hdrs[(size_t)ti++] = T.hdr()[i];
-      }
-    }
+    const int rc = knz_check_entries(ctx, KnzTable(ctx, PL), d_src, n, P, blockBitOff, blockBits, nIndex, [&](int64_t k) {
+      if (ti >= nb || R.blocks[(size_t)ti] != k) return KnzEntry{k, nullptr};                          // a kept block
+      uint64_t* keep = &hdrs[(size_t)ti];
+      return R.covered[(size_t)ti++] ? KnzEntry{-1, nullptr} : KnzEntry{k, keep};                       // a wholly covered block's entry is not looked at
+    });
+    if (rc) return rc;
   }
   {
-    int rc = kz_stage_reserve(ctx, ctx->devIn[0], (size_t)cmax * P.iS, false);
-    if (!rc) rc = kz_stage_reserve(ctx, ctx->devOut[0], (size_t)cmax * (size_t)blockSize, false);
+    int rc = kz_stage_reserve(ctx, ctx->devOut[0], (size_t)cmax * (size_t)blockSize, false);
     if (!rc) rc = kz_stage_reserve(ctx, ctx->devOut[1], (size_t)cmax * (size_t)oS, false);
     if (rc) return rc;
   }
@@ -997,25 +962,22 @@ extern "C" int64_t kz_write_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int6
   if ((uintptr_t)rows & 15) { snprintf(ctx->err, sizeof(ctx->err), "kz_write_bytes_device: staging rows off a 16-byte boundary"); return -KZ_ERR_DEVICE; }   // (unit0 counts on it)
   auto tooSmall = [&]() { snprintf(ctx->err, sizeof(ctx->err), "kz_write_bytes_device: destination too small"); return (int64_t)-KZ_ERR_WRITE_FILE; };
   // blocks [k0, k1) of the new stream from bit `pos` on, in launches of PL pieces: the blocks t0 .. of the touched list (ascending) come
-  // from the encoder's rows (eW: their bits), all others from where they lie in d_src; then tailBits zero bits.  The room was checked.
+  // from the encoder's rows (eW: their bits), all others from where they lie in d_src; then tailBits zero bits.  knz_write_walk
+  // (kz_knz_host.h) lays them out, first for the room, which is decided before a bit is written, then launch by launch.
   int64_t pos = (int64_t)hb.pos;
-  auto emit = [&](int64_t k0, int64_t k1, int64_t t0, int64_t t1, const int64_t* eW, int tailBits) -> int {
+  auto emit = [&](int64_t k0, int64_t k1, int64_t t0, int64_t t1, const int64_t* eW, int tailBits) -> int64_t {
     KnzPiece* pc = (KnzPiece*)(ctx->knzPin.p + 64);
     int64_t t = t0;
+    if (((knz_write_walk(blockBits, R.blocks.data(), k0, k1, t, t1, eW, pos, knz_write_walk_only) + tailBits + 7) >> 3) > dstCap) return tooSmall();
+    t = t0;
     for (int64_t a = k0; a < k1 || (a == k0 && tailBits); a += PL) {
       const int cnt = (int)std::max<int64_t>(0, std::min<int64_t>(PL, k1 - a));
       const int64_t start = pos;
-      for (int i = 0; i < cnt; i++) {
-        const int64_t k = a + i;
-        const bool rec = t < t1 && R.blocks[(size_t)t] == k;
-        const int64_t W = rec ? eW[t - t0] : blockBits[k];
-        pos += 5 + knz_prefix_width((uint64_t)W);
-        pc[i] = rec ? KnzPiece{pos, W, (int64_t)((intptr_t)(enc + (t - t0) * oS) - (intptr_t)d_src), (W + 7) >> 3, 0, 0}
-                    : KnzPiece{pos, W, 0, n, blockBitOff[k], P.hdrEnd};
-        if (newBitOff) { newBitOff[k] = pos; newBits[k] = W; }
-        pos += W;
-        if (rec) t++;
-      }
+      pos = knz_write_walk(blockBits, R.blocks.data(), a, a + cnt, t, t1, eW + (t - t0), pos, [&](int64_t k, int64_t r, int64_t W, int64_t pay) {
+        pc[k - a] = r >= 0 ? KnzPiece{pay, W, (int64_t)((intptr_t)(enc + (r - t0) * oS) - (intptr_t)d_src), (W + 7) >> 3, 0, 0}
+                           : KnzPiece{pay, W, 0, n, blockBitOff[k], P.hdrEnd};
+        if (newBitOff) { newBitOff[k] = pay; newBits[k] = W; }
+      });
       const bool last = a + cnt >= k1;
       if (last) pos += tailBits;
       if (cnt) KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + 64, pc, (size_t)cnt * sizeof(KnzPiece), hipMemcpyHostToDevice, ctx->stream));
@@ -1026,48 +988,21 @@ extern "C" int64_t kz_write_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int6
     }
     return 0;
   };
-  // the bit behind blocks [k0, k1) laid out from `from`, the touched ones t0 .. with eW bits
-  auto layout = [&](int64_t from, int64_t k0, int64_t k1, int64_t t0, int64_t t1, const int64_t* eW) {
-    int64_t t = t0;
-    for (int64_t k = k0; k < k1; k++) {
-      const bool rec = t < t1 && R.blocks[(size_t)t] == k;
-      const int64_t W = rec ? eW[t++ - t0] : blockBits[k];
-      from += 5 + knz_prefix_width((uint64_t)W) + W;
-    }
-    return from;
-  };
-  // ---- chunks of touched blocks, ascending: prechecks, unpack, decode into rows blockSize apart, patch, encode, copy ----
-  const uint64_t nbits = (uint64_t)n * 8;
+  // ---- chunks of touched blocks, ascending: the decode into rows blockSize apart, then patch, encode, copy ----
   const KnzTable T(ctx, cmax);
   std::vector<kz_block_result> res((size_t)cmax), eres((size_t)cmax);
-  std::vector<int64_t> W((size_t)cmax), eW((size_t)cmax);
+  std::vector<int64_t> W((size_t)cmax), off((size_t)cmax), eW((size_t)cmax);
   std::vector<int32_t> lens((size_t)cmax);
   int64_t next = 0;                                               // the first block not yet in the new stream
   size_t li = 0;                                                  // the next patch launch of the plan
   for (int64_t b0 = 0, c = 0; b0 < nb; b0 += CH, c++) {
     const int cnt = (int)std::min<int64_t>(CH, nb - b0);
-    int64_t maxBytes = 0;
-    for (int i = 0; i < cnt; i++) {
-      const int32_t k = R.blocks[(size_t)(b0 + i)];
-      memset(&res[i], 0, sizeof(res[i]));
-      if (R.covered[(size_t)(b0 + i)]) { W[i] = 0; res[i].status = 1; T.off()[i] = 0; T.bits()[i] = 0; continue; }   // (1: left out of the decode)
-      W[i] = blockBits[k];
-      const int rc = knz_check_walked(hdrs[(size_t)(b0 + i)], (uint64_t)W[i], (uint64_t)blockBitOff[k], nbits, P);
-      res[i].bits = W[i]; res[i].status = rc;
-      T.off()[i] = blockBitOff[k];
-      T.bits()[i] = rc ? 0 : W[i];                                  // a row of no bits: nothing of it is unpacked
-      if (!rc) maxBytes = std::max<int64_t>(maxBytes, (W[i] + 7) >> 3);
-    }
-    if (maxBytes > 0) {
-      KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-      KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-      { const int rc = kz_knz_unpack(ctx, d_src, n, T.d_off(), T.d_bits(), cnt, maxBytes, ctx->devIn[0].p, P.iS); if (rc) return rc; }
-      { const int rc = indexed_decode_runs(ctx, P, ctx->devIn[0].p, W.data(), cnt, rows, blockSize, res.data(), KZ_MEM_DEVICE); if (rc) return rc; }
-      KZ_HIP(kz_stream_sync(ctx, ctx->stream));                    // the pinned table becomes the segments'
-      kz_ktimer_flush(ctx);
-    }
-    for (int i = 0; i < cnt; i++)
-      if (R.covered[(size_t)(b0 + i)]) { const int32_t k = R.blocks[(size_t)(b0 + i)]; res[i].status = 0; res[i].length = (int32_t)(blockByteOff[k + 1] - blockByteOff[k]); }
+    const uint8_t* covered = &R.covered[(size_t)b0];
+    knz_chunk_entries(&R.blocks[(size_t)b0], covered, cnt, blockBitOff, blockBits, off.data(), W.data());
+    knz_write_covered(R, b0, cnt, blockByteOff, false, res.data());
+    // (behind it the pinned table becomes the segments')
+    { const int rc = knz_chunk_decode(ctx, T, d_src, n, P, off.data(), W.data(), &hdrs[(size_t)b0], covered, cnt, rows, blockSize, res.data()); if (rc) return rc; }
+    knz_write_covered(R, b0, cnt, blockByteOff, true, res.data());
     { const int rc = knz_write_settle(R, c, CH, blockByteOff, nIndex, blockSize, res.data(), lens.data(), ctx->err, sizeof(ctx->err)); if (rc) return rc; }
     // ---- the patch: the chunk's segments into the rows ----
     for (; li + 1 < R.cuts.size() && R.cuts[li] < R.first[(size_t)c + 1]; li++) {   // (a launch's segments are of one chunk)
@@ -1095,25 +1030,17 @@ extern "C" int64_t kz_write_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int6
     }
     // ---- one batched encode of the chunk's rows, with the chain of the stream's header ----
     {
-      const int rc = kz_encode_blocks_pre(ctx, h.transformType, (uint32_t)h.entropyType, blockSize, rows, blockSize, lens.data(), cnt, enc, oS, eres.data(), KZ_MEM_DEVICE, nullptr);
+      int rc = kz_encode_blocks_pre(ctx, h.transformType, (uint32_t)h.entropyType, blockSize, rows, blockSize, lens.data(), cnt, enc, oS, eres.data(), KZ_MEM_DEVICE, nullptr);
+      if (!rc) rc = knz_recoded_bits(ctx, &R.blocks[(size_t)b0], eres.data(), cnt, eW.data());
       if (rc) return rc;
-      for (int i = 0; i < cnt; i++) {
-        if (eres[i].status || eres[i].bits <= 0) {
-          snprintf(ctx->err, sizeof(ctx->err), "block %d: its encode failed (%d)", (int)R.blocks[(size_t)(b0 + i)], (int)eres[i].status);
-          return eres[i].status ? eres[i].status : -KZ_ERR_PROCESS_BLOCK;
-        }
-        eW[i] = eres[i].bits;
-      }
     }
     // ---- the copy: every kept block since the previous chunk, and the chunk's recoded ones, behind the previous chunk's last bit ----
     const int64_t k1 = (int64_t)R.blocks[(size_t)(b0 + cnt - 1)] + 1;
-    if (((layout(pos, next, k1, b0, b0 + cnt, eW.data()) + 7) >> 3) > dstCap) return tooSmall();
-    { const int rc = emit(next, k1, b0, b0 + cnt, eW.data(), 0); if (rc) return rc; }
+    { const int64_t rc = emit(next, k1, b0, b0 + cnt, eW.data(), 0); if (rc) return rc; }
     next = k1;
   }
   // ---- the kept tail and the end marker (:491-492) ----
-  if (((layout(pos, next, nIndex, nb, nb, nullptr) + 8 + 7) >> 3) > dstCap) return tooSmall();
-  { const int rc = emit(next, nIndex, nb, nb, nullptr, 8); if (rc) return rc; }
+  { const int64_t rc = emit(next, nIndex, nb, nb, nullptr, 8); if (rc) return rc; }
   { const int hrc = knz_put_header(ctx, nh, (int64_t)(hb.pos >> 3), d_dst); if (hrc) return hrc; }
   KZ_HIP(kz_stream_sync(ctx, ctx->stream));
   kz_ktimer_flush(ctx);

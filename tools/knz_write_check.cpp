@@ -1,5 +1,5 @@
 // knz_write_check.cpp -- the host-only plan of the byte-addressed writes (kanzi_amd/csrc/kz_knz_host.h: knz_write_args, knz_write_plan,
-// knz_write_settle, knz_write_bound) under the sanitizers, on the CPU:
+// knz_write_settle, knz_write_bound, knz_write_walk) under the sanitizers, on the CPU:
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I kanzi_amd/csrc tools/knz_write_check.cpp -o /tmp/knz_write_check && /tmp/knz_write_check
 // Every array is a heap allocation of the exact size, so a read or write one element outside it is reported.  The plan is compared
 // with a per-byte simulation: the ranges applied in argument order to an array of owner ids say which range owns every byte, and the
@@ -283,10 +283,54 @@ static void check_refusals() {
   CHECK(knz_write_bound(nullptr, 1, 1024) == -KZ_ERR_INVALID_PARAM && knz_write_bound(nullptr, -1, 1024) == -KZ_ERR_INVALID_PARAM, "bad bound arguments");
 }
 
+// knz_write_walk on seeded random blockBits, touched sets and recoded lengths: every block once and in order, the recoded ones with
+// their place in the touched list and their new bits, each payload at a plain running sum of 5 + knz_prefix_width(W) + W; whole and
+// cut into pieces at random blocks, as the launches of kz_write_bytes_device cut it.
+static void check_walk() {
+  for (int it = 0; it < 400; it++) {
+    const int nIndex = (int)(rnd() % 40);
+    std::vector<int64_t> bits, eW;
+    std::vector<int32_t> touched;
+    for (int k = 0; k < nIndex; k++) {
+      bits.push_back(rnd() % 5 == 0 ? 1 + (int64_t)(rnd() % 9) : 1 + (((int64_t)rnd() << 2) % ((1LL << 34) - 1)));
+      if (rnd() % 3 == 0) { touched.push_back(k); eW.push_back(rnd() % 4 == 0 ? 1 + (int64_t)(rnd() % 9) : 1 + (int64_t)(rnd() % 40000)); }
+    }
+    auto B = exact(bits); auto E = exact(eW); auto T = exact(touched);
+    const int64_t nt = (int64_t)touched.size(), pos0 = 160 + 16 * (int64_t)(rnd() % 4);
+    std::vector<int64_t> wantW, wantPay;                               // the plain sum
+    int64_t sum = pos0;
+    for (int k = 0, t = 0; k < nIndex; k++) {
+      const int64_t W = (t < nt && touched[(size_t)t] == k) ? eW[(size_t)t++] : bits[(size_t)k];
+      sum += 5 + knz_prefix_width((uint64_t)W);
+      wantW.push_back(W); wantPay.push_back(sum);
+      sum += W;
+    }
+    int64_t t = 0, seen = 0, recs = 0;
+    auto block = [&](int64_t k, int64_t r, int64_t W, int64_t pay) {
+      CHECK(k == seen && W == wantW[(size_t)k] && pay == wantPay[(size_t)k], "block %lld of the walk: %lld bits at %lld", (long long)k, (long long)W, (long long)pay);
+      if (r >= 0) { CHECK(r == recs && touched[(size_t)r] == k, "block %lld: place %lld in the touched list", (long long)k, (long long)r); recs++; }
+      else CHECK(recs == nt || touched[(size_t)recs] != k, "touched block %lld is not recoded", (long long)k);
+      seen++;
+    };
+    CHECK(knz_write_walk(B.get(), T.get(), 0, nIndex, t, nt, E.get(), pos0, block) == sum && seen == nIndex && t == nt && recs == nt, "the walk's end");
+    t = 0;
+    CHECK(knz_write_walk(B.get(), T.get(), 0, nIndex, t, nt, E.get(), pos0, knz_write_walk_only) == sum, "the room decision");
+    t = 0; seen = 0; recs = 0;
+    int64_t pos = pos0;
+    for (int64_t a = 0; a < nIndex;) {                                 // in pieces: the cursor t and eW move on with them
+      const int64_t b = std::min<int64_t>(nIndex, a + 1 + (int64_t)(rnd() % 7));
+      pos = knz_write_walk(B.get(), T.get(), a, b, t, nt, E.get() + t, pos, block);
+      a = b;
+    }
+    CHECK(pos == sum && seen == nIndex && t == nt, "the walk in pieces");
+  }
+}
+
 int main() {
   check_refusals();
   check_cases();
   check_random();
+  check_walk();
   printf("knz_write_check ok: %ld checks\n", checked);
   return 0;
 }
