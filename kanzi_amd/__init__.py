@@ -400,7 +400,8 @@ class BWTBlockCodec(_Transform):
 
 class TextCodec(_Transform):
     """K/transform/TextCodec.java (host stage).  Like the reference's constructor it takes the variant from the context map:
-    entropy (TextCodec2 for NONE / ANS0 / HUFFMAN / RANGE, else TextCodec1) and blockSize (hash map size)."""
+    entropy (TextCodec2 for NONE / ANS0 / HUFFMAN / RANGE, else TextCodec1) and blockSize (hash map size).  In batched encodes the
+    forward of either codec runs on the device for large batches (KZ_TEXT_FWD_GPU / KZ_TEXT1_FWD_GPU)."""
     TYPE = TEXT_TYPE
 
     def __init__(self, ctx, entropy="NONE", blockSize=4 * 1024 * 1024):

@@ -54,6 +54,8 @@ void kz_switches_read(kz_switches& s) {
   s.textGpuMin = num("KZ_TEXT_GPU_MIN", 512);
   s.textFwdGpu = digit("KZ_TEXT_FWD_GPU", 0, 1, -1);
   s.textFwdGpuMin = num("KZ_TEXT_FWD_GPU_MIN", 256);
+  s.text1FwdGpu = digit("KZ_TEXT1_FWD_GPU", 0, 1, -1);
+  s.text1FwdGpuMin = num("KZ_TEXT1_FWD_GPU_MIN", 64);
   s.utfGpu = digit("KZ_UTF_GPU", 0, 0, 1);
   s.utfFwdGpu = digit("KZ_UTF_FWD_GPU", 0, 1, -1);
   s.textGpuTrace = flag("KZ_TEXT_GPU_TRACE");
@@ -878,8 +880,19 @@ static bool text_gpu_on(const kz_ctx* ctx, uint32_t entropyType, int nBlocks) { 
 // blocks (256) or more -- a block's dictionary walk takes the kernel ~0.1 s however few there are, so small batches stay on the host's
 // chunk pipeline (measured with 16 host CPUs, level-exact -l 5 encode of 64 / 128 / 256 / 512 blocks: host 102 / 159 / 293 / 529 ms,
 // device 157 / 188 / 247 / 379 ms).  KZ_TEXT_FWD_GPU=0: host stage, =1: any batch size.  (Read per call: the tests force both.)
+// TextCodec1 streams (FPAQ / CM / ANS1: the same kernels at TextCodec1's seams) have switches of their own: KZ_TEXT1_FWD_GPU=0: host
+// stage, =1: any batch size, unset: batches of KZ_TEXT1_FWD_GPU_MIN blocks (64) or more, 0 = never.  64 is the smallest size measured
+// (tools/text1_probe.py, 16 host CPUs, text-heavy mix at 4 MiB blocks in HBM, 64 / 128 / 256 / 512 blocks, median of 5, spread under
+// 1 %): level-6 encode host 1966 / 2005 / 2094 / 1696 ms, device 735 / 763 / 816 / 932 ms; TEXT+UTF & FPAQ host 5126 / 5163 / 5195 /
+// 3643 ms, device 1786 / 1793 / 1799 / 1821 ms.  The walk itself is ~75 - 85 ms; most of the gain is that a batch on the device path
+// is coded in ONE pass, where the host chunk pipeline codes it in thirds (halves from 512 blocks on) and k_fpaq_enc takes ~630 ms
+// (level 6) per pass however few blocks it has.
 static bool text_fwd_gpu_on(const kz_ctx* ctx, uint32_t entropyType, int nBlocks) {
-  if (!kz_fast_coder((int)entropyType) || entropyType == KZ_E_RANGE) return false;   // RANGE chains: never measured there
+  if (entropyType == KZ_E_RANGE) return false;                                        // RANGE chains: never measured there
+  if (!kz_fast_coder((int)entropyType)) {
+    if (ctx->sw.text1FwdGpu >= 0) return ctx->sw.text1FwdGpu == 1;
+    return ctx->sw.text1FwdGpuMin > 0 && nBlocks >= ctx->sw.text1FwdGpuMin;
+  }
   if (ctx->sw.textFwdGpu >= 0) return ctx->sw.textFwdGpu == 1;
   return nBlocks >= ctx->sw.textFwdGpuMin;
 }
@@ -1340,7 +1353,7 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
   Pipe P;
   int64_t extra = (host ? (int64_t)outStride * B : 0) + (int64_t)B * (sizeof(kz_block_result) + 64) + (int64_t)B * 32 + 8192;
   if (textFwdGpu) {                     // the device TEXT forward runs first and gives its scratch back: it needs the larger of the two, not the sum
-    const int64_t tf = (int64_t)kz_text_fwd_gpu_scratch(B, blockSize, maxLen), rest = (int64_t)pipeline_scratch(B, maxLen, false, CS);
+    const int64_t tf = (int64_t)kz_text_fwd_gpu_scratch(B, blockSize, maxLen, !kz_fast_coder((int)entropyType)), rest = (int64_t)pipeline_scratch(B, maxLen, false, CS);
     if (tf > rest) extra += tf - rest;
   }
   int rc = pipe_setup(ctx, P, B, maxLen, extra, false, CS);
@@ -1404,7 +1417,7 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
       std::unique_ptr<TextFwdJob, void (*)(TextFwdJob*)> J(kz_text_fwd_gpu_new(), kz_text_fwd_gpu_free);
       std::vector<int32_t> take(B), keeps;
       for (int b = 0; b < B; b++) take[b] = (!h_copy[b] && lengths[b] > 0) ? 1 : 0;
-      rc = kz_text_fwd_gpu_classify(ctx, bt, blockSize, take, keeps, textDeclined, *J);
+      rc = kz_text_fwd_gpu_classify(ctx, bt, blockSize, take, keeps, textDeclined, *J, !kz_fast_coder((int)entropyType));
       if (rc) return rc;
       // a block that is not text: TEXT declined it on the device and left its "dataType"; UTF (if the chain has it) looks at UNDEFINED
       // and UTF8 blocks only (UTFCodec.java:93-101), on the host, from that entry on; every other block is done with the host stages
@@ -1451,7 +1464,7 @@ int32_t kz_encode_blocks_pre(kz_ctx* ctx, uint64_t transformType, uint32_t entro
         const auto t0 = std::chrono::steady_clock::now();
         host_prestage_list(types, hp, (int)entropyType, blockSize, maxLen, ptrs, lens, passP[pass], store, &firstStage, &dtIn);
         if (ctx->sw.textGpuTrace)
-          fprintf(stderr, "[textfwd] host pass %d: %d blocks, %.0f ms\n", pass, (int)blocks.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+          fprintf(stderr, "[textfwd%s] host pass %d: %d blocks, %.0f ms\n", kz_fast_coder((int)entropyType) ? "" : "1", pass, (int)blocks.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
         return 0;
       };
       std::vector<int> first, second;

@@ -63,6 +63,8 @@ struct kz_switches {
   int textGpuMin = 512;          // KZ_TEXT_GPU_MIN
   int textFwdGpu = -1;           // KZ_TEXT_FWD_GPU: -1 unset, 0 host, 1 any batch
   int textFwdGpuMin = 256;       // KZ_TEXT_FWD_GPU_MIN
+  int text1FwdGpu = -1;          // KZ_TEXT1_FWD_GPU: the same for TextCodec1 streams (FPAQ / CM / ANS1): -1 unset, 0 host, 1 any batch
+  int text1FwdGpuMin = 64;       // KZ_TEXT1_FWD_GPU_MIN: batch size from which the unset case uses the device (0 = never; the default: kz_api.hip, text_fwd_gpu_on)
   int utfGpu = 1;                // KZ_UTF_GPU=0: UTF inverse on the host
   int utfFwdGpu = -1;            // KZ_UTF_FWD_GPU: -1 unset (with the device TEXT forward), 0 host, 1 any batch
   int textGpuTrace = 0;          // KZ_TEXT_GPU_TRACE
@@ -285,8 +287,8 @@ int kz_host_transform_forward(int type, int entropyType, int blockSize, int* dat
 int kz_host_transform_inverse(int type, int blockSize, const uint8_t* src, int n, uint8_t* dst, int dstCap, int* produced);
 // kz_text_gpu.hip: the TEXT inverse of blocks that are still in HBM (done[b] = 1 for the blocks it finished; the others: host stage)
 size_t kz_text_gpu_scratch_per_block(int blockSize);
-// kz_text_fwd_gpu.hip: the TEXT forward (TextCodec2) of blocks that sit in HBM (done[b] = 1 for the blocks it finished; the others: host stage)
-size_t kz_text_fwd_gpu_scratch(int B, int blockSize, int maxLen);
+// kz_text_fwd_gpu.hip: the TEXT forward (TextCodec2, or TextCodec1 with variant1) of blocks that sit in HBM (done[b] = 1 for the blocks it finished; the others: host stage)
+size_t kz_text_fwd_gpu_scratch(int B, int blockSize, int maxLen, bool variant1);
 // kz_utf_fwd_gpu.hip: UTFCodec.forward of the blocks TEXT declined with "dataType" UTF8 (done[b]: 1 applied, 2 declined by the reference's rules, 0 host stage)
 int kz_utf_fwd_gpu(kz_ctx* ctx, kz_batch& bt, const std::vector<int32_t>& take, std::vector<int32_t>& done);
 bool kz_text_fwd_gpu_applies(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int nBlocks);   // kz_api.hip
@@ -294,7 +296,7 @@ struct TextFwdJob;
 TextFwdJob* kz_text_fwd_gpu_new();
 void kz_text_fwd_gpu_free(TextFwdJob*);
 int kz_text_fwd_gpu_classify(kz_ctx* ctx, kz_batch& bt, int blockSize, const std::vector<int32_t>& take, std::vector<int32_t>& keeps,
-                             std::vector<int32_t>& declined, TextFwdJob& J);
+                             std::vector<int32_t>& declined, TextFwdJob& J, bool variant1);
 int kz_text_fwd_gpu_launch(kz_ctx* ctx, kz_batch& bt, TextFwdJob& J);
 int kz_text_fwd_gpu_finish(kz_ctx* ctx, kz_batch& bt, TextFwdJob& J, std::vector<int32_t>& done);
 size_t kz_utf_gpu_scratch_per_block(int maxLen);

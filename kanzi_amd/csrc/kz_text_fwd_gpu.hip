@@ -1,5 +1,6 @@
-// kz_text_fwd_gpu.hip -- TEXT forward (TextCodec2) on the device: K/transform/TextCodec.java:1124-1300 (TextCodec2.forward),
-// :269-384 (computeStats, the text branch), :1304-1394 (emitSymbols / emitWordIndex) for blocks that sit in HBM.
+// kz_text_fwd_gpu.hip -- TEXT forward on the device, both codecs: K/transform/TextCodec.java:1124-1300 (TextCodec2.forward),
+// :269-384 (computeStats, the text branch), :1304-1394 (emitSymbols / emitWordIndex); :618-795 (TextCodec1.forward), :806-863
+// (its emitSymbols / emitWordIndex) for blocks that sit in HBM.
 //
 // The host form (kz_text.hip: text_forward) stays the reference of this file and the fallback: a block the device does not take or
 // does not finish cleanly (not text by the order-0 rules -- detectType then wants the whole pair table --, a Magic number in front, fewer
@@ -21,6 +22,10 @@
 //                  a found word leaves (number + 1 | length << 24 | flip << 31) at its first letter in `tok`;
 //     k_tf_emit<false> / k_tf_scan / k_tf_emit<true> = output bytes per 1 024 positions (and the letters of every found word against
 //                  its dictionary word), offsets and the verdict, the bytes.
+// TextCodec1 (streams under FPAQ / CM / ANS1) is the same walk, dictionary discipline and learn rule (kz_text.hip: text_forward).
+// Its seams: the strict text verdict (k_tf_decide), a fixed dictionary part of sCount + 2 words -- the two escape bytes as one-letter
+// words with hash 0, which hold map slot 0 until the first learn (host side of classify; TextFwd.sCount is the FIXED count, so the
+// walk needs no variant) --, a map of blockSize / 8 slots, and the byte costs and encodings of the output (k_tf_emit<.., true>).
 #include "kz_device.h"
 #include "kz_internal.h"
 #include "kz_magic.h"
@@ -47,6 +52,8 @@ void kz_text_static_tables(std::vector<uint32_t>& hash, std::vector<int32_t>& po
 #define TF_LF 0x0Au
 #define TF_CR 0x0Du
 #define TF_ESC1 0x0Fu
+#define TF_ESC2 0x0Eu
+#define TF_T1 128
 #define TF_HASH1 0x7FEB352Du
 #define TF_HASH2 0x846CA68Bu
 #define TF_CRLF 0x40
@@ -57,7 +64,7 @@ void kz_text_static_tables(std::vector<uint32_t>& hash, std::vector<int32_t>& po
 #define TF_MARGIN 8
 
 struct TextFwd {
-  const u8* sText; const u8* delim; const u64* sMap; const int32_t* sPos; int sMapN; int sCount;   // static dictionary: text, delimiter set, (slot, e0, e1) triples
+  const u8* sText; const u8* delim; const u64* sMap; const int32_t* sPos; int sMapN; int sCount;   // fixed dictionary (TextCodec1: + its two escape words): text, delimiter set, (slot, e0, e1) triples
   u64* map;            // [A][slotsPer][2]: hash | (length << 24 | number) << 32,  position | valid << 32 | static << 33
   u32* tok;            // [A][NS]
   u32* wpos;           // [A][TF_MAXDICT] position of a learned word's first letter, by word number
@@ -118,7 +125,8 @@ __global__ __launch_bounds__(256) void k_tf_stats(const u8* __restrict__ srcAll,
 }
 
 // one thread per block: text or not (:310-331), the mode byte (:333-381)
-__global__ __launch_bounds__(64) void k_tf_decide(const u8* __restrict__ srcAll, int64_t stride, const int32_t* __restrict__ d_len, TextFwd G, int B) {
+// strict (TextCodec1: computeStats(strict) :320-326): no space-frequency rule; NUL bytes >= 1 %, or printable ASCII / 95 < 1 %: not text
+__global__ __launch_bounds__(64) void k_tf_decide(const u8* __restrict__ srcAll, int64_t stride, const int32_t* __restrict__ d_len, TextFwd G, int B, int strict) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
   const int a = G.ord[b];
@@ -132,7 +140,7 @@ __global__ __launch_bounds__(64) void k_tf_decide(const u8* __restrict__ srcAll,
     for (int c = 0; c < 128; c++) { if (tf_is_text((u32)c)) letters += f[c]; ascii += f[c]; }
     const long long bin = n - ascii;
     bool notText = bin > (n >> 2);
-    if (!notText) notText = letters < n / 4 || f[32] < n / 50;                                         // :321, :326 (not strict)
+    if (!notText) notText = letters < n / 4 || (strict ? (f[0] >= n / 100 || ascii / 95 < n / 100) : f[32] < n / 50);   // :321, :323-324 (strict), :326
     if (!notText) {
       int m = 0;
       if (bin <= n - n / 10) {                                                                           // :336-356
@@ -242,7 +250,7 @@ __global__ __launch_bounds__(64) void k_tf_walk(const u8* __restrict__ srcAll, i
   const uint64_t dm0 = kz_ballot(G.delim[lane] != 0), dm1 = kz_ballot(G.delim[64 + lane] != 0), dm2 = kz_ballot(G.delim[128 + lane] != 0), dm3 = kz_ballot(G.delim[192 + lane] != 0);
 #define TF_DELIM(cc) ((((cc) < 64u ? dm0 : ((cc) < 128u ? dm1 : ((cc) < 192u ? dm2 : dm3))) >> ((cc) & 63u)) & 1ULL)
   const uint64_t lt = kz_lanemask_lt();
-  int words = G.sCount;                           // the next word number (TextCodec2: the static words, nothing else fixed)
+  int words = G.sCount;                           // the next word number (TextCodec2: the static words, nothing else fixed; TextCodec1: + 2)
   int carry = -1;                                 // position of the last non-letter in front of the row (:694: a letter first = -1 / the last leading space)
   bool failed = false;
   // one letter of the words the row closes (letters: no sign to extend), and a group of four behind a test that some word is that long
@@ -370,7 +378,14 @@ __global__ __launch_bounds__(64) void k_tf_walk(const u8* __restrict__ srcAll, i
 }
 
 // ---- output: sizes per tile, then the bytes (:752-771 between the words, emitSymbols :1304-1367, emitWordIndex :1370-1394) ----
-template <bool WRITE>
+// V1: TextCodec1's costs and encodings (:806-863): a reference is 0x0F (0x0E: first letter's case flipped) + the word NUMBER in 1 - 3
+// bytes, a literal 0x0E / 0x0F is a reference to its one-letter word (sCount - 2 / sCount - 1), bytes >= 0x80 are plain.
+__device__ __forceinline__ u32 tf_idx1_bytes(u32 v) { return v >= TF_T2 ? 3u : (v >= TF_T1 ? 2u : 1u); }
+__device__ __forceinline__ void tf_idx1(u8* o, u32 v) {                                                  // :850-863
+  if (v >= TF_T1) { if (v >= TF_T2) *o++ = (u8)(0xE0u | (v >> 14)); o[0] = (u8)(0x80u | (v >> 7)); o[1] = (u8)(v & 0x7Fu); }
+  else o[0] = (u8)v;
+}
+template <bool WRITE, bool V1>
 __global__ __launch_bounds__(256) void k_tf_emit(const u8* __restrict__ srcAll, u8* __restrict__ dstAll, int64_t stride, const int32_t* __restrict__ d_len, TextFwd G, int B) {
   const int b = blockIdx.y;
   const int a = G.ord[b];
@@ -389,7 +404,7 @@ __global__ __launch_bounds__(256) void k_tf_emit(const u8* __restrict__ srcAll, 
   const bool crlf = (mode & TF_CRLF) != 0;
   const uint64_t le = kz_lanemask_lt() | (1ULL << lane);
   u32 off = WRITE ? 1u + (u32)G.tileSum[(int64_t)a * G.maxTiles + t] : 0u;
-  if (WRITE && t == 0 && lane == 0) dst[0] = (u8)(mode | TF_CODEC2);                                  // TextCodec.java:496-501
+  if (WRITE && t == 0 && lane == 0) dst[0] = (u8)(V1 ? mode : (mode | TF_CODEC2));                    // TextCodec.java:496-501
   u32 tPrev = (base >= 64) ? tok[base - 64 + lane] : 0u;
   for (int r = 0; r < TF_TILE / 64; r++) {
     const int row = base + r * 64;
@@ -411,9 +426,16 @@ __global__ __launch_bounds__(256) void k_tf_emit(const u8* __restrict__ srcAll, 
     const bool ends = tS != 0 && p == sPos + L;
     const bool skipSp = ends && c == ' ' && tNxt != 0;                                                  // :752: a single space between two references
     u32 lit = 0;
-    if (inb && !cov && !skipSp) lit = (c == TF_ESC1) ? 2u : ((c == TF_CR) ? (crlf ? 0u : 1u) : 1u + (c >> 7));
     const u32 v = tCur & 0x00FFFFFFu;
-    const u32 code = tCur ? ((tCur >> 31) + (v >= TF_T4 ? 3u : (v >= TF_T3 ? 2u : 1u))) : 0u;
+    u32 code;
+    if constexpr (V1) {
+      const bool esc = c == TF_ESC1 || c == TF_ESC2;
+      if (inb && !cov && !skipSp) lit = esc ? 1u + tf_idx1_bytes((u32)G.sCount - (c == TF_ESC1 ? 1u : 2u)) : ((c == TF_CR && crlf) ? 0u : 1u);
+      code = tCur ? 1u + tf_idx1_bytes(v - 1u) : 0u;
+    } else {
+      if (inb && !cov && !skipSp) lit = (c == TF_ESC1) ? 2u : ((c == TF_CR) ? (crlf ? 0u : 1u) : 1u + (c >> 7));
+      code = tCur ? ((tCur >> 31) + (v >= TF_T4 ? 3u : (v >= TF_T3 ? 2u : 1u))) : 0u;
+    }
     if (!WRITE && tCur) {
       // sameWords (:720-723), which the walk left out: the letters behind the first against the dictionary word's, four at a time
       // (both buffers have slack behind them).  A mismatch -- a hash collision at equal length -- fails the block: host stage.
@@ -430,7 +452,11 @@ __global__ __launch_bounds__(256) void k_tf_emit(const u8* __restrict__ srcAll, 
     const u32 incl = kz_wave_incl_sum(sz);
     if (WRITE && sz) {
       u8* o = dst + off + incl - sz;
-      if (tCur) {
+      if constexpr (V1) {
+        if (tCur) { o[0] = (u8)((tCur >> 31) ? TF_ESC2 : TF_ESC1); tf_idx1(o + 1, v - 1u); }
+        else if (c == TF_ESC1 || c == TF_ESC2) { o[0] = (u8)TF_ESC1; tf_idx1(o + 1, (u32)G.sCount - (c == TF_ESC1 ? 1u : 2u)); }
+        else o[0] = (u8)c;
+      } else if (tCur) {
         if (tCur >> 31) *o++ = 0x80;
         if (v >= TF_T4) { o[0] = (u8)(0xF0u | (v >> 16)); o[1] = (u8)(v >> 8); o[2] = (u8)v; }
         else if (v >= TF_T3) { o[0] = (u8)(0xC0u | (v >> 8)); o[1] = (u8)v; }
@@ -474,13 +500,19 @@ __global__ __launch_bounds__(256) void k_tf_copy_back(const u8* __restrict__ src
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += gridDim.x * blockDim.x) d[i] = s[i];
 }
 
-static int tf_log_v2(int blockSize) { int l = 13; if (blockSize >= 32) l = std::max(std::min(31 - __builtin_clz((unsigned)(blockSize / 32)), 24), 13); return l; }   // :1068-1081
+// the map's size from the stream's "blockSize": TextCodec2 blockSize / 32 in 2^13 .. 2^24 (:1068-1081), TextCodec1 blockSize / 8 in 2^13 .. 2^26 (:561-575)
+static int tf_log(int blockSize, bool variant1) {
+  const int div = variant1 ? 8 : 32, top = variant1 ? 26 : 24;
+  int l = 13;
+  if (blockSize >= div) l = std::max(std::min(31 - __builtin_clz((unsigned)(blockSize / div)), top), 13);
+  return l;
+}
 
 // bytes of scratch the stage wants for a batch of B blocks of at most maxLen bytes, all of them text (kz_api.hip sizes the arena with it):
 // 4 bytes of `tok` per input byte, 16 bytes per hash slot and 4 per word number
-size_t kz_text_fwd_gpu_scratch(int B, int blockSize, int maxLen) {
+size_t kz_text_fwd_gpu_scratch(int B, int blockSize, int maxLen, bool variant1) {
   const size_t NS = kz_align((size_t)maxLen + 64, 256);
-  return (size_t)B * (NS * 4 + ((size_t)32 << tf_log_v2(blockSize)) + (size_t)TF_MAXDICT * 4 + (size_t)(maxLen / TF_TILE + 2) * 4 + TF_STATS * 4 + 96) + (1 << 20);
+  return (size_t)B * (NS * 4 + ((size_t)32 << tf_log(blockSize, variant1)) + (size_t)TF_MAXDICT * 4 + (size_t)(maxLen / TF_TILE + 2) * 4 + TF_STATS * 4 + 96) + (1 << 20);
 }
 
 // The stage in three steps, so that the caller can run the host stages of the blocks the device does not keep while the walk runs:
@@ -500,18 +532,20 @@ struct TextFwdJob {
   kz_ctx* holder = nullptr;                         // the context whose arena holds this job's scratch above `mark` (null: nothing held)
   int A = 0, kept = 0;
   bool live = false;
+  bool variant1 = false;                            // TextCodec1 (the stream's entropy coder is not one of the "fast" ones)
 };
 TextFwdJob* kz_text_fwd_gpu_new() { return new TextFwdJob(); }
 // the job's owner drops it on every path out of the encode call: an early error return gives the arena back here
 void kz_text_fwd_gpu_free(TextFwdJob* J) { if (J && J->holder) J->holder->arenaTop = J->mark; delete J; }
 
 int kz_text_fwd_gpu_classify(kz_ctx* ctx, kz_batch& bt, int blockSize, const std::vector<int32_t>& take, std::vector<int32_t>& keeps,
-                             std::vector<int32_t>& declined, TextFwdJob& J) {
+                             std::vector<int32_t>& declined, TextFwdJob& J, bool variant1) {
   const int B = bt.B;
   keeps.assign(B, 0);
   declined.assign(B, -1);
   J.ord.assign(B, -1);
   J.live = false;
+  J.variant1 = variant1;
   int A = 0, maxLen = 0;
   for (int b = 0; b < B; b++) if (take[b] && bt.h_len[b] >= TF_MINBLOCK && bt.h_len[b] < TF_MAXBLOCK) { J.ord[b] = A++; maxLen = std::max(maxLen, bt.h_len[b]); }
   J.A = A;
@@ -520,16 +554,20 @@ int kz_text_fwd_gpu_classify(kz_ctx* ctx, kz_batch& bt, int blockSize, const std
   static std::once_flag once;
   std::call_once(once, [] { kz_text_static_tables(hHash, hPos, hLenIdx, hText, hDelim, &hCount); });
   TextFwd& G = J.G;
-  const int logV2 = tf_log_v2(blockSize);
-  G.slotsPer = (int64_t)1 << logV2; G.mask = (u32)(G.slotsPer - 1);
+  const int logMap = tf_log(blockSize, variant1);
+  G.slotsPer = (int64_t)1 << logMap; G.mask = (u32)(G.slotsPer - 1);
   G.NS = (int64_t)kz_align((size_t)maxLen + 64, 256);
   G.maxTiles = maxLen / TF_TILE + 2;
-  G.sCount = hCount;
-  // the static words' map entries for this map size: the words take their slots in order, a later word takes a shared slot (:1109-1113)
+  // TextCodec1: the two escape bytes are one-letter words sCount and sCount + 1 with hash 0 (:600-603; kz_text_static_tables lists them
+  // behind the static words): both claim slot 0 behind every static word, so a length-1 entry holds it -- a static word that hashes
+  // there is shadowed, a new one is not learnable (:725) -- until the first learn empties it (the walk's tf_st(map + 1, 0))
+  const int fixed = hCount + (variant1 ? 2 : 0);
+  G.sCount = fixed;
+  // the fixed words' map entries for this map size: the words take their slots in order, a later word takes a shared slot (:1109-1113)
   std::vector<u64> sMap;
   {
     std::unordered_map<u32, int> owner;
-    for (int i = 0; i < hCount; i++) owner[hHash[i] & G.mask] = i;
+    for (int i = 0; i < fixed; i++) owner[hHash[i] & G.mask] = i;
     for (const auto& kv : owner) {
       const int i = kv.second;
       sMap.push_back((u64)kv.first);
@@ -565,7 +603,7 @@ int kz_text_fwd_gpu_classify(kz_ctx* ctx, kz_batch& bt, int blockSize, const std
   G.map = nullptr; G.tok = nullptr; G.wpos = nullptr; G.tileSum = nullptr;
   const u8* src = bt.buf[bt.cur];
   KZ_LAUNCH(ctx, KID_TEXT_FWD, k_tf_stats, dim3(16, B), dim3(256), src, bt.stride, bt.d_len, G, B);
-  KZ_LAUNCH(ctx, KID_TEXT_FWD, k_tf_decide, dim3((B + 63) / 64), dim3(64), src, bt.stride, bt.d_len, G, B);
+  KZ_LAUNCH(ctx, KID_TEXT_FWD, k_tf_decide, dim3((B + 63) / 64), dim3(64), src, bt.stride, bt.d_len, G, B, variant1 ? 1 : 0);
   KZ_LAUNCH(ctx, KID_TEXT_FWD, k_tf_pairs, dim3(B), dim3(256), src, bt.stride, bt.d_len, G, B);
   std::vector<int32_t> mode(A), tdt(A);
   KZ_HIP(hipMemcpyAsync(mode.data(), G.mode, (size_t)A * 4, hipMemcpyDeviceToHost, st));
@@ -585,7 +623,7 @@ int kz_text_fwd_gpu_classify(kz_ctx* ctx, kz_batch& bt, int blockSize, const std
   G.map = (u64*)kz_arena_alloc(ctx, (size_t)K * (size_t)G.slotsPer * 16);
   G.tok = (u32*)kz_arena_alloc(ctx, (size_t)K * (size_t)G.NS * 4);
   if (!dMode2 || !dFail2 || !G.tileSum || !G.wpos || !G.map || !G.tok) {
-    if (ctx->sw.textGpuTrace) fprintf(stderr, "[textfwd] no scratch for %d blocks: host stage\n", K);
+    if (ctx->sw.textGpuTrace) fprintf(stderr, "[textfwd%s] no scratch for %d blocks: host stage\n", variant1 ? "1" : "", K);
     ctx->arenaTop = J.mark; J.holder = nullptr; J.kept = 0; return 0;
   }
   std::vector<int32_t> mode2(K);
@@ -611,9 +649,12 @@ int kz_text_fwd_gpu_launch(kz_ctx* ctx, kz_batch& bt, TextFwdJob& J) {
   const u8* src = bt.buf[bt.cur]; u8* dst = bt.buf[bt.cur ^ 1];
   KZ_LAUNCH(ctx, KID_TEXT_FWD, k_tf_init, dim3(2, B), dim3(256), G, B);
   KZ_LAUNCH(ctx, KID_TEXT_WALK, k_tf_walk, dim3(B), dim3(64), src, bt.stride, bt.d_len, G, B);
-  KZ_LAUNCH(ctx, KID_TEXT_FWD, k_tf_emit<false>, dim3((G.maxTiles + 3) / 4, B), dim3(256), src, dst, bt.stride, bt.d_len, G, B);
+  const dim3 eg((G.maxTiles + 3) / 4, B);
+  if (J.variant1) KZ_LAUNCH(ctx, KID_TEXT_FWD, (k_tf_emit<false, true>), eg, dim3(256), src, dst, bt.stride, bt.d_len, G, B);
+  else KZ_LAUNCH(ctx, KID_TEXT_FWD, (k_tf_emit<false, false>), eg, dim3(256), src, dst, bt.stride, bt.d_len, G, B);
   KZ_LAUNCH(ctx, KID_TEXT_FWD, k_tf_scan, dim3(B), dim3(256), bt.d_len, G, B);
-  KZ_LAUNCH(ctx, KID_TEXT_FWD, k_tf_emit<true>, dim3((G.maxTiles + 3) / 4, B), dim3(256), src, dst, bt.stride, bt.d_len, G, B);
+  if (J.variant1) KZ_LAUNCH(ctx, KID_TEXT_FWD, (k_tf_emit<true, true>), eg, dim3(256), src, dst, bt.stride, bt.d_len, G, B);
+  else KZ_LAUNCH(ctx, KID_TEXT_FWD, (k_tf_emit<true, false>), eg, dim3(256), src, dst, bt.stride, bt.d_len, G, B);
   return 0;
 }
 
@@ -637,7 +678,7 @@ int kz_text_fwd_gpu_finish(kz_ctx* ctx, kz_batch& bt, TextFwdJob& J, std::vector
     KZ_HIP(kz_stream_sync(ctx, st));
   }
   KZ_HIP(hipGetLastError());
-  if (ctx->sw.textGpuTrace) fprintf(stderr, "[textfwd] took %d blocks, finished %d (kept %d after the statistics)\n", J.A, nDone, J.kept);
+  if (ctx->sw.textGpuTrace) fprintf(stderr, "[textfwd%s] took %d blocks, finished %d (kept %d after the statistics)\n", J.variant1 ? "1" : "", J.A, nDone, J.kept);
   ctx->arenaTop = J.mark; J.holder = nullptr;
   J.live = false;
   return 0;
