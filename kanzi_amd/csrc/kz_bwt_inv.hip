@@ -472,7 +472,7 @@ int kz_stage_bwt_inverse(kz_ctx* ctx, kz_batch& bt) {
   BwtInv V;
   V.NS = (int64_t)kz_align((size_t)(maxN > 0 ? maxN : 1), BI_TILE);
   V.T = (int)(V.NS / BI_TILE);
-  // the large arrays only exist for the blocks that have data: a lengths-masked view of a batch (kz_api.hip: one cost class
+  // the large arrays only exist for the blocks that have data: a lengths-masked view of a batch (kz_overlap.hip: one cost class
   // of the decoder's overlapped schedule) takes its share of the scratch, and the classes' stages can be in flight together
   int A = 0;
   for (int b = 0; b < B; b++) if (bt.h_len[b] > 0) A++;

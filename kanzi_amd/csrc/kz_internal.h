@@ -64,7 +64,7 @@ struct kz_switches {
   int textFwdGpu = -1;           // KZ_TEXT_FWD_GPU: -1 unset, 0 host, 1 any batch
   int textFwdGpuMin = 256;       // KZ_TEXT_FWD_GPU_MIN
   int text1FwdGpu = -1;          // KZ_TEXT1_FWD_GPU: the same for TextCodec1 streams (FPAQ / CM / ANS1): -1 unset, 0 host, 1 any batch
-  int text1FwdGpuMin = 64;       // KZ_TEXT1_FWD_GPU_MIN: batch size from which the unset case uses the device (0 = never; the default: kz_api.hip, text_fwd_gpu_on)
+  int text1FwdGpuMin = 64;       // KZ_TEXT1_FWD_GPU_MIN: batch size from which the unset case uses the device (0 = never; the default: kz_overlap.hip, text_fwd_gpu_on)
   int utfGpu = 1;                // KZ_UTF_GPU=0: UTF inverse on the host
   int utfFwdGpu = -1;            // KZ_UTF_FWD_GPU: -1 unset (with the device TEXT forward), 0 host, 1 any batch
   int textGpuTrace = 0;          // KZ_TEXT_GPU_TRACE
@@ -142,11 +142,11 @@ struct kz_ctx {
   struct Stage { uint8_t* p = nullptr; size_t cap = 0; };
   Stage pinIn[2], pinOut[2];       // pinned host memory (hipHostMalloc)
   Stage devIn[2], devOut[2];       // HBM outside the arena (the arena is reset by every batched call)
-  Stage hsIn[2], hsOut[2];         // pinned: the host-stage pipeline's copy of a chunk's blocks / the stages' outputs (kz_api.hip)
+  Stage hsIn[2], hsOut[2];         // pinned: the host-stage pipeline's copy of a chunk's blocks / the stages' outputs (kz_encode.hip, kz_decode.hip)
   Stage tfIn, tfOut[2];           // pinned: the device TEXT forward's host passes (kz_encode_blocks_pre).  Their own buffers and
   hipStream_t tfCopy = nullptr;    // stream: kz_compress's upload thread fills hsOut[k & 1] / drains on copyDown for the NEXT chunk meanwhile
   hipStream_t copyUp = nullptr, copyDown = nullptr;
-  Stage hiAux[2];                  // HBM: per-block lengths / masks of the decoder's host-inverse chunks (kz_api.hip)
+  Stage hiAux[2];                  // HBM: per-block lengths / masks of the decoder's host-inverse chunks (kz_decode.hip, kz_host_stages.hip)
   hipStream_t hiStream[2] = {nullptr, nullptr};   // their gather / scatter kernels run beside the main stream's next chunk
   Stage knzPin, knzAux;            // pinned / HBM: the device stream calls' per-chunk tables (bit offsets, lengths, header bytes; kz_stream_device.hip)
   // waits of the context's own thread: 1 = block on an event (hipEventBlockingSync) instead of hipStreamSynchronize's spin loop.
@@ -281,7 +281,7 @@ void kz_ktimer_flush(kz_ctx* ctx);     // call after the stream has been synchro
 
 // ---- host (CPU) stages in front of the GPU chain: TEXT and UTF (kz_text.hip) ----
 bool kz_is_host_transform(int type);
-bool kz_fast_coder(int entropyType);    // kz_api.hip: NONE / ANS0 / HUFFMAN / RANGE, the entropy table's flag
+bool kz_fast_coder(int entropyType);    // kz_pipe.hip: NONE / ANS0 / HUFFMAN / RANGE, the entropy table's flag
 int kz_host_block_data_type(const uint8_t* p, int n, int init);
 int kz_host_transform_forward(int type, int entropyType, int blockSize, int* dataType, const uint8_t* src, int n, uint8_t* dst, int dstCap, int* produced);
 int kz_host_transform_inverse(int type, int blockSize, const uint8_t* src, int n, uint8_t* dst, int dstCap, int* produced);
@@ -291,7 +291,7 @@ size_t kz_text_gpu_scratch_per_block(int blockSize);
 size_t kz_text_fwd_gpu_scratch(int B, int blockSize, int maxLen, bool variant1);
 // kz_utf_fwd_gpu.hip: UTFCodec.forward of the blocks TEXT declined with "dataType" UTF8 (done[b]: 1 applied, 2 declined by the reference's rules, 0 host stage)
 int kz_utf_fwd_gpu(kz_ctx* ctx, kz_batch& bt, const std::vector<int32_t>& take, std::vector<int32_t>& done);
-bool kz_text_fwd_gpu_applies(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int nBlocks);   // kz_api.hip
+bool kz_text_fwd_gpu_applies(kz_ctx* ctx, uint64_t transformType, uint32_t entropyType, int nBlocks);   // kz_overlap.hip
 struct TextFwdJob;
 TextFwdJob* kz_text_fwd_gpu_new();
 void kz_text_fwd_gpu_free(TextFwdJob*);

@@ -719,7 +719,7 @@ __global__ __launch_bounds__(512) void k_sbrt_inverse(const u8* __restrict__ src
                                                        const int32_t* __restrict__ d_len, const int32_t* __restrict__ order, int wavesPerGroup, int prio) {
   const int b = __builtin_amdgcn_readfirstlane(order[blockIdx.x * wavesPerGroup + (int)(threadIdx.x >> 6)]);
   if (b < 0) return;
-  // one serial chain per wave.  The overlapped decoder schedule (kz_api.hip) runs several launches of this kernel and HBM-bound
+  // one serial chain per wave.  The overlapped decoder schedule (kz_overlap.hip) runs several launches of this kernel and HBM-bound
   // kernels on the same SIMDs: the launch on the critical path (the most expensive blocks) issues ahead of its neighbours
   const bool useOldCold = (prio & 8) != 0;                          // A/B switch (KZ_SBRT_OLDCOLD): cold rows in the by-position layout
   if ((prio & 7) >= 2) __builtin_amdgcn_s_setprio(3);

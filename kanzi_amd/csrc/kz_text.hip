@@ -3,7 +3,7 @@
 //          NONE/ANS0/HUFFMAN/RANGE: TransformFactory.java:275-286; the variant is bit 0x10 of the first coded byte, :496-528)
 //   UTF  = K/transform/UTFCodec.java (UTF-8 code points -> one- or two-byte aliases ranked by frequency)
 // Both are branchy sequential dictionary coders whose output depends on the exact order of dictionary updates; they run per
-// block on host threads in front of (forward) or behind (inverse) the batched GPU stages (kz_api.hip).
+// block on host threads in front of (forward) or behind (inverse) the batched GPU stages (kz_host_stages.hip).
 //
 // Data structures differ from the reference's object graph: the dictionary is a table of plain records indexed by word
 // number, the hash map holds word numbers (-1 = empty) instead of references, and one arena per thread is reused from
@@ -751,7 +751,7 @@ void kz_text_static_tables(std::vector<uint32_t>& hash, std::vector<int32_t>& po
   for (int c = 0; c < 256; c++) delim[c] = sd.delim[c] ? 1 : 0;
 }
 
-// ---- entry points used by kz_api.hip / kz_stream.hip ----
+// ---- entry points used by kz_api.hip / kz_host_stages.hip / kz_stream.hip ----
 bool kz_is_host_transform(int type) { return type == KZ_T_TEXT || type == KZ_T_UTF; }
 
 // the writer's tag from the block's first four bytes (CompressedOutputStream.java:795-804)

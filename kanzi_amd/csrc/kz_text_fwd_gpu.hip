@@ -508,7 +508,7 @@ static int tf_log(int blockSize, bool variant1) {
   return l;
 }
 
-// bytes of scratch the stage wants for a batch of B blocks of at most maxLen bytes, all of them text (kz_api.hip sizes the arena with it):
+// bytes of scratch the stage wants for a batch of B blocks of at most maxLen bytes, all of them text (kz_encode.hip sizes the arena with it):
 // 4 bytes of `tok` per input byte, 16 bytes per hash slot and 4 per word number
 size_t kz_text_fwd_gpu_scratch(int B, int blockSize, int maxLen, bool variant1) {
   const size_t NS = kz_align((size_t)maxLen + 64, 256);

@@ -815,7 +815,7 @@ __global__ __launch_bounds__(256) void k_text_copy_back(const u8* __restrict__ s
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += gridDim.x * blockDim.x) d[i] = s[i];
 }
 
-// bytes of scratch per block taken (kz_api.hip sizes the arena with it)
+// bytes of scratch per block taken (kz_decode.hip sizes the arena with it)
 size_t kz_text_gpu_scratch_per_block(int blockSize) {
   int l1 = 13; if (blockSize >= 8) { l1 = 31 - __builtin_clz((unsigned)(blockSize / 8)); l1 = l1 > 26 ? 26 : (l1 < 13 ? 13 : l1); }
   return ((size_t)4 << l1) + (size_t)TG_MAXDICT * sizeof(TgWord) + 1024;

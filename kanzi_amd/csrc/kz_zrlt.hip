@@ -381,7 +381,7 @@ __global__ __launch_bounds__(64) void k_zrlt_i2(const int32_t* __restrict__ d_le
 }
 
 // zero the output of the blocks this call decodes, and only theirs (zero runs are "written" here).  Other slots of the
-// batch may be in use by another stream at this moment (the decoder's expensive-blocks-first schedule, kz_api.hip).
+// batch may be in use by another stream at this moment (the decoder's expensive-blocks-first schedule, kz_decode.hip).
 __global__ __launch_bounds__(256) void k_zrlt_izero(u8* __restrict__ dst, int64_t stride, const int32_t* __restrict__ d_len, ZiScratch S) {
   const int b = blockIdx.y;
   if (d_len[b] <= 0 || S.fail[b]) return;

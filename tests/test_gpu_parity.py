@@ -1136,7 +1136,7 @@ def test_async_batches_on_two_contexts(ctx):
 
 def test_overlapped_rank_bwt_inverse_schedule(ctx, monkeypatch):
     """Large batches decode the expensive blocks' RANK inverse on a side stream while the other blocks go on to the BWT
-    inverse (kz_api.hip: overlapped_rank_bwt_inverse).  Forced here on a small batch: same bytes, lengths and statuses as the
+    inverse (kz_overlap.hip: overlapped_rank_bwt_inverse).  Forced here on a small batch: same bytes, lengths and statuses as the
     stage-by-stage schedule, corrupted blocks and raw / copy blocks included."""
     bs, B = 65536, 40
     inp = np.stack([datagen.block(i, bs) for i in range(B)])
@@ -1166,7 +1166,7 @@ def test_overlapped_rank_bwt_inverse_schedule(ctx, monkeypatch):
 
 def test_expensive_blocks_first_decode_schedule(ctx, monkeypatch):
     """BWT+RANK+ZRLT / BWT+MTFT+ZRLT batches without empty or damaged-header blocks take the "expensive blocks first" decoder
-    schedule (kz_api.hip): the expensive group runs entropy decoding and ZRLT inverse first and starts its RANK inverse on the
+    schedule (kz_decode.hip): the expensive group runs entropy decoding and ZRLT inverse first and starts its RANK inverse on the
     side stream while the other group is still being entropy decoded.  Same results as the staged schedule, transformed-copy
     blocks (uniform data), blocks with ZRLT skipped and a damaged payload included."""
     bs, B = 131072, 40
