@@ -420,6 +420,58 @@ int32_t kz_decode_indexed_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n,
                                  const int64_t* blockBitOff /* host */, const int64_t* blockBits /* host */, int32_t nBlocks,
                                  uint8_t* d_dst, int64_t dstStride, kz_block_result* results /* host */);
 
+/* ---- scan: the blocks of a stream found without the walk, behind damage as well -----------------------
+ * Every other way into a stream walks the length prefixes from the front, and one damaged prefix, a lost byte or a cut ends that
+ * walk although every block behind the break is intact and independently coded.  The scan asks at EVERY bit position q behind the
+ * stream header whether a reader that stands there would accept a block:
+ *
+ *   accept(q)   the 5 + lr bits at q are a length prefix that fits in the stream, with W > 0, and the block of W bits behind it
+ *               (payload at pay = q + 5 + lr) passes what every reader checks before it decodes: the block-header precheck (header
+ *               sizes, the checksum byte, which mixes in W), the staging-row bound and pay + W <= 8 n.  succ(q) = pay + W.
+ *   final(s)    the prefix at s is the end marker (W == 0) and the byte that holds its last bit is byte n - 1.  An end marker in the
+ *               middle of the bytes is no end: runs of zeros are common inside payloads.
+ *   path        a sequence of accepted positions, each the succ of the one before.
+ *   kept        q is kept if and only if it lies on a path of at least minChain positions, or its path reaches a position s with
+ *               final(s).  With a kept q, an accepted succ(q) is kept as well.
+ *
+ * Between 1.5 (streams of 1 KiB blocks) and 7 (4 MiB blocks) in 10^4 positions of random bytes are accepted, the more the longer a W
+ * the stream's block size admits, and almost none of them has an accepted successor: minChain = 4 leaves chance
+ * hits of the order of one per hundreds of GiB of incompressible payload, and costs the runs of fewer than 4 intact blocks between
+ * two breaks (minChain = 1 keeps every accepted position).  The kept positions come back in ascending q, entry i as
+ * prefixBitOff[i] = q, blockBitOff[i] = pay, blockBits[i] = W -- the latter two exactly what kz_knz_index reports for a block and
+ * what kz_decode_indexed[_device] takes -- and next[i] = the index of the entry at succ(q), KZ_SCAN_END if final(succ(q)), else
+ * KZ_SCAN_BROKEN.  *head = the index of the entry at the first bit behind the stream header, KZ_SCAN_END for a stream that is header
+ * plus end marker, else KZ_SCAN_BROKEN.  On an intact stream the chain from *head is kz_knz_index's list.  Only *head says which
+ * chain is the stream's own: a .knz stored raw inside a block shows up as a chain of its own, and an accepted position off the
+ * stream's chain whose successor is a block of the stream is kept with it (a chance hit inside a payload; or a true prefix read a
+ * second time two bits early, with a wider length field and the same W, which gives a second entry with the same blockBitOff and
+ * blockBits: DESIGN 7).
+ *
+ * The device form tests the positions in two passes of the stream (k_knz_scan_count, then k_knz_scan_write: a workgroup per 4 KiB tile and
+ * its 16-byte halo, eight positions a lane, the accepted ones gathered in ascending order by per-tile counts and their scan) and
+ * links the accepted positions, which are sparse, by binary search (k_knz_scan_link, _run, _mark, _emit).  Its host waits do not
+ * grow with n; its scratch (the context's table buffers) is 52 bytes per accepted position and 12 bytes per tile; the link passes'
+ * work grows with minChain.
+ *
+ *   addresses   src / d_src: any address, any alignment.  Every array and every out-pointer is host memory in both calls.  The five
+ *               header out-pointers may be NULL; the four arrays may be NULL when cap == 0.
+ *   read        nothing outside src[0 .. n); bytes behind n never influence a result.  kz_knz_scan touches no GPU.
+ *   written     the header fields; *head; entries [0, min(returned count, cap)) of the four arrays, nothing behind them.  next[]
+ *               values point by index whether or not that index is below cap.
+ *   returns     the number of kept entries, which may exceed cap (call again with that many), or a negative code: the stream
+ *               header's as from kz_knz_index[_device] (n < 20 included; same kz_last_error texts on the device form),
+ *               -KZ_ERR_INVALID_PARAM for a null ctx, src, head or array, n < 0, cap < 0 or minChain < 1, -KZ_ERR_DEVICE.
+ *   stream      kz_knz_scan_device is synchronous and runs on the context's stream.
+ */
+enum { KZ_SCAN_END = -1, KZ_SCAN_BROKEN = -2 };
+int64_t kz_knz_scan(const uint8_t* src, int64_t n, int32_t minChain,
+                    uint64_t* transformType, uint32_t* entropyType, int32_t* blockSize, int64_t* inputSize, int32_t* checksumBits,
+                    int64_t* prefixBitOff, int64_t* blockBitOff, int64_t* blockBits, int64_t* next, int64_t cap, int64_t* head);
+int64_t kz_knz_scan_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, int32_t minChain,
+                           uint64_t* transformType, uint32_t* entropyType, int32_t* blockSize, int64_t* inputSize, int32_t* checksumBits,
+                           int64_t* prefixBitOff /* host */, int64_t* blockBitOff /* host */, int64_t* blockBits /* host */, int64_t* next /* host */,
+                           int64_t cap, int64_t* head /* host */);
+
 /* ---- byte-addressed reads: many ranges of the original data in one call ---------------------------
  * "Give me bytes [rangeOff[i], rangeOff[i] + rangeLen[i]) of the original data, for nRanges ranges at once", on host memory and on
  * device memory.  The index (blockBitOff, blockBits, nIndex) is the WHOLE stream's, exactly as kz_knz_index / kz_knz_index_device

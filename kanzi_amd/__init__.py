@@ -110,6 +110,8 @@ def load_library():
         "kz_knz_writer_add": (c.c_int32, [vp, u8p, c.c_int64]),
         "kz_knz_writer_close": (c.c_int64, [vp]),
         "kz_knz_index": (c.c_int32, [u8p, c.c_int64, vp, vp, vp, vp, vp, i64p, i64p, c.c_int32]),
+        "kz_knz_scan": (c.c_int64, [u8p, c.c_int64, c.c_int32, vp, vp, vp, vp, vp, i64p, i64p, i64p, i64p, c.c_int64, i64p]),
+        "kz_knz_scan_device": (c.c_int64, [vp, u8p, c.c_int64, c.c_int32, vp, vp, vp, vp, vp, i64p, i64p, i64p, i64p, c.c_int64, i64p]),
         "kz_compress_device": (c.c_int64, [vp, c.c_uint64, c.c_uint32, c.c_int32, u8p, c.c_int64, u8p, c.c_int64]),
         "kz_decompress_device": (c.c_int64, [vp, u8p, c.c_int64, u8p, c.c_int64]),
         "kz_knz_assemble_device": (c.c_int64, [vp, c.c_uint64, c.c_uint32, c.c_int32, c.c_int64, c.c_int32, u8p, c.c_int64, i64p, c.c_int32, u8p, c.c_int64]),
@@ -162,6 +164,7 @@ ABI_SYMBOLS = ["kz_abi_version", "kz_ctx_create", "kz_ctx_destroy", "kz_last_err
                "kz_read_bytes", "kz_read_bytes_device",
                "kz_write_bytes_bound", "kz_write_bytes", "kz_write_bytes_device",
                "kz_knz_splice_bound", "kz_knz_splice", "kz_knz_splice_device",
+               "kz_knz_scan", "kz_knz_scan_device",
                "kz_set_timing", "kz_get_stage_count", "kz_get_stage_ms", "kz_get_stage_alg_bytes", "kz_reset_timing",
                "kz_set_kernel_timing", "kz_get_kernel_count", "kz_get_kernel_name", "kz_get_kernel_ms", "kz_get_kernel_max_ms",
                "kz_get_kernel_launches", "kz_reset_kernel_timing"]
@@ -864,6 +867,135 @@ def knz_index_device(ctx, src, n):
         raise KanziError(-nb, "knz_index_device")
     return {"transform": tt.value, "entropy": et.value, "blockSize": bs.value, "inputSize": isz.value, "checksum": chk.value,
             "blocks": [(int(off[i]), int(bits[i])) for i in range(nb)]}
+
+
+# ---- scan: the blocks of a stream found without the walk (kz_knz_scan / kz_knz_scan_device) ----
+SCAN_END, SCAN_BROKEN = -1, -2
+
+
+def _scan(call, head_bytes, n, min_chain, what):
+    """call(minChain, header out-pointers ..., four arrays, cap, head) -> count; a second call when cap was too small"""
+    tt, et, bs, isz, chk, head = ctypes.c_uint64(0), ctypes.c_uint32(0), ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
+    cap = max(16, int(n) // 512)
+    while True:
+        cols = np.zeros((4, cap), dtype=np.int64)
+        k = call(int(min_chain), ctypes.addressof(tt), ctypes.addressof(et), ctypes.addressof(bs), ctypes.addressof(isz), ctypes.addressof(chk),
+                 cols[0].ctypes.data, cols[1].ctypes.data, cols[2].ctypes.data, cols[3].ctypes.data, cap, ctypes.addressof(head))
+        if k < 0:
+            raise KanziError(-k, what)
+        if k <= cap:
+            break
+        cap = int(k)
+    pre, off, bits, nxt = (cols[j][:k].tolist() for j in range(4))
+    if head.value >= 0:
+        header_bits = pre[head.value]                      # the entry behind the stream header starts where the header ends
+    elif head_bytes is not None:
+        header_bits = 160 + 16 * ((int.from_bytes(bytes(head_bytes[:20]), "big") >> 39) & 3)       # the 2-bit length of the size field, in 16-bit units
+    else:
+        header_bits = 160 + 16 * _size_field_units(isz.value)
+    return {"transform": tt.value, "entropy": et.value, "blockSize": bs.value, "inputSize": isz.value, "checksum": chk.value,
+            "blocks": list(zip(off, bits)), "prefix": pre, "next": nxt, "head": int(head.value),
+            "headerBits": header_bits, "streamBits": 8 * int(n)}
+
+
+def _size_field_units(n):
+    """the 16-bit units of the stream header's size field that this library's writer (and the reference's) uses for n input bytes"""
+    if n <= 0 or n >= 1 << 48:
+        return 0
+    if n >= 1 << 32:
+        return 3
+    units = 0
+    if n > 1 << 30:
+        n, units = n >> 4, 1
+    return units + ((n.bit_length() - 1) >> 4) + 1
+
+
+def knz_scan(data, min_chain=4):
+    """kz_knz_scan (host only, no GPU): the blocks that a reader would accept at ANY bit position of the .knz bytes `data`, found without
+    the walk and so behind damage as well -> knz_index's dict with "blocks" = the kept entries in ascending position, plus "prefix"
+    (the bit where each entry's length prefix starts), "next" (the index of the entry that follows it in the stream, SCAN_END, or
+    SCAN_BROKEN) and "head" (the entry behind the stream header, SCAN_END, or SCAN_BROKEN); "headerBits" and "streamBits" say where
+    the stream header ends and the stream itself.  An entry is kept if it lies on a run of at least min_chain blocks, or if its run
+    ends at the stream's end marker."""
+    L = load_library()
+    data = bytes(data)
+    src = np.frombuffer(data + b"\0" * 16, dtype=np.uint8)
+    return _scan(lambda mc, *a: L.kz_knz_scan(src.ctypes.data, len(data), mc, *a), data, len(data), min_chain, "knz_scan")
+
+
+def knz_scan_device(ctx, src, n, min_chain=4, head_bytes=None):
+    """kz_knz_scan_device: knz_scan of the n-byte stream at device address `src` -> the same dict.  "headerBits" is the position of
+    the entry at "head"; for a scan whose head is SCAN_END or SCAN_BROKEN it is read from head_bytes, the stream's first 20 bytes,
+    when the caller has them on the host (knz_salvage passes them), and is otherwise the header length that the writer gives a
+    stream of this "inputSize"."""
+    def call(mc, *a):
+        k = ctx.lib.kz_knz_scan_device(ctx.h, _ptr(src), int(n), mc, *a)
+        return int(ctx.check(k)) if k < 0 else k
+    return _scan(call, head_bytes, n, min_chain, "knz_scan_device")
+
+
+def knz_recover_index(scan):
+    """What a scan (knz_scan / knz_scan_device) holds of the stream, in stream order; pure Python -> (entries, gaps).  The scan's
+    entries are gone through in ascending prefix position; whenever one starts at or behind the end of what has been taken, its chain
+    is followed by "next" to its end.  The last entry of a chain that ends SCAN_BROKEN counts as taken up to its payload's first bit
+    only: the block in front of a break may be the damaged one, and then claims bits that are not its own (after a lost byte, the
+    first bits of the next block).  The price: kept entries whose prefix lies INSIDE that last block's payload are taken as well,
+    with their chains (a stream nested in it; chance hits at a small min_chain), and knz_salvage decodes them beside the block that
+    holds them; inside a block of an unbroken chain such entries are passed over.  entries = the indices into the scan's lists in that order (on an intact stream: the chain from
+    "head", which is kz_knz_index's list); gaps = [(first bit, end bit)] of what lies between the stream header and the stream's end
+    and belongs to no taken entry: their prefixes, payloads and the final end marker do."""
+    pre, blocks, nxt = scan["prefix"], scan["blocks"], scan["next"]
+    entries, gaps = [], []
+    pos = covered = scan["headerBits"]                     # entries in front of pos are passed over; bits in front of covered are taken
+    end = scan["streamBits"]
+    if not pre and scan["head"] == SCAN_END:
+        return entries, gaps
+    for i in range(len(pre)):
+        if pre[i] < pos:
+            continue
+        if pre[i] > covered:
+            gaps.append((covered, pre[i]))
+        j = i
+        while j >= 0:
+            entries.append(j)
+            pos = covered = max(covered, blocks[j][0] + blocks[j][1])
+            if nxt[j] == SCAN_END:
+                pos = covered = end
+            elif nxt[j] == SCAN_BROKEN:
+                pos = blocks[j][0]
+            j = nxt[j]
+    if covered < end:
+        gaps.append((covered, end))
+    return entries, gaps
+
+
+def knz_salvage(ctx, knz, min_chain=4):
+    """Everything that can still be read of a damaged .knz stream (bytes, or a torch.uint8 device tensor): scan it, put its chains in
+    stream order (knz_recover_index) and decode them by index -> [(prefix bit, payload bit, bits, status, bytes or None)], one per
+    recovered block in stream order; status is the block's own (0, or a negative code with None for its bytes).  The stream header
+    must be whole; what lies between the recovered blocks is knz_recover_index's gaps."""
+    if isinstance(knz, (bytes, bytearray, memoryview)):
+        data = bytes(knz)
+        scan = knz_scan(data, min_chain)
+        entries, _ = knz_recover_index(scan)
+        offs, bits = [scan["blocks"][i][0] for i in entries], [scan["blocks"][i][1] for i in entries]
+        out, res = decode_indexed(ctx, data, offs, bits, stride=scan["blockSize"]) if entries else (None, None)
+        rows = [out[k, :res[k].length].tobytes() if res[k].status == 0 else None for k in range(len(entries))]
+    else:
+        import torch
+        src = knz.reshape(-1)
+        torch.cuda.current_stream(src.device).synchronize()          # the calls run on the context's own stream
+        scan = knz_scan_device(ctx, src.data_ptr(), src.numel(), min_chain, head_bytes=src[:20].cpu().numpy().tobytes())
+        entries, _ = knz_recover_index(scan)
+        offs, bits = [scan["blocks"][i][0] for i in entries], [scan["blocks"][i][1] for i in entries]
+        rows = []
+        if entries:
+            bs = scan["blockSize"]
+            out = torch.empty((len(entries), bs), dtype=torch.uint8, device=src.device)
+            res = decode_indexed_device(ctx, src.data_ptr(), src.numel(), offs, bits, out.data_ptr(), bs)
+            host = out.cpu().numpy()
+            rows = [host[k, :res[k].length].tobytes() if res[k].status == 0 else None for k in range(len(entries))]
+    return [(scan["prefix"][i], offs[k], bits[k], int(res[k].status), rows[k]) for k, i in enumerate(entries)]
 
 
 def _byte_view(t):

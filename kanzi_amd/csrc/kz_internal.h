@@ -49,7 +49,9 @@
   X(KID_EXE_EMIT, "k_exe_emit") X(KID_KNZ_PACK, "k_knz_pack") X(KID_KNZ_WALK, "k_knz_walk") X(KID_KNZ_UNPACK, "k_knz_unpack") \
   X(KID_KNZ_CHECK, "k_knz_check") X(KID_KNZ_GATHER, "k_knz_gather") X(KID_KNZ_PACK_MANY, "k_knz_pack_many") X(KID_KNZ_HEADS, "k_knz_heads") \
   X(KID_KNZ_WALK_MANY, "k_knz_walk_many") X(KID_KNZ_UNPACK_MANY, "k_knz_unpack_many") X(KID_KNZ_SCATTER, "k_knz_scatter") \
-  X(KID_KNZ_CHECK_MANY, "k_knz_check_many") X(KID_KNZ_SPLICE, "k_knz_splice") X(KID_KNZ_READ, "k_knz_read") X(KID_KNZ_WRITE, "k_knz_write")
+  X(KID_KNZ_CHECK_MANY, "k_knz_check_many") X(KID_KNZ_SPLICE, "k_knz_splice") X(KID_KNZ_READ, "k_knz_read") X(KID_KNZ_WRITE, "k_knz_write") \
+  X(KID_KNZ_SCAN_COUNT, "k_knz_scan_count") X(KID_KNZ_SCAN_SUM, "k_knz_scan_sum") X(KID_KNZ_SCAN_WRITE, "k_knz_scan_write") X(KID_KNZ_SCAN_LINK, "k_knz_scan_link") \
+  X(KID_KNZ_SCAN_RUN, "k_knz_scan_run") X(KID_KNZ_SCAN_MARK, "k_knz_scan_mark") X(KID_KNZ_SCAN_EMIT, "k_knz_scan_emit")
 #define KZ_KERNEL_ENUM(id, name) id,
 #define KZ_KERNEL_NAME(id, name) name,
 enum KzKernelId { KZ_KERNELS(KZ_KERNEL_ENUM) KID_COUNT };
@@ -348,6 +350,15 @@ int kz_knz_read(kz_ctx*, const uint8_t* d_rows, int64_t stride, int rowLen, cons
 // apart; the launch owns the row units [unitBase, unitBase + units), d_seg[0].unit0 == unitBase
 struct KnzWriteSeg;
 int kz_knz_write(kz_ctx*, const uint8_t* d_data, int64_t dataLen, const KnzWriteSeg* d_seg, int ns, uint8_t* d_rows, int64_t stride, int64_t unitBase, int64_t units);
+// scan (kz_knz_scan_device): the rule (kz_knz_host.h) at every bit position of d_src[0 .. n), in tiles; d_tileOff[0 .. nTiles] = the
+// first index of every tile's accepted positions, d_tileOff[nTiles] = their number A; d_cols = kz_knz_scan_cols_bytes(A) bytes for
+// the link passes; d_out = four columns (prefix, payload, bits, next) of M = min(A, cap) entries; d_res = (kept entries, head)
+struct KnzScanRule;
+int64_t kz_knz_scan_tiles_of(const uint8_t* d_src, int64_t n);
+size_t kz_knz_scan_cols_bytes(int64_t A);
+int kz_knz_scan_count(kz_ctx*, const uint8_t* d_src, int64_t n, const KnzScanRule& R, int64_t nTiles, int32_t* d_cnt, int64_t* d_tileOff);
+int kz_knz_scan_links(kz_ctx*, const uint8_t* d_src, int64_t n, const KnzScanRule& R, int64_t nTiles, const int64_t* d_tileOff, uint8_t* d_cols, int64_t A, int mc);
+int kz_knz_scan_emit(kz_ctx*, const uint8_t* d_src, int64_t n, const KnzScanRule& R, uint8_t* d_cols, int64_t A, int64_t cap, int64_t* d_out, int64_t M, int64_t* d_res);
 
 // timing helpers
 void kz_stage_begin(kz_ctx*, hipEvent_t* e0);

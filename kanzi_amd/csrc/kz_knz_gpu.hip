@@ -6,6 +6,8 @@
 // where they are in their source streams, with the check of every piece against its own source in front of it (kz_knz_splice_device);
 // and the copy of the byte-addressed reads: many (range x block) segments of decoded rows to their places in one launch (k_knz_read),
 // with its mirror image for the byte-addressed writes: segments of new bytes into decoded rows (k_knz_write).
+// Last, the scan (kz_knz_scan_device): the reader's acceptance test at every bit position of a stream and the link step over the
+// accepted positions (k_knz_scan_*), which finds a stream's blocks without the walk and behind damage.
 // The callers (kz_stream_device.hip: kz_compress_device / kz_decompress_device / kz_decompress_range_device / kz_decode_indexed_device /
 // kz_knz_assemble_device / kz_knz_index_device, the two many-stream calls, kz_knz_splice_device, kz_read_bytes_device and
 // kz_write_bytes_device) do the bit-offset arithmetic, the stream header and the block-header prechecks on the host; no payload byte
@@ -467,7 +469,231 @@ __global__ void __launch_bounds__(256) k_knz_unpack_many(const u8* __restrict__ 
   }
 }
 
+// ==== scan: the blocks of a stream found without the walk (kz_knz_scan_device) ================================================
+// The rule (accept, final: kz_knz_host.h, one definition for host and device) asked at every bit position behind the stream header,
+// then the link step over the accepted positions, which are sparse (1.5 to 7 in 10^4 positions of random bytes, by the stream's block size).
+
+// ---- pass 1: every bit position --------------------------------------------------------------------------------------------------
+// A workgroup takes a tile of KNZ_SCAN_TILE bytes of MEMORY (tiles start at multiples of the tile size from the 16-byte aligned
+// address at or below src, so that the loads are aligned words whatever src's alignment is; what a tile holds in front of src or behind
+// src + n reads as zero and is no position) and the 16 bytes behind it (the test looks at no more than 16 bytes from q's byte on), as
+// big-endian words in LDS.  Lanes take consecutive bytes, eight positions each, 16 bytes a lane per tile.  The count form leaves the
+// tile's accepted positions in cnt[t]; the write form, behind the exclusive scan tileOff of those counts, stores them in ascending q
+// from index tileOff[t] on: positions ascend with (byte, bit), that is with (round, lane, bit), so a round's lanes take their places by
+// a prefix sum over the workgroup.  Nothing outside src[0 .. n) is read: a word is loaded whole only if it lies inside, else bytewise.
+#define KNZ_SCAN_TILE 4096
+#define KNZ_SCAN_WORDS (KNZ_SCAN_TILE / 4 + 4)
+// the exclusive prefix sum of c over the workgroup's 256 lanes and its total (ws: 4 ints of LDS; every lane calls, two barriers)
+__device__ __forceinline__ int knz_block_excl(int c, int* ws, int& total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int incl = c;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+  if (lane == 63) ws[wv] = incl;
+  __syncthreads();
+  int base = 0;
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < 4; w++) { const int s = ws[w]; if (w < wv) base += s; total += s; }
+  __syncthreads();
+  return base + incl - c;
+}
+template <bool WRITE>
+__device__ __forceinline__ void knz_scan_tiles(const u8* __restrict__ src, int64_t n, const KnzScanRule& R, int64_t nTiles, int32_t* __restrict__ cnt,
+                                               const int64_t* __restrict__ tileOff, int64_t* __restrict__ oq, int64_t* __restrict__ opay, int64_t* __restrict__ oW) {
+  __shared__ u32 win[KNZ_SCAN_WORDS];
+  __shared__ int ws[4];
+  const uintptr_t lo = (uintptr_t)src, hi = lo + (uintptr_t)n, A0 = lo & ~(uintptr_t)15;
+  for (int64_t t = blockIdx.x; t < nTiles; t += gridDim.x) {
+    const uintptr_t ta = A0 + (uintptr_t)t * KNZ_SCAN_TILE;
+    for (int w = threadIdx.x; w < KNZ_SCAN_WORDS; w += 256) {
+      const uintptr_t a = ta + 4 * (uintptr_t)w;
+      u32 v = 0;
+      if (a >= lo && a + 4 <= hi) v = __builtin_bswap32(*(const u32*)a);
+      else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) v = (v << 8) | ((a + k >= lo && a + k < hi) ? (u32) * (const u8*)(a + k) : 0u);
+      }
+      win[w] = v;
+    }
+    __syncthreads();
+    int mine = 0;
+    int64_t run = WRITE ? tileOff[t] : 0;
+    for (int it = 0; it < KNZ_SCAN_TILE / 256; it++) {
+      const int B = it * 256 + (int)threadIdx.x;
+      const int64_t by = (int64_t)(ta - lo) + B;                                      // the byte's index in the stream (< 0: in front of it)
+      u32 mask = 0;
+      uint64_t a = 0, b = 0;
+      if (by >= 0 && by < n && by * 8 + 7 >= R.hdrEnd) {
+        const int wi = B >> 2, s = (B & 3) << 3;
+        u32 w[5], o[4];
+#pragma unroll
+        for (int i = 0; i < 5; i++) w[i] = win[wi + i];
+#pragma unroll
+        for (int i = 0; i < 4; i++) o[i] = s ? ((w[i] << s) | (w[i + 1] >> (32 - s))) : w[i];
+        a = ((u64)o[0] << 32) | o[1];
+        b = ((u64)o[2] << 32) | o[3];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          int64_t pay, W;
+          if (by * 8 + k >= R.hdrEnd && knz_scan_accept(a, b, by * 8 + k, R, pay, W)) mask |= 1u << k;
+        }
+      }
+      if (!WRITE) { mine += __popc(mask); continue; }
+      int total;
+      int64_t at = run + knz_block_excl(__popc(mask), ws, total);
+      run += total;
+      for (; mask; mask &= mask - 1, at++) {
+        const int64_t q = by * 8 + (__ffs((int)mask) - 1);
+        int64_t pay = 0, W = 0;
+        knz_scan_prefix(a, b, q, R.nbits, pay, W);
+        oq[at] = q; opay[at] = pay; oW[at] = W;
+      }
+    }
+    if (!WRITE) {
+      int total;
+      knz_block_excl(mine, ws, total);
+      if (threadIdx.x == 0) cnt[t] = total;
+    }
+    __syncthreads();                                                                  // the window is the next tile's
+  }
+}
+__global__ void __launch_bounds__(256) k_knz_scan_count(const u8* __restrict__ src, int64_t n, KnzScanRule R, int64_t nTiles, int32_t* __restrict__ cnt) {
+  knz_scan_tiles<false>(src, n, R, nTiles, cnt, nullptr, nullptr, nullptr, nullptr);
+}
+__global__ void __launch_bounds__(256) k_knz_scan_write(const u8* __restrict__ src, int64_t n, KnzScanRule R, int64_t nTiles, const int64_t* __restrict__ tileOff,
+                                                        int64_t* __restrict__ oq, int64_t* __restrict__ opay, int64_t* __restrict__ oW) {
+  knz_scan_tiles<true>(src, n, R, nTiles, nullptr, tileOff, oq, opay, oW);
+}
+// out[j] = in[0] + .. + in[j - 1] for j in 0 .. m: the tiles' counts to their first indices, the keep flags to ranks.  One workgroup
+// goes through the array in rounds of 4096 entries, four neighbours a lane, and carries the sum from round to round.
+__global__ void __launch_bounds__(1024) k_knz_scan_sum(const int32_t* __restrict__ in, int64_t m, int64_t* __restrict__ out) {
+  __shared__ int ws[16];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int64_t carry = 0;
+  for (int64_t base = 0; base < m; base += 4096) {
+    const int64_t j0 = base + 4 * tid;
+    int v[4], s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) { v[k] = j0 + k < m ? in[j0 + k] : 0; s += v[k]; }
+    int incl = s;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+    if (lane == 63) ws[wv] = incl;
+    __syncthreads();
+    int64_t at = carry + incl - s;
+    int total = 0;
+#pragma unroll
+    for (int w = 0; w < 16; w++) { const int x = ws[w]; if (w < wv) at += x; total += x; }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; k++) if (j0 + k < m) { out[j0 + k] = at; at += v[k]; }
+    carry += total;
+  }
+  if (tid == 0) out[m] = carry;
+}
+
+// ---- the link passes: over the A accepted positions, ascending in q --------------------------------------------------------------
+// What knz_scan_link (kz_knz_host.h) defines, a lane per position.  link: sidx[i] = the entry at succ(i) = pay[i] + W[i], by binary
+// search behind i, or -1, and then fin[i] = final(succ(i)).  run: fwd[i] = the positions on the path from i on, counted up to mc; keep[i]
+// = 1 if that path has mc of them or ends in front of a final marker.  mark: from every i along its path, at most mc - 1 links: entry
+// j, d links on, lies on a path of d + fwd[j] positions that starts at i, and is kept when those are mc (every lane stores the same 1).
+// A path of mc positions through j has such a start no more than mc - 1 links in front of j, so this is the rule.  The work of run and
+// mark grows with mc.
+struct KnzScanCols { int64_t *q, *pay, *W, *sidx, *rank; int32_t *fwd, *fin, *keep; };
+__global__ void __launch_bounds__(256) k_knz_scan_link(const u8* __restrict__ src, int64_t n, KnzScanCols c, int64_t A) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A) return;
+  const int64_t s = c.pay[i] + c.W[i];
+  int64_t lo = i + 1, hi = A;                                                       // invariant: q of entries < lo is < s
+  while (lo < hi) { const int64_t m = (lo + hi) >> 1; if (c.q[m] < s) lo = m + 1; else hi = m; }
+  const bool hit = lo < A && c.q[lo] == s;
+  uint64_t a = 0, b = 0;
+  if (!hit) knz_scan_window(src, n, s >> 3, a, b);
+  c.sidx[i] = hit ? lo : -1;
+  c.fin[i] = (!hit && knz_scan_final(a, b, s, n << 3)) ? 1 : 0;
+}
+__global__ void __launch_bounds__(256) k_knz_scan_run(KnzScanCols c, int64_t A, int mc) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A) return;
+  int64_t j = i;
+  int len = 1;
+  while (len < mc && c.sidx[j] >= 0) { j = c.sidx[j]; len++; }
+  c.fwd[i] = len;
+  c.keep[i] = (len >= mc || (c.sidx[j] < 0 && c.fin[j])) ? 1 : 0;
+}
+__global__ void __launch_bounds__(256) k_knz_scan_mark(KnzScanCols c, int64_t A, int mc) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A) return;
+  int64_t j = c.sidx[i];
+  for (int d = 1; d < mc && j >= 0; d++, j = c.sidx[j])
+    if (d + c.fwd[j] >= mc) c.keep[j] = 1;
+}
+// The kept entries in ascending order, behind the exclusive scan `rank` of keep: entry i goes to index rank[i] if that is below cap,
+// with next = the rank of the entry at its succ (kept with it), or KNZ_SCAN_END / _BROKEN.  res[0] = the kept entries, res[1] = head:
+// the entry at hdrEnd if it is kept (the first of all then), else END / BROKEN by final(hdrEnd).
+__global__ void __launch_bounds__(256) k_knz_scan_emit(const u8* __restrict__ src, int64_t n, int64_t hdrEnd, KnzScanCols c, int64_t A, int64_t cap,
+                                                       int64_t* __restrict__ oq, int64_t* __restrict__ opay, int64_t* __restrict__ oW, int64_t* __restrict__ onext,
+                                                       int64_t* __restrict__ res) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) {
+    uint64_t a, b;
+    knz_scan_window(src, n, hdrEnd >> 3, a, b);
+    res[0] = A > 0 ? c.rank[A] : 0;
+    res[1] = (A > 0 && c.q[0] == hdrEnd && c.keep[0]) ? 0 : (knz_scan_final(a, b, hdrEnd, n << 3) ? KNZ_SCAN_END : KNZ_SCAN_BROKEN);
+  }
+  if (i >= A || !c.keep[i]) return;
+  const int64_t r = c.rank[i];
+  if (r >= cap) return;
+  const int64_t j = c.sidx[i];
+  oq[r] = c.q[i]; opay[r] = c.pay[i]; oW[r] = c.W[i];
+  onext[r] = j >= 0 ? c.rank[j] : (c.fin[i] ? KNZ_SCAN_END : KNZ_SCAN_BROKEN);
+}
+
 // ---- launchers -------------------------------------------------------------------------------------------------------------------
+// the scan's steps (kz_knz_scan_device): the tiles' counts and their scan into d_tileOff[0 .. nTiles]; the accepted positions; the
+// link passes and the ranks; the kept entries.  The columns of A entries (rank: A + 1) lie one after the other from d_cols on.
+int64_t kz_knz_scan_tiles_of(const uint8_t* d_src, int64_t n) {
+  const uintptr_t lo = (uintptr_t)d_src, A0 = lo & ~(uintptr_t)15;
+  return (int64_t)((lo + (uintptr_t)n - A0 + KNZ_SCAN_TILE - 1) / KNZ_SCAN_TILE);
+}
+size_t kz_knz_scan_cols_bytes(int64_t A) { return (size_t)(5 * A + 1) * 8 + 3 * kz_align((size_t)A * 4, 8); }
+static inline KnzScanCols knz_scan_cols(uint8_t* d_cols, int64_t A) {
+  KnzScanCols c;
+  int64_t* p = (int64_t*)d_cols;
+  c.q = p; c.pay = p + A; c.W = p + 2 * A; c.sidx = p + 3 * A; c.rank = p + 4 * A;
+  const size_t w = kz_align((size_t)A * 4, 8);
+  uint8_t* z = (uint8_t*)(p + 5 * A + 1);
+  c.fwd = (int32_t*)z; c.fin = (int32_t*)(z + w); c.keep = (int32_t*)(z + 2 * w);
+  return c;
+}
+static inline dim3 knz_scan_grid(int64_t nTiles) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(nTiles, 1 << 20))); }
+int kz_knz_scan_count(kz_ctx* ctx, const uint8_t* d_src, int64_t n, const KnzScanRule& R, int64_t nTiles, int32_t* d_cnt, int64_t* d_tileOff) {
+  KZ_LAUNCH(ctx, KID_KNZ_SCAN_COUNT, k_knz_scan_count, knz_scan_grid(nTiles), dim3(256), d_src, n, R, nTiles, d_cnt);
+  KZ_LAUNCH(ctx, KID_KNZ_SCAN_SUM, k_knz_scan_sum, dim3(1), dim3(1024), (const int32_t*)d_cnt, nTiles, d_tileOff);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_scan_links(kz_ctx* ctx, const uint8_t* d_src, int64_t n, const KnzScanRule& R, int64_t nTiles, const int64_t* d_tileOff, uint8_t* d_cols, int64_t A, int mc) {
+  if (A <= 0) return 0;
+  const KnzScanCols c = knz_scan_cols(d_cols, A);
+  const dim3 g((unsigned)((A + 255) / 256));
+  KZ_LAUNCH(ctx, KID_KNZ_SCAN_WRITE, k_knz_scan_write, knz_scan_grid(nTiles), dim3(256), d_src, n, R, nTiles, d_tileOff, c.q, c.pay, c.W);
+  KZ_LAUNCH(ctx, KID_KNZ_SCAN_LINK, k_knz_scan_link, g, dim3(256), d_src, n, c, A);
+  KZ_LAUNCH(ctx, KID_KNZ_SCAN_RUN, k_knz_scan_run, g, dim3(256), c, A, mc);
+  if (mc > 1) KZ_LAUNCH(ctx, KID_KNZ_SCAN_MARK, k_knz_scan_mark, g, dim3(256), c, A, mc);
+  KZ_LAUNCH(ctx, KID_KNZ_SCAN_SUM, k_knz_scan_sum, dim3(1), dim3(1024), (const int32_t*)c.keep, A, c.rank);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_scan_emit(kz_ctx* ctx, const uint8_t* d_src, int64_t n, const KnzScanRule& R, uint8_t* d_cols, int64_t A, int64_t cap, int64_t* d_out, int64_t M, int64_t* d_res) {
+  const KnzScanCols c = knz_scan_cols(d_cols, A);
+  KZ_LAUNCH(ctx, KID_KNZ_SCAN_EMIT, k_knz_scan_emit, dim3((unsigned)std::max<int64_t>(1, (A + 255) / 256)), dim3(256), d_src, n, R.hdrEnd, c, A, cap,
+            d_out, d_out + M, d_out + 2 * M, d_out + 3 * M, d_res);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+
 static inline dim3 knz_pack_grid(int64_t units) { return dim3((unsigned)std::min<int64_t>((units + 255) / 256, 1 << 20)); }
 static inline dim3 knz_unpack_grid(int nb, int64_t maxBytes) {
   const int64_t units = (maxBytes + 15) >> 4;

@@ -1,8 +1,8 @@
 // kz_knz_host.h -- the host-only core of the .knz container: bit I/O, the stream header, the chain of block length prefixes, the
-// block-header precheck and the check of an index entry, the plan of a splice and its host copy, the plan of a byte-addressed read
+// block-header precheck and the check of an index entry, the scan's rule, link step and host loop, the plan of a splice and its host copy, the plan of a byte-addressed read
 // and that of a byte-addressed write, and the container's rules that every call must share, each written once.
 // This is the part that parses untrusted input.  It needs no GPU and no HIP header, so that a plain C++ program can run it under
-// the sanitizers (tools/knz_host_check.cpp, tools/knz_read_check.cpp, tools/knz_write_check.cpp); kz_stream.hip and kz_stream_device.hip are its users.
+// the sanitizers (tools/knz_host_check.cpp, tools/knz_scan_check.cpp, tools/knz_read_check.cpp, tools/knz_write_check.cpp); kz_stream.hip and kz_stream_device.hip are its users.
 // Layout: K/io/CompressedOutputStream.java (writeHeader :236-313, ordered block emission :1024-1035, end marker :483-493) and
 // K/io/CompressedInputStream.java (readHeader :359-515, block length prefix :1127-1129).
 #pragma once
@@ -12,6 +12,14 @@
 #include <algorithm>
 #include <vector>
 #include "../../include/kanzi_hip.h"
+
+// what the host and the device share by one definition (the block-header precheck and the scan's rule): host code in a plain C++
+// program, both in a HIP source
+#ifdef __HIPCC__
+#define KNZ_HD __host__ __device__
+#else
+#define KNZ_HD
+#endif
 
 struct HostBits {            // MSB-first writer (DefaultOutputBitStream.java:103-205)
   uint8_t* p; int64_t cap; uint64_t pos; bool overflow;
@@ -74,7 +82,7 @@ struct HostBitsIn {
     if (r) d[full] = (uint8_t)(get(r) << (8 - r));
   }
 };
-static inline uint32_t mix32(uint32_t c, uint32_t h, uint32_t v) { c ^= h * ~v; c = (c << 13) | (c >> 19); return c * 5u + 0x52DCE729u; }
+KNZ_HD inline uint32_t mix32(uint32_t c, uint32_t h, uint32_t v) { c ^= h * ~v; c = (c << 13) | (c >> 19); return c * 5u + 0x52DCE729u; }
 static inline int ilog2(uint32_t x) { return 31 - __builtin_clz(x); }
 
 // ---- the container's rules, one definition each ----
@@ -183,13 +191,16 @@ static inline int knz_read_prefix(HostBitsIn& bs, uint64_t& W) {
   return W == 0 ? KNZ_PREFIX_END : 0;
 }
 
-// Host restatement of DecodingTask.readBlockHeader + the two checks that follow it
+// Restatement of DecodingTask.readBlockHeader + the two checks that follow it
 // (CompressedInputStream.java:1025-1095, :1145-1164): the reference validates a block's header on the shared
 // bit stream BEFORE it reads the payload, so a truncated or tampered stream is reported with the header's error
 // (ERR_CRC_CHECK / ERR_BLOCK_SIZE / ERR_READ_FILE), not as a short read.  Returns 0 or -(error code).
-static inline int precheck_block_header(HostBitsIn bs /* by value: peek */, uint64_t W, int nbFunctions, int blockSize, int chkKind) {
+// One definition for the host and the device: over hdr = the first 64 bits of the block's stream, left aligned (the header is 7
+// bytes at the most; the device walk brings that word back), of which the stream holds the first `avail` (<= 64; what lies behind
+// them in hdr is not looked at).
+KNZ_HD inline int knz_precheck_word(uint64_t hdr, int avail, uint64_t W, int nbFunctions, int blockSize, int chkKind) {
   if (W < 8) return -KZ_ERR_BLOCK_SIZE;
-  const uint32_t mode = (uint32_t)bs.get(8);
+  const uint32_t mode = avail >= 8 ? (uint32_t)(hdr >> 56) : 0u;      // (a mode byte that does not fit reads as 0, and fails below)
   uint32_t skipFlags = 0;
   bool hasSkip = false;
   if (mode & 0x80) {
@@ -199,11 +210,11 @@ static inline int precheck_block_header(HostBitsIn bs /* by value: peek */, uint
   const int dataSize = 1 + (int)((mode >> 5) & 3);
   const int headerSize = 1 + (hasSkip ? 1 : 0) + dataSize + 1;
   if (W < (uint64_t)headerSize * 8) return -KZ_ERR_BLOCK_SIZE;
-  if (hasSkip) skipFlags = (uint32_t)bs.get(8);
-  uint32_t preLen = 0;
-  for (int i = 0; i < dataSize; i++) preLen = (preLen << 8) | (uint32_t)bs.get(8);
-  const uint32_t ck = (uint32_t)bs.get(8);
-  if (bs.error) return -KZ_ERR_READ_FILE;
+  if (avail < headerSize * 8) return -KZ_ERR_READ_FILE;
+  int at = 8;
+  if (hasSkip) { skipFlags = (uint32_t)(hdr >> 48) & 0xFF; at = 16; }
+  const uint32_t preLen = (uint32_t)((hdr << at) >> (64 - 8 * dataSize));
+  const uint32_t ck = (uint32_t)(hdr >> (56 - at - 8 * dataSize)) & 0xFF;
   const uint32_t HASH = 0x1E35A7BDu;
   uint32_t c = HASH * 0x01030507u;
   c = mix32(c, HASH, mode & 0xFF);
@@ -213,11 +224,19 @@ static inline int precheck_block_header(HostBitsIn bs /* by value: peek */, uint
   c = mix32(c, HASH, (uint32_t)W);
   c = (c >> 23) ^ (c >> 3);
   if (ck != (c & 0xFF)) return -KZ_ERR_CRC_CHECK;
-  const int64_t maxTL = std::min<int64_t>(std::max<int64_t>((int64_t)blockSize + blockSize / 2, 2048), 1LL << 30);
+  int64_t maxTL = (int64_t)blockSize + blockSize / 2;
+  if (maxTL < 2048) maxTL = 2048;
+  if (maxTL > (1LL << 30)) maxTL = 1LL << 30;
   if ((int32_t)preLen < 0 || (int64_t)preLen > maxTL) return -KZ_ERR_READ_FILE;
   const int checksumSize = (chkKind == 2) ? 8 : (chkKind == 1 ? 4 : 0);
   if ((int64_t)((W + 7) >> 3) > (int64_t)preLen + headerSize + checksumSize) return -KZ_ERR_BLOCK_SIZE;
   return 0;
+}
+// the same for a reader that stands at the block's first bit
+static inline int precheck_block_header(HostBitsIn bs /* by value: peek */, uint64_t W, int nbFunctions, int blockSize, int chkKind) {
+  const int avail = bs.pos < bs.nbits ? (int)std::min<uint64_t>(64, bs.nbits - bs.pos) : 0;
+  const uint64_t hdr = avail ? bs.get(avail) << (64 - avail) : 0;
+  return knz_precheck_word(hdr, avail, W, nbFunctions, blockSize, chkKind);
 }
 // A reader's checks on one block of W bits whose payload starts at bit `at` of a stream of nbits bits, in the reader's order: the
 // block header (peek: a reader at the payload's first bit), the staging-row bound, the payload's end inside the stream.  The indexed
@@ -255,6 +274,111 @@ static inline bool knz_check_entry(const uint8_t* src, int64_t n, int64_t hdrEnd
     if ((int)t.get(5) + 3 == lr && (int64_t)t.get(lr) == W) return true;
   }
   return false;
+}
+
+// ---- scan: the blocks of a stream found without the walk (kz_knz_scan / kz_knz_scan_device) ----
+// The rule, asked at a bit position q of a stream of nbits bits whose header ends at bit hdrEnd: would a reader that stands at q
+// accept a block?  accept(q): knz_read_prefix at q gives 0 and W > 0, and knz_check_block on the block behind it gives 0 (the header
+// precheck, the staging-row bound, the payload's end inside the stream).  The test is local: 5 + lr <= 39 prefix bits and at most 56
+// bits of block header, so with the (at most 7) bits in front of q in its byte it looks at no more than the 16 bytes from q's byte
+// on.  a, b = those 16 bytes as two big-endian words, zeros where the stream has ended.
+struct KnzScanRule { int64_t hdrEnd, nbits, maxBytes; int nbFunctions, blockSize, chkKind; };   // maxBytes: the staging-row bound, iS - 64
+static inline KnzScanRule knz_scan_rule(const KnzHeader& h, int64_t hdrEnd, int64_t n) {
+  return KnzScanRule{hdrEnd, n * 8, knz_dec_row_stride(h.blockSize) - 64, knz_nb_functions(h.transformType), h.blockSize, h.chkKind};
+}
+// the 64 bits from bit k (0 .. 127) of the 128-bit string a : b, zeros behind its end
+KNZ_HD inline uint64_t knz_bits128(uint64_t a, uint64_t b, int k) {
+  return k == 0 ? a : (k < 64 ? (a << k) | (b >> (64 - k)) : (k == 64 ? b : b << (k - 64)));
+}
+// the prefix at q: false when it does not fit; else pay = the bit behind it and W (0: the end marker's)
+KNZ_HD inline bool knz_scan_prefix(uint64_t a, uint64_t b, int64_t q, int64_t nbits, int64_t& pay, int64_t& W) {
+  if (q + 5 > nbits) return false;
+  const uint64_t x = knz_bits128(a, b, (int)(q & 7));
+  const int lr = (int)(x >> 59) + 3;
+  pay = q + 5 + lr;
+  if (pay > nbits) return false;
+  W = (int64_t)((x << 5) >> (64 - lr));
+  return true;
+}
+// accept(q), cheapest test first: the range of W, then the header's sizes and its checksum mix (knz_precheck_word)
+KNZ_HD inline bool knz_scan_accept(uint64_t a, uint64_t b, int64_t q, const KnzScanRule& R, int64_t& pay, int64_t& W) {
+  if (!knz_scan_prefix(a, b, q, R.nbits, pay, W)) return false;
+  if (W < 8 || W > R.nbits - pay || ((W + 7) >> 3) > R.maxBytes) return false;
+  const uint64_t hdr = knz_bits128(a, b, (int)(q & 7) + (int)(pay - q));
+  return knz_precheck_word(hdr, W < 64 ? (int)W : 64, (uint64_t)W, R.nbFunctions, R.blockSize, R.chkKind) == 0;   // (W <= nbits - pay: that much of hdr is the stream's)
+}
+// final(s): the end marker at s, and the byte behind it is the stream's last (an end marker in the middle of the bytes is no end:
+// runs of zeros are common inside payloads)
+KNZ_HD inline bool knz_scan_final(uint64_t a, uint64_t b, int64_t s, int64_t nbits) {
+  int64_t pay, W;
+  return knz_scan_prefix(a, b, s, nbits, pay, W) && W == 0 && ((pay + 7) >> 3) == (nbits >> 3);
+}
+// a, b for the byte `by` of src[0 .. n)
+KNZ_HD inline void knz_scan_window(const uint8_t* src, int64_t n, int64_t by, uint64_t& a, uint64_t& b) {
+  a = b = 0;
+  for (int i = 0; i < 8; i++) { a = (a << 8) | (by + i < n ? src[by + i] : 0u); b = (b << 8) | (by + 8 + i < n ? src[by + 8 + i] : 0u); }
+}
+enum { KNZ_SCAN_END = -1, KNZ_SCAN_BROKEN = -2 };                  // KZ_SCAN_END / KZ_SCAN_BROKEN (kanzi_hip.h)
+static inline int knz_scan_args(const void* src, int64_t n, int32_t minChain, const int64_t* prefixBitOff, const int64_t* blockBitOff, const int64_t* blockBits,
+                                const int64_t* next, int64_t cap, const int64_t* head) {
+  if (!src || n < 0 || cap < 0 || minChain < 1 || !head || (cap > 0 && (!prefixBitOff || !blockBitOff || !blockBits || !next))) return -KZ_ERR_INVALID_PARAM;
+  return 0;
+}
+// Which accepted positions are kept (the link step, the definition that the device's link kernels restate).  q[], pay[], W[]: the A
+// accepted positions in ascending q; succ(i) = pay[i] + W[i]; fin(s) = final(s).  A path is a run of accepted positions, each the
+// succ of the one before; i is kept if it lies on a path of at least minChain positions, or if its path ends in front of a final
+// marker.  sidx[i] = the entry at succ(i) or -1, fin[i] = final(succ(i)), keep[i] = 0 / 1.  (succ(i) > q[i]: one pass down gives
+// what lies in front of i, one pass up what lies behind it.)
+template <class F> static inline void knz_scan_link(const int64_t* q, const int64_t* pay, const int64_t* W, int64_t A, int64_t minChain, F fin_,
+                                                    std::vector<int64_t>& sidx, std::vector<uint8_t>& fin, std::vector<uint8_t>& keep) {
+  sidx.assign((size_t)A, -1); fin.assign((size_t)A, 0); keep.assign((size_t)A, 0);
+  std::vector<int64_t> fwd((size_t)A, 1), back((size_t)A, 1);
+  std::vector<uint8_t> reach((size_t)A, 0);
+  for (int64_t i = A - 1; i >= 0; i--) {
+    const int64_t s = pay[i] + W[i];
+    const int64_t j = std::lower_bound(q + i + 1, q + A, s) - q;
+    if (j < A && q[j] == s) { sidx[(size_t)i] = j; fwd[(size_t)i] = std::min<int64_t>(minChain, fwd[(size_t)j] + 1); reach[(size_t)i] = reach[(size_t)j]; }
+    else reach[(size_t)i] = fin[(size_t)i] = fin_(s) ? 1 : 0;
+  }
+  for (int64_t i = 0; i < A; i++) {
+    const int64_t j = sidx[(size_t)i];
+    if (j >= 0) back[(size_t)j] = std::max(back[(size_t)j], std::min<int64_t>(minChain, back[(size_t)i] + 1));
+    keep[(size_t)i] = (reach[(size_t)i] || back[(size_t)i] + fwd[(size_t)i] - 1 >= minChain) ? 1 : 0;   // (back[i] is final: every predecessor lies in front of i)
+  }
+}
+// kz_knz_scan: every bit position behind the stream header, the link step, the kept entries in ascending order
+static inline int64_t knz_scan_host(const uint8_t* src, int64_t n, int32_t minChain, uint64_t* transformType, uint32_t* entropyType, int32_t* blockSize, int64_t* inputSize,
+                                    int32_t* checksumBits, int64_t* prefixBitOff, int64_t* blockBitOff, int64_t* blockBits, int64_t* next, int64_t cap, int64_t* head) {
+  { const int rc = knz_scan_args(src, n, minChain, prefixBitOff, blockBitOff, blockBits, next, cap, head); if (rc) return rc; }
+  if (n < 20) return -KZ_ERR_INVALID_FILE;                         // (kz_knz_index's)
+  HostBitsIn bs{src, (uint64_t)n * 8, 0, false};
+  KnzHeader h;
+  { const int hrc = read_stream_header(bs, h, nullptr, 0); if (hrc) return hrc; }
+  knz_header_out(h, transformType, entropyType, blockSize, inputSize, checksumBits);
+  const KnzScanRule R = knz_scan_rule(h, (int64_t)bs.pos, n);
+  std::vector<int64_t> q, pay, W;
+  for (int64_t by = R.hdrEnd >> 3; by < n; by++) {
+    uint64_t a, b;
+    knz_scan_window(src, n, by, a, b);
+    for (int k = 0; k < 8; k++) {
+      int64_t p, w;
+      if (by * 8 + k >= R.hdrEnd && knz_scan_accept(a, b, by * 8 + k, R, p, w)) { q.push_back(by * 8 + k); pay.push_back(p); W.push_back(w); }
+    }
+  }
+  auto fin_ = [&](int64_t s) { uint64_t a, b; knz_scan_window(src, n, s >> 3, a, b); return knz_scan_final(a, b, s, R.nbits); };
+  const int64_t A = (int64_t)q.size();
+  std::vector<int64_t> sidx, rank((size_t)A + 1, 0);
+  std::vector<uint8_t> fin, keep;
+  knz_scan_link(q.data(), pay.data(), W.data(), A, minChain, fin_, sidx, fin, keep);
+  for (int64_t i = 0; i < A; i++) rank[(size_t)i + 1] = rank[(size_t)i] + keep[(size_t)i];
+  for (int64_t i = 0; i < A; i++) {
+    const int64_t r = rank[(size_t)i];
+    if (!keep[(size_t)i] || r >= cap) continue;
+    prefixBitOff[r] = q[(size_t)i]; blockBitOff[r] = pay[(size_t)i]; blockBits[r] = W[(size_t)i];
+    next[r] = sidx[(size_t)i] >= 0 ? rank[(size_t)sidx[(size_t)i]] : (fin[(size_t)i] ? KNZ_SCAN_END : KNZ_SCAN_BROKEN);   // (the entry at succ of a kept one is kept)
+  }
+  *head = (A > 0 && q[0] == R.hdrEnd && keep[0]) ? 0 : (fin_(R.hdrEnd) ? KNZ_SCAN_END : KNZ_SCAN_BROKEN);
+  return rank[(size_t)A];
 }
 
 // ---- splice: a new stream out of blocks of existing streams (kz_knz_splice / kz_knz_splice_device) ----

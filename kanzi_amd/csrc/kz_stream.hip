@@ -76,6 +76,12 @@ extern "C" int32_t kz_knz_index(const uint8_t* src, int64_t n, uint64_t* transfo
   return nb;
 }
 
+// The blocks of a stream found without the walk, in host memory: the rule, the link step and the loop are in kz_knz_host.h.
+extern "C" int64_t kz_knz_scan(const uint8_t* src, int64_t n, int32_t minChain, uint64_t* transformType, uint32_t* entropyType, int32_t* blockSize, int64_t* inputSize,
+                               int32_t* checksumBits, int64_t* prefixBitOff, int64_t* blockBitOff, int64_t* blockBits, int64_t* next, int64_t cap, int64_t* head) {
+  return knz_scan_host(src, n, minChain, transformType, entropyType, blockSize, inputSize, checksumBits, prefixBitOff, blockBitOff, blockBits, next, cap, head);
+}
+
 // A new stream out of blocks of existing streams, all in host memory: the plan and the copy are in kz_knz_host.h.
 extern "C" int64_t kz_knz_splice_bound(const int64_t* pieceBits, int32_t nPieces) { return knz_splice_bound(pieceBits, nPieces); }
 extern "C" int64_t kz_knz_splice(const uint8_t* src, const int64_t* srcOff, const int64_t* srcLen, int32_t nSrc,

@@ -207,6 +207,65 @@ extern "C" int32_t kz_knz_index_device(kz_ctx* ctx, const uint8_t* d_src, int64_
   return (int32_t)nb;
 }
 
+// kz_knz_scan with the stream in HBM: kz_knz_host.h's rule at every bit position (pass 1, in tiles) and its link step over the
+// accepted positions (kz_knz_gpu.hip).  Three waits whatever n is: the stream header, the number A of accepted positions (the
+// scratch is proportional to it; when the tables grow for it, the count pass runs once more), the results.  The table buffers hold, behind 64 bytes of front: the tiles' first indices and counts,
+// the four result columns of min(A, cap) entries, the link passes' columns.
+extern "C" int64_t kz_knz_scan_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n, int32_t minChain, uint64_t* transformType, uint32_t* entropyType, int32_t* blockSize,
+                                      int64_t* inputSize, int32_t* checksumBits, int64_t* prefixBitOff, int64_t* blockBitOff, int64_t* blockBits, int64_t* next,
+                                      int64_t cap, int64_t* head) {
+  if (!ctx) return -KZ_ERR_INVALID_PARAM;
+  { const int rc = knz_scan_args(d_src, n, minChain, prefixBitOff, blockBitOff, blockBits, next, cap, head); if (rc) return rc; }
+  if (n < 20) return -KZ_ERR_INVALID_FILE;
+  KZ_HIP(hipSetDevice(ctx->device));
+  KnzPlan P;
+  { const int rc = knz_open_device(ctx, d_src, n, P); if (rc) return rc; }
+  knz_header_out(P.h, transformType, entropyType, blockSize, inputSize, checksumBits);
+  const KnzScanRule R = knz_scan_rule(P.h, P.hdrEnd, n);
+  const int64_t nTiles = kz_knz_scan_tiles_of(d_src, n);
+  const size_t offAt = 64, cntAt = offAt + (size_t)(nTiles + 1) * 8, outAt = cntAt + kz_align((size_t)nTiles * 4, 8);
+  auto count = [&]() { return kz_knz_scan_count(ctx, d_src, n, R, nTiles, (int32_t*)(ctx->knzAux.p + cntAt), (int64_t*)(ctx->knzAux.p + offAt)); };
+  {                                                                                 // (the pinned side: the front, later the result columns)
+    int rc = kz_stage_reserve(ctx, ctx->knzPin, 64, true);
+    if (!rc) rc = kz_stage_reserve(ctx, ctx->knzAux, outAt, false);
+    if (!rc) rc = count();
+    if (rc) return rc;
+  }
+  KZ_HIP(hipMemcpyAsync(ctx->knzPin.p, ctx->knzAux.p + offAt + (size_t)nTiles * 8, 8, hipMemcpyDeviceToHost, ctx->stream));
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  const int64_t A = *(const int64_t*)ctx->knzPin.p;
+  if (A < 0 || A > n * 8 || A > 0x7FFFFFF0LL) { snprintf(ctx->err, sizeof(ctx->err), "knz scan: bad count"); return -KZ_ERR_DEVICE; }
+  const int64_t M = std::min(A, cap);
+  const size_t colsAt = outAt + (size_t)M * 32;
+  {
+    // A table that grows is a new allocation (kz_stage_reserve frees the old one first, so the same address may come back with other
+    // contents): whether it grew is decided by its capacity, and the tiles' first indices are then counted once more.
+    const size_t had = ctx->knzAux.cap;
+    int rc = kz_stage_reserve(ctx, ctx->knzPin, 64 + (size_t)M * 32, true);
+    if (!rc) rc = kz_stage_reserve(ctx, ctx->knzAux, colsAt + kz_knz_scan_cols_bytes(A), false);
+    if (!rc && ctx->knzAux.cap != had) rc = count();
+    if (rc) return rc;
+  }
+  const int mc = (int)std::min<int64_t>(minChain, A + 1);                           // (no path is longer than A)
+  int64_t* d_res = (int64_t*)ctx->knzAux.p;
+  int rc = kz_knz_scan_links(ctx, d_src, n, R, nTiles, (const int64_t*)(ctx->knzAux.p + offAt), ctx->knzAux.p + colsAt, A, mc);
+  if (!rc) rc = kz_knz_scan_emit(ctx, d_src, n, R, ctx->knzAux.p + colsAt, A, cap, (int64_t*)(ctx->knzAux.p + outAt), M, d_res);
+  if (rc) return rc;
+  KZ_HIP(hipMemcpyAsync(ctx->knzPin.p, d_res, 64, hipMemcpyDeviceToHost, ctx->stream));
+  if (M) KZ_HIP(hipMemcpyAsync(ctx->knzPin.p + 64, ctx->knzAux.p + outAt, (size_t)M * 32, hipMemcpyDeviceToHost, ctx->stream));
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  const int64_t K = ((const int64_t*)ctx->knzPin.p)[0];
+  if (K < 0 || K > A) { snprintf(ctx->err, sizeof(ctx->err), "knz scan: bad count"); return -KZ_ERR_DEVICE; }
+  *head = ((const int64_t*)ctx->knzPin.p)[1];
+  const int64_t got = std::min(K, cap);
+  const int64_t* out = (const int64_t*)(ctx->knzPin.p + 64);
+  int64_t* const cols[4] = {prefixBitOff, blockBitOff, blockBits, next};
+  for (int k = 0; k < 4; k++) if (got) memcpy(cols[k], out + k * M, (size_t)got * 8);
+  return K;
+}
+
 // kz_decompress_device and kz_decompress_range_device: decompress_host's contract (kz_stream.hip), source and destination in HBM.
 // kz_decompress looks at the room left in dst once per batch of ITS size (KnzPlan::NB), so chunks never straddle those batches and
 // carry the batch's count of blocks that may still start inside dst: both calls cut a stream at the same block.

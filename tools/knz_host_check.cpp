@@ -405,12 +405,87 @@ static void check_splice() {
   { const int64_t w1[1] = {-1}, w2[1] = {1LL << 34}; CHECK(knz_splice_bound(w1, 1) == -KZ_ERR_INVALID_PARAM && knz_splice_bound(w2, 1) == -KZ_ERR_INVALID_PARAM && knz_splice_bound(nullptr, 1) == -KZ_ERR_INVALID_PARAM && knz_splice_bound(nullptr, 0) == 27, "splice bound refusals"); }
 }
 
+// ---- precheck_block_header over the 64-bit header word (knz_precheck_word) against the byte-by-byte reader it replaced, restated
+//      here: the same code for every header, every W and every place where the stream may end inside or behind the header ----
+static int precheck_by_bytes(HostBitsIn bs, uint64_t W, int nbFunctions, int blockSize, int chkKind) {
+  if (W < 8) return -KZ_ERR_BLOCK_SIZE;
+  const uint32_t mode = (uint32_t)bs.get(8);
+  uint32_t skipFlags = 0;
+  bool hasSkip = false;
+  if (mode & 0x80) {
+    if (mode & 0x10) { if (nbFunctions > 4) hasSkip = true; else skipFlags = ((mode << 4) | 0x0F) & 0xFF; }
+  } else if (mode & 0x10) hasSkip = true;
+  else skipFlags = ((mode << 4) | 0x0F) & 0xFF;
+  const int dataSize = 1 + (int)((mode >> 5) & 3);
+  const int headerSize = 1 + (hasSkip ? 1 : 0) + dataSize + 1;
+  if (W < (uint64_t)headerSize * 8) return -KZ_ERR_BLOCK_SIZE;
+  if (hasSkip) skipFlags = (uint32_t)bs.get(8);
+  uint32_t preLen = 0;
+  for (int i = 0; i < dataSize; i++) preLen = (preLen << 8) | (uint32_t)bs.get(8);
+  const uint32_t ck = (uint32_t)bs.get(8);
+  if (bs.error) return -KZ_ERR_READ_FILE;
+  const uint32_t HASH = 0x1E35A7BDu;
+  uint32_t c = HASH * 0x01030507u;
+  c = mix32(c, HASH, mode & 0xFF);
+  c = mix32(c, HASH, skipFlags & 0xFF);
+  c = mix32(c, HASH, preLen);
+  c = mix32(c, HASH, (uint32_t)(W >> 32));
+  c = mix32(c, HASH, (uint32_t)W);
+  c = (c >> 23) ^ (c >> 3);
+  if (ck != (c & 0xFF)) return -KZ_ERR_CRC_CHECK;
+  const int64_t maxTL = std::min<int64_t>(std::max<int64_t>((int64_t)blockSize + blockSize / 2, 2048), 1LL << 30);
+  if ((int32_t)preLen < 0 || (int64_t)preLen > maxTL) return -KZ_ERR_READ_FILE;
+  const int checksumSize = (chkKind == 2) ? 8 : (chkKind == 1 ? 4 : 0);
+  if ((int64_t)((W + 7) >> 3) > (int64_t)preLen + headerSize + checksumSize) return -KZ_ERR_BLOCK_SIZE;
+  return 0;
+}
+static void check_precheck_forms() {
+  long codes[6] = {0, 0, 0, 0, 0, 0};
+  for (int it = 0; it < 40000; it++) {
+    const int phase = (int)(rnd() % 8), nbf = (it & 1) ? 3 : 6, chk = (int)(rnd() % 3);
+    const int blockSize = (it % 3) ? 1024 : 65536;
+    uint8_t raw[12];
+    for (int i = 0; i < 12; i++) raw[i] = (uint8_t)rnd();
+    if (it % 4 == 0) raw[0] = (uint8_t)(rnd() & 0x9F);                      // one length byte, so that small lengths pass the later checks
+    const Buf b = buf(12);
+    memcpy(b.get(), raw, 12);
+    uint64_t W = (it % 5 == 0) ? rnd() % 80 : (rnd() % 3 ? 8 * (uint64_t)(rnd() % 300) : ((uint64_t)rnd() << 3) | rnd() % 8);
+    if (it % 2 == 0) {                                                       // a checksum byte that fits: the checks behind it are reached
+      HostBitsIn t{b.get(), 96, (uint64_t)phase, false};
+      const uint32_t mode = (uint32_t)t.get(8);
+      const bool hasSkip = (mode & 0x10) && (!(mode & 0x80) || nbf > 4);
+      uint32_t skip = hasSkip ? (uint32_t)t.get(8) : (((mode & 0x80) && !(mode & 0x10)) ? 0u : (((mode << 4) | 0x0F) & 0xFF));
+      const int ds = 1 + (int)((mode >> 5) & 3);
+      uint32_t pre = 0;
+      for (int i = 0; i < ds; i++) pre = (pre << 8) | (uint32_t)t.get(8);
+      const uint32_t HASH = 0x1E35A7BDu;
+      uint32_t c = HASH * 0x01030507u;
+      c = mix32(c, HASH, mode); c = mix32(c, HASH, skip); c = mix32(c, HASH, pre); c = mix32(c, HASH, (uint32_t)(W >> 32)); c = mix32(c, HASH, (uint32_t)W);
+      const uint32_t want = ((c >> 23) ^ (c >> 3)) & 0xFF;
+      for (int k = 0; k < 8; k++) {                                           // at the place of the checksum byte, whatever the bit phase
+        const uint64_t bit = t.pos + k;
+        const uint8_t m = (uint8_t)(0x80 >> (bit & 7));
+        if ((want >> (7 - k)) & 1) b.get()[bit >> 3] |= m; else b.get()[bit >> 3] &= (uint8_t)~m;
+      }
+    }
+    for (uint64_t nbits = (uint64_t)phase; nbits <= 96; nbits++) {          // the stream ends anywhere from the block's first bit on
+      const HostBitsIn at{b.get(), nbits, (uint64_t)phase, false};
+      const int a = precheck_by_bytes(at, W, nbf, blockSize, chk), n = precheck_block_header(at, W, nbf, blockSize, chk);
+      CHECK(a == n, "precheck forms differ: %d against %d (W %llu, phase %d, %llu bits, %d functions)", a, n, (unsigned long long)W, phase, (unsigned long long)nbits, nbf);
+      codes[a == 0 ? 0 : (a == -KZ_ERR_BLOCK_SIZE ? 1 : (a == -KZ_ERR_READ_FILE ? 2 : (a == -KZ_ERR_CRC_CHECK ? 3 : 4)))]++;
+    }
+  }
+  CHECK(codes[0] > 1000 && codes[1] > 1000 && codes[2] > 1000 && codes[3] > 1000 && codes[4] == 0, "codes reached: %ld ok, %ld size, %ld read, %ld crc, %ld other",
+        codes[0], codes[1], codes[2], codes[3], codes[4]);
+}
+
 int main() {
   check_prefix_width();
   check_bit_io();
   check_stream_header();
   check_entries();
   check_block_header();
+  check_precheck_forms();
   check_rules();
   check_splice();
   printf("knz_host_check ok: %ld checks\n", checked);
