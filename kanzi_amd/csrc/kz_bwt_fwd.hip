@@ -21,44 +21,14 @@
 //   3. SA order: the members of an old group g occupy the slots g, g+1, ... in sorted order; a new group starts
 //      wherever the key changes; rank[val] = new head slot | LIVE, and suffixes whose new group is a singleton are
 //      final: sa[slot] = val.  Two max-scans (old-group start index, new-group start index) give the slots.
-#include "kz_device.h"
-#include "kz_internal.h"
+#include "kz_bwt_fwd.h"
 #include <stdlib.h>
 #include <algorithm>
 
 #define RS_ITEMS 16
 #define RS_TILE (KZ_WG * RS_ITEMS)   // 4096 elements per workgroup
-#define BW_LIVE 0x80000000u
 #define RSORT_TILE 16384               // keys per radix tile: a digit run of a tile averages 64 keys = 512 B
 #define RSORT_ITEMS (RSORT_TILE / KZ_WG)
-
-typedef unsigned long long u64;
-typedef uint32_t u32;
-typedef uint8_t u8;
-typedef u64 __attribute__((aligned(1))) bw_u64_unaligned;
-
-struct BwtArrays {
-  u64* key[2]; u32* val[2];
-  u32* rank; u32* sa;
-  u32* tileHist;     // [B][radix tiles][256 | MSD_BINS]
-  u32* digitBase;    // [B][MSD_BINS]
-  u32* bucketCnt;    // [B][MSD_BINS] elements per bucket of the current round (bit 31: too large for the LDS sort)
-  int32_t* d_w;      // [B] window start: the LSD passes and the k_seg_* kernels work on [d_w, d_m) of the compact arrays
-  int32_t* d_big;    // [B] d_m - d_w after k_msd_scan
-  u32* tileA;        // [B][T] scan temporaries
-  u32* tileB;        // [B][T]
-  u32* tileLive;     // [B][T] live suffixes of the text tile in the previous round (0 stays 0: suffixes only become final)
-  int32_t* d_n;      // [B] block length
-  int32_t* d_m;      // [B] compact size (current)
-  int32_t* d_m2;     // [B] compact size (next)
-  int64_t NS;        // element stride per block
-  int T;             // tile stride per block
-  int64_t HS;        // tileHist stride per block: radix tiles x MSD_BINS
-  const int32_t* act; // later rounds: the blocks that still have live suffixes, one grid row each (nullptr: row = block)
-};
-// A block whose suffixes are all final takes no part in the later rounds: their grids have one row per block that is still live
-// (a mixed batch used to carry the uniform / geometric blocks' empty workgroups through every round).
-__device__ __forceinline__ int bw_row_block(const BwtArrays& A, unsigned row) { return A.act ? A.act[row] : (int)row; }
 
 // ---------------------------------------------------------------------------------------------
 // round 0 keys: the first 7 bytes, zero padded at the end of the text.  A truncated suffix can therefore share a
@@ -141,9 +111,6 @@ __global__ __launch_bounds__(256) void k_radix_scan(BwtArrays A) {
 // LDS is sorted and applied by one workgroup (k_bucket_sort): one read of the pair instead of six LSD passes.
 // Buckets above BK_CAP elements (long runs: one old group of many thousand suffixes) are placed BEHIND the small ones,
 // in bucket order, and that window [d_w, d_m) goes through the LSD passes and k_seg_* as before.
-#define BK_BITS 12
-#define BK_CAP 6144            // 4096 slots + an overhang of 2048: 48 KiB of LDS, two workgroups per CU
-#define BK_BIG 0x80000000u
 __global__ __launch_bounds__(MSD_BINS) void k_msd_scan(BwtArrays A) {
   const int b = bw_row_block(A, blockIdx.x);
   const int m = A.d_m[b];
@@ -174,27 +141,6 @@ __global__ __launch_bounds__(MSD_BINS) void k_msd_scan(BwtArrays A) {
 #define RSC_WAVES 16                      // scatter workgroup: 16 waves x 16 rows of 64 keys = one radix tile
 #define RSC_ITEMS (RSORT_TILE / (64 * RSC_WAVES))
 #define RSC_WG (64 * RSC_WAVES)
-// lanes of the wave whose NBITS-bit digit equals this lane's (0 for a lane that is not valid).
-// Per digit bit: x = the lane's bit spread over a word (0 / ~0), bal = the lanes whose bit is set; the lanes that agree with this lane
-// in the bit are ~(bal ^ x).  Kept in 32-bit halves: the compiler then spends six VALU instructions per bit (shift, v_bfe_i32, v_cmp,
-// two v_xor and half a v_or3 over the differences) instead of the nine of `m &= bit ? bal : ~bal` on 64-bit masks; the ranking phase of
-// the LDS sorts is VALU bound (k_tr_sort 39.8 -> 36.8 ms, k_bucket_sort 16.9 -> 15.3 ms per 342 mixed blocks).  A hand-scheduled
-// four-instruction form (v_bfe_i32, v_cmp into an SGPR pair, two v_bitop3_b32 reading it) is correct but SLOWER (50.7 ms): an
-// instruction with an SGPR operand occupies the SIMD twice as long as a VGPR-only one (tools/ubench_valu_rate.hip) and a VALU read of an
-// SGPR that a VALU compare just wrote stalls the wave for about 16 cycles.
-template <int NBITS>
-__device__ __forceinline__ uint64_t bw_match(u32 d, bool valid) {
-  const uint64_t m0 = kz_ballot(valid);
-  u32 mlo = (u32)m0, mhi = (u32)(m0 >> 32);
-#pragma unroll
-  for (int b = 0; b < NBITS; b++) {
-    const u32 x = (u32)(((int32_t)(d << (31 - b))) >> 31);
-    const uint64_t bal = kz_ballot(x != 0u);
-    mlo &= ~((u32)bal ^ x);
-    mhi &= ~((u32)(bal >> 32) ^ x);
-  }
-  return valid ? (((uint64_t)mhi << 32) | mlo) : 0ULL;
-}
 template <int BINS, int NBITS, bool MSD, typename CNT, bool TEXT>
 __device__ __forceinline__ void radix_scatter_body(const u64* __restrict__ keyIn, const u32* __restrict__ valIn,
                                                    u64* __restrict__ keyOut, u32* __restrict__ valOut,
@@ -519,10 +465,6 @@ __global__ __launch_bounds__(KZ_WG) void k_seg_apply(const u64* __restrict__ key
 // k_seg_apply do for the sorted run.  An element is one u64: (group - bucket base : BK_BITS | r2 : bitsR | suffix : bitsG),
 // 58 bits for 4 MiB blocks.  Wave w owns the contiguous rows [w*R, (w+1)*R) of 64 elements; between passes the elements
 // live in registers, the LDS buffer is only the exchange (48 KiB + 16 KiB of u16 counters, 64 VGPRs: two workgroups per CU).
-#define BK_DBITS 9             // LDS sort digit: 36 key bits of a 4 MiB block in four passes
-#define BK_DBINS (1 << BK_DBITS)
-#define BK_SMALL 1024
-#define BK_SORT 0x40000000u
 static_assert(RSC_WG == MSD_BINS, "k_msd_scatter geometry");
 
 template <int WAVES, int ROWS>
@@ -553,6 +495,10 @@ __device__ __forceinline__ void bucket_body(const u64* __restrict__ keyS, const 
     k[r] = ~0ULL;
     if (r < R && idx < cnt) k[r] = ((keyS[off + bo + idx] - kbase) << bitsG) | (u64)valS[off + bo + idx];
   }
+  // The pass loop below and the one of tr_sort_body (kz_bwt_trie.hip) are the same LSD pass in two texts, and stay two: this one keeps
+  // a digit's per-wave counts in registers (c[][]) between the barriers, that one reads them from LDS twice because k_tr_sort /
+  // k_trk_sort have no registers left.  One shared loop was measured in both forms (profiles/bwt_fwd_refactor.txt): re-reading costs
+  // k_bucket_sort 2.5 %, keeping the counts costs the trie sorts 28 to 68 B more scratch per lane.  A change to one is due in the other.
   {
     if (threadIdx.x < 8) skip[threadIdx.x] = 0;
     const int keyBits = bitsR + BK_BITS;
@@ -638,6 +584,8 @@ __device__ __forceinline__ void bucket_body(const u64* __restrict__ keyS, const 
     }
     __syncthreads();
   }
+  // groups (NOT shared with tr_sort_body's, on purpose: here the rows' ballots stay in registers between the two loops, there they
+  // are computed twice -- k_tr_sort / k_trk_sort have no registers left for them: see the comment there)
   uint64_t hb[ROWS], sb[ROWS];
   u32 ms = 0, mh = 0;
   const int gsh = bitsG + bitsR;
@@ -701,8 +649,6 @@ __global__ __launch_bounds__(1024, 8) void k_bucket_sort(const u64* __restrict__
 // PARTITIONED by old group (LDS atomics on one counter per slot of the bucket: order inside a group is irrelevant), and
 // every element then walks the members of its group.  Groups are small where this is used (a handful of suffixes
 // sharing 7, 14, ... bytes); a bucket holding a group above BK_GMAX is left to k_bucket_sort (flag BK_SORT).
-#define BK_GMAX 256
-#define BK_SLOTS (1 << BK_BITS)
 template <int WAVES, int ROWS, int LO, int HI, typename CNT>
 __device__ __forceinline__ void bucket_count_body(const u64* __restrict__ keyS, const u32* __restrict__ valS, const BwtArrays& A, int bitsR, int bitsG, u32 gmax) {
   const int b = bw_row_block(A, blockIdx.y);
@@ -818,8 +764,6 @@ __global__ __launch_bounds__(1024) void k_bucket_count(const u64* __restrict__ k
   bucket_count_body<16, BK_CAP / 1024, BK_SMALL, BK_CAP, u32>(keyS, valS, A, bitsR, bitsG, gmax);
 }
 
-// (the trie rounds' per-block counters, defined further down; k_live_emit reads two of them)
-#define TR_META 32               // ints per block: [0] nodes, [1] buckets, [2 + L] first node of depth L, [10 + L] end, [18] error, [20] lazy ranks: live suffixes found
 // ---------------------------------------------------------------------------------------------
 // step 1 (text order): compact the LIVE suffixes and build their keys from sequential rank reads
 // The compact list need not be in text order (its only readers partition it by group: k_msd_* / the key trie round), so a tile
@@ -882,871 +826,6 @@ __global__ __launch_bounds__(KZ_WG) void k_live_emit(u64* __restrict__ keyN, u32
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Round 0 as a TRIE round: count first, move once.
-// The seven LSD passes of the old round 0 moved every suffix seven times (24 B per pass) to learn, for three of
-// the five data classes, that half of the suffixes sit in groups of many thousand equal 7-byte prefixes which no
-// amount of sorting can split.  Here the text is only COUNTED, level by level, until every prefix class is either
-// small enough to be finished in LDS or known to be one large group:
-//   node   = a prefix of d bytes shared by more than TR_CAP suffixes (depth-1 nodes = the 256 first bytes, always
-//            expanded); its 256 children are counted by the next byte (k_tr_hist16 for depth 1: LDS histogram of byte
-//            pairs; k_tr_count for the deeper levels: LDS counters of the level's nodes, one info lookup per suffix);
-//   k_tr_assign turns the counts of a level into child ranges of the suffix array (slots) and classifies each child:
-//            EXPANDED (count > TR_CAP and depth < Dmax: a node of the next level), TERMINAL (count > TR_CAP at depth
-//            Dmax: one group, nothing to sort), or SMALL: consecutive small siblings are merged greedily into buckets
-//            of at most TR_CAP suffixes (a bucket is a contiguous slot range);
-//   k_tr_scatter moves every suffix ONCE: terminal ones just get their group's head slot as rank (a coalesced store in
-//            text order, they are never moved at all); the others go to their bucket as one 8-byte element
-//            (the 64 - bitsG key bits that follow the bucket's common prefix | suffix index), staged per tile in LDS
-//            so that a bucket's elements leave in runs;
-//   k_tr_sort sorts one bucket in LDS (LSD radix over the bits that differ inside the bucket only), finds the groups
-//            of equal keys and writes ranks and final suffixes like k_seg_apply.
-// Depth: a bucket whose common prefix has d >= 1 bytes is sorted to d + (64 - bitsG) / 8 >= 6 bytes (zero padded at the
-// end of the text like the old keys), terminal groups share Dmax >= 6 bytes.  The ranks are therefore a refinement of
-// the 6-byte order and a coarsening of the suffix order, which is all the doubling rounds (h = 6, 12, ...) need: equal
-// rank => equal 6-byte prefix; different rank => the true order.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "the trie rounds are sized for gfx950's 160 KiB of LDS per workgroup (k_tr_hist16 128 KiB, k_tr_scatter / k_trk_scatter 152 KiB, the bucket sorts 77 KiB)"
-#endif
-#define TR_CAP 7680u             // LDS sort capacity (60 KiB of elements + 16 KiB of counters: two workgroups per CU)
-#define TR_MERGE (TR_CAP / 2)    // siblings above this are a bucket of their own
-#define TR_K_SMALL 1u
-#define TR_K_EXP 2u
-#define TR_K_TERM 3u
-#define TR_UNCHANGED (1u << 29)     // key rounds, terminal child: the new group keeps the old group's head slot (its members' ranks stay)
-#define TR_NODECHUNK 128         // nodes whose counters fit the LDS of k_tr_count
-struct TrieArrays {
-  u32* cnt;        // [B][MN][256] children counts
-  u32* info;       // [B][MN][256] kind << 30 | payload (SMALL: skip << 16 | bucket; EXP: node; TERM: head slot)
-  u32* nodeStart;  // [B][MN] first slot of the node's range
-  u32* bStart;     // [B][MB]
-  u32* bCount;     // [B][MB]
-  u32* bFill;      // [B][MB] elements placed so far (k_tr_scatter)
-  u32* bAux;       // [B][MB] key rounds: skip >= 3: slot of the bucket's first element (g + bStart - group start); skip < 3: the bucket's prefix bytes
-  u32* bG;         // [B][MB] key rounds, skip >= 3: the old group g all elements of the bucket belong to
-  u32* nodePfx;    // [B][MN] key rounds: the node's prefix bytes (depth < 3) or its old group g (depth >= 3)
-  u32* nodeGS;     // [B][MN] key rounds, depth >= 3: position of the old group's first element in the sorted window
-  int32_t* meta;   // [B][TR_META]
-  int32_t* err;    // [1] set when a table overflows (cannot happen for blocks the host admits: see tr_max_nodes / tr_max_buckets)
-  int MN, MB;
-};
-
-__device__ __forceinline__ u32 tr_byte(const u8* __restrict__ s, int i, int n) { return i < n ? (u32)s[i] : 0u; }
-
-// level 1: histogram of byte pairs (x[i], x[i+1]), x[n] = 0, one half of the 65536 bins per workgroup
-__global__ __launch_bounds__(1024) void k_tr_hist16(const u8* __restrict__ srcAll, int64_t stride, BwtArrays A, TrieArrays T) {
-  const int b = blockIdx.y;
-  const int n = A.d_n[b];
-  const u32 half = blockIdx.x;
-  __shared__ u32 hist[32768];
-  for (int i = threadIdx.x; i < 32768; i += 1024) hist[i] = 0;
-  __syncthreads();
-  const u8* s = srcAll + (int64_t)b * stride;
-  const int lane = kz_lane();
-  for (int base = 0; base < n; base += 1024 * 16) {
-    const int p = base + threadIdx.x * 16;
-    uint4 q = make_uint4(0, 0, 0, 0);
-    if (p < n) q = *(const uint4*)(s + p);                               // blocks are 256-byte aligned with >= 4 KiB of slack
-    u32 nxt = (u32)__shfl_down((int)(q.x & 0xFFu), 1, 64);
-    if (lane == 63) nxt = (p + 16 < n) ? (u32)s[p + 16] : 0u;
-    const u32 w[5] = {q.x, q.y, q.z, q.w, nxt};
-    u32 runKey = 0xFFFFFFFFu, runCnt = 0;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-      const int i = p + j;
-      const u32 c0 = (w[j >> 2] >> ((j & 3) * 8)) & 0xFFu;
-      const u32 c1r = (w[(j + 1) >> 2] >> (((j + 1) & 3) * 8)) & 0xFFu;
-      const u32 c1 = (i + 1 < n) ? c1r : 0u;
-      const u32 key = (c0 << 8) | c1;
-      const bool mine = i < n && (key >> 15) == half;
-      if (mine && key == runKey) runCnt++;
-      else {
-        if (runCnt) atomicAdd(&hist[runKey & 32767u], runCnt);
-        runKey = mine ? key : 0xFFFFFFFFu; runCnt = mine ? 1u : 0u;
-      }
-    }
-    if (runCnt) atomicAdd(&hist[runKey & 32767u], runCnt);
-  }
-  __syncthreads();
-  u32* out = T.cnt + (int64_t)b * T.MN * 256 + half * 32768;
-  for (int i = threadIdx.x; i < 32768; i += 1024) out[i] = hist[i];
-}
-
-// classify the children of the nodes of depth L (thread = node, its 256 children in order)
-__global__ __launch_bounds__(256) void k_tr_assign(BwtArrays A, TrieArrays T, int L, int Dmax, int keys) {
-  const int b = bw_row_block(A, blockIdx.x);
-  int32_t* meta = T.meta + (int64_t)b * TR_META;
-  __shared__ u32 sNodes, sBuckets, sErr;
-  __shared__ u32 scan[32];
-  const int lo = (L == 1) ? 0 : meta[2 + L], hi = (L == 1) ? 256 : meta[10 + L];
-  if (threadIdx.x == 0) { sNodes = (L == 1) ? 256u : (u32)meta[0]; sBuckets = (L == 1) ? 0u : (u32)meta[1]; sErr = 0; }
-  __syncthreads();
-  const u32 firstNew = sNodes;
-  u32* cnt = T.cnt + (int64_t)b * T.MN * 256;
-  u32* info = T.info + (int64_t)b * T.MN * 256;
-  u32* nodeStart = T.nodeStart + (int64_t)b * T.MN;
-  u32* bStart = T.bStart + (int64_t)b * T.MB;
-  u32* bCount = T.bCount + (int64_t)b * T.MB;
-  u32* bAux = T.bAux + (int64_t)b * T.MB;
-  u32* bG = T.bG + (int64_t)b * T.MB;
-  u32* nodePfx = T.nodePfx + (int64_t)b * T.MN;
-  u32* nodeGS = T.nodeGS + (int64_t)b * T.MN;
-  const u32 skipTag = (u32)L << 16;                                      // packed next to a bucket's count (k_tr_sort reads it)
-  for (int base = lo; base < hi; base += 256) {                          // uniform
-    const int node = base + threadIdx.x;
-    const bool valid = node < hi;
-    u32 start = 0;
-    if (L == 1) {                                                        // depth-1 nodes: their ranges from the byte totals
-      u32 tot = 0;
-      for (int c = 0; c < 256; c += 4) {
-        const uint4 v = *(const uint4*)(cnt + (int64_t)node * 256 + c);
-        tot += v.x + v.y + v.z + v.w;
-      }
-      u32 total;
-      start = kz_wg_excl_sum(tot, scan, &total);
-      nodeStart[node] = start;
-      if (keys) nodePfx[node] = (u32)node;
-    } else if (valid) start = nodeStart[node];
-    if (!valid) continue;
-    u32 run = start, curCnt = 0;
-    int curB = -1;
-    // key rounds (see k_trk_*): the first three key bytes are the old group g; a node of depth >= 3 knows g and where g's elements start
-    const u32 pfxN = keys ? nodePfx[node] : 0u;
-    const u32 gsN = (keys && L >= 3) ? nodeGS[node] : 0u;
-    const u32 auxSmall = !keys ? 0u : (L >= 3 ? pfxN - gsN : pfxN);      // skip >= 3: slot = aux + position; skip < 3: the prefix bytes
-    for (int c4 = 0; c4 < 256; c4 += 4) {
-      const uint4 v4 = *(const uint4*)(cnt + (int64_t)node * 256 + c4);
-      const u32 cc4[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const u32 cc = cc4[j];
-        if (cc == 0) continue;
-        const u32 s0 = run;
-        run += cc;
-        u32 e;
-        const u32 cbyte = (u32)(c4 + j);
-        if (cc > TR_CAP) {
-          if (curB >= 0) { bCount[curB] = curCnt | skipTag; curB = -1; }
-          if (L + 1 < Dmax) {
-            const u32 M = atomicAdd(&sNodes, 1u);
-            if (M < (u32)T.MN) {
-              nodeStart[M] = s0; e = (TR_K_EXP << 30) | M;
-              uint4* z = (uint4*)(cnt + (int64_t)M * 256);                // the new node's counters start at zero (no memset of the whole table)
-              for (int q = 0; q < 64; q++) z[q] = make_uint4(0, 0, 0, 0);
-              if (keys) { nodePfx[M] = (L < 3) ? ((pfxN << 8) | cbyte) : pfxN; nodeGS[M] = (L + 1 == 3) ? s0 : gsN; }
-            } else { sErr = 1; e = (TR_K_TERM << 30) | s0; }
-          } else if (keys) {                                              // all key bytes equal: one new group; its head slot = g + (s0 - group start)
-            const u32 head = pfxN + (s0 - gsN);
-            e = (TR_K_TERM << 30) | (s0 == gsN ? TR_UNCHANGED : 0u) | (head & 0xFFFFFFu);
-          } else e = (TR_K_TERM << 30) | s0;
-        } else if (cc > TR_MERGE) {
-          if (curB >= 0) { bCount[curB] = curCnt | skipTag; curB = -1; }
-          const u32 id = atomicAdd(&sBuckets, 1u);
-          if (id < (u32)T.MB) { bStart[id] = s0; bCount[id] = cc | skipTag; bAux[id] = (keys && L >= 3) ? auxSmall + s0 : auxSmall; bG[id] = pfxN; } else sErr = 1;
-          e = (TR_K_SMALL << 30) | ((u32)L << 16) | (id & 0xFFFFu);
-        } else {
-          if (curB >= 0 && curCnt + cc <= TR_CAP) curCnt += cc;
-          else {
-            if (curB >= 0) bCount[curB] = curCnt | skipTag;
-            const u32 id = atomicAdd(&sBuckets, 1u);
-            if (id < (u32)T.MB) { bStart[id] = s0; curB = (int)id; bAux[id] = (keys && L >= 3) ? auxSmall + s0 : auxSmall; bG[id] = pfxN; } else { sErr = 1; curB = -1; }
-            curCnt = cc;
-          }
-          e = (TR_K_SMALL << 30) | ((u32)L << 16) | ((u32)curB & 0xFFFFu);
-        }
-        info[(int64_t)node * 256 + c4 + j] = e;
-      }
-    }
-    if (curB >= 0) bCount[curB] = curCnt | skipTag;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    meta[0] = (int32_t)min(sNodes, (u32)T.MN); meta[1] = (int32_t)min(sBuckets, (u32)T.MB);
-    meta[2 + L + 1] = (int32_t)firstNew; meta[10 + L + 1] = (int32_t)min(sNodes, (u32)T.MN);
-    if (sErr) { meta[18] = 1; atomicOr(T.err, 1); }
-  }
-}
-
-// level L >= 2: every suffix that is still inside an expanded node of depth L-1 looks its child up; children that were
-// expanded (nodes of depth L) count the suffix's byte L in LDS.  state[i] = the suffix's leaf, or node | depth << 16.
-#define TRC_U 4                  // quads of suffixes a thread keeps in flight
-__global__ __launch_bounds__(1024) void k_tr_count(const u8* __restrict__ srcAll, int64_t stride, u32* __restrict__ stateAll, BwtArrays A, TrieArrays T, int L) {
-  const int b = blockIdx.y;
-  const int32_t* meta = T.meta + (int64_t)b * TR_META;
-  const int lo = meta[2 + L], hi = meta[10 + L];
-  if (hi <= lo) return;                                                  // no node of this depth: the states stay as they are
-  const int n = A.d_n[b];
-  __shared__ u32 lds[TR_NODECHUNK * 256];
-  const u8* s = srcAll + (int64_t)b * stride;
-  u32* state = stateAll + (int64_t)b * A.NS;
-  const u32* info = T.info + (int64_t)b * T.MN * 256;
-  u32* cnt = T.cnt + (int64_t)b * T.MN * 256;
-  const int P = gridDim.x;
-  const int per = (((n + P - 1) / P) + 1023) & ~1023;
-  const int pbeg = blockIdx.x * per, pend = min(n, pbeg + per);
-  for (int chunk = 0; lo + chunk * TR_NODECHUNK < hi; chunk++) {
-    for (int i = threadIdx.x; i < TR_NODECHUNK * 256; i += 1024) lds[i] = 0;
-    __syncthreads();
-    const int nlo = lo + chunk * TR_NODECHUNK;
-    // a thread takes four CONSECUTIVE suffixes: one 16-byte state access and one 8-byte text window serve all four, equal
-    // targets in a row (runs) are added once; two such quads per thread are in flight (the chain state -> info -> counter is latency)
-    for (int i0 = pbeg; i0 < pend; i0 += TRC_U * 4096) {
-      uint4 st4[TRC_U]; u64 win[TRC_U]; bool any[TRC_U];
-#pragma unroll
-      for (int u = 0; u < TRC_U; u++) {
-        const int i = i0 + u * 4096 + threadIdx.x * 4;
-        any[u] = i < pend;
-        st4[u] = make_uint4(0xC0000000u, 0xC0000000u, 0xC0000000u, 0xC0000000u);
-        win[u] = 0;
-        if (any[u]) {
-          if (!(L == 2 && chunk == 0)) st4[u] = *(const uint4*)(state + i);
-          const int at = i + L - 2;                                        // bytes at .. at + 5: previous byte, child byte, counted byte of the four
-          u64 k = __builtin_bswap64(*(const bw_u64_unaligned*)(s + at));
-          const int rem = n - at;
-          if (rem < 8) k = rem <= 0 ? 0ULL : (k & (~0ULL << (8 * (8 - rem))));
-          win[u] = k;
-        }
-      }
-      // the info lookups of ALL the quads are issued before any of them is used: one workgroup per CU (128 KiB of counters)
-      // hides the chain state -> info -> counter only by what a thread keeps in flight
-      u32 stqA[TRC_U][4]; u32 eA[TRC_U][4]; bool lookA[TRC_U][4];
-#pragma unroll
-      for (int u = 0; u < TRC_U; u++) {
-        const int i = i0 + u * 4096 + threadIdx.x * 4;
-        stqA[u][0] = st4[u].x; stqA[u][1] = st4[u].y; stqA[u][2] = st4[u].z; stqA[u][3] = st4[u].w;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          if (L == 2 && chunk == 0) stqA[u][q] = (any[u] && i + q < pend) ? ((1u << 16) | (u32)((win[u] >> (56 - 8 * q)) & 0xFFu)) : 0xC0000000u;
-          lookA[u][q] = any[u] && (i + q < pend) && (stqA[u][q] >> 30) == 0 && ((stqA[u][q] >> 16) & 7u) != (u32)L;
-          eA[u][q] = 0;
-          if (lookA[u][q]) eA[u][q] = info[(stqA[u][q] & 0xFFFFu) * 256 + (u32)((win[u] >> (48 - 8 * q)) & 0xFFu)];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < TRC_U; u++) {
-        if (!any[u]) continue;
-        const int i = i0 + u * 4096 + threadIdx.x * 4;
-        u32 (&stq)[4] = stqA[u];
-        u32 (&e)[4] = eA[u]; bool (&look)[4] = lookA[u];
-        bool changed = false;
-        u32 runT = 0xFFFFFFFFu, runC = 0;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          u32 tgt = 0xFFFFFFFFu;
-          if ((i + q < pend) && (stq[q] >> 30) == 0) {
-            if (look[q]) {
-              stq[q] = ((e[q] >> 30) == TR_K_EXP) ? ((e[q] & 0xFFFFu) | ((u32)L << 16)) : e[q];
-              changed = true;
-            }
-            if ((stq[q] >> 30) == 0) {                                       // inside a node of depth L now
-              const int k = (int)(stq[q] & 0xFFFFu) - nlo;
-              if (k >= 0 && k < TR_NODECHUNK) tgt = (u32)k * 256 + (u32)((win[u] >> (40 - 8 * q)) & 0xFFu);
-            }
-          }
-          if (tgt == runT) runC++;
-          else {
-            if (runC && runT != 0xFFFFFFFFu) atomicAdd(&lds[runT], runC);
-            runT = tgt; runC = 1;
-          }
-        }
-        if (runC && runT != 0xFFFFFFFFu) atomicAdd(&lds[runT], runC);
-        if (changed) *(uint4*)(state + i) = make_uint4(stq[0], stq[1], stq[2], stq[3]);
-      }
-    }
-    __syncthreads();
-    for (int j = threadIdx.x; j < TR_NODECHUNK * 256; j += 1024) {
-      const u32 v = lds[j];
-      if (v && nlo + (j >> 8) < hi) atomicAdd(&cnt[(int64_t)(nlo + (j >> 8)) * 256 + (j & 255)], v);
-    }
-    __syncthreads();
-  }
-}
-
-// move every suffix once (see above).  Tile = 8192 suffixes in text order.  The tile's count per bucket lives in
-// 16-bit halves of LDS words (a tile holds at most 8192 suffixes), so that TR_MAXB buckets fit next to the staging buffer.
-#define TRS_TILE 8192
-#define TRS_ITEMS (TRS_TILE / 1024)
-#define TR_MAXB 12288
-// Two sizes of the same kernel (round 5): blocks with at most TRS_FASTB buckets (every block measured: 456 .. 790) take tiles of 4096
-// suffixes with 52 KiB of LDS -- three workgroups per CU to hide the state -> info -> text chain -- the others the full tables
-// (152 KiB, one workgroup per CU).  Both are launched; a block's workgroups of the form that is not its own return at once.
-#define TRS_FASTB 2048
-template <int TILE_, int MAXB_, bool FAST>
-__device__ __forceinline__ void tr_scatter_body(const u8* __restrict__ srcAll, int64_t stride, const u32* __restrict__ stateAll,
-                                                u64* __restrict__ elemAll, const BwtArrays& A, const TrieArrays& T, int bitsG) {
-  constexpr int ITEMS_ = TILE_ / 1024;
-  if ((T.meta[(int64_t)blockIdx.y * TR_META + 1] <= TRS_FASTB) != FAST) return;
-  const int b = blockIdx.y;
-  const int n = A.d_n[b];
-  const int tile = blockIdx.x;
-  const int tbase = tile * TILE_;
-  if (tbase >= n) return;
-  __shared__ u32 tc2[MAXB_ / 2];                                       // two 16-bit counters per word
-  __shared__ u32 gdelta[MAXB_];
-  __shared__ u64 stage[TILE_];
-  __shared__ uint16_t stageB[TILE_];
-  __shared__ u32 scan[32];
-  const int32_t* meta = T.meta + (int64_t)b * TR_META;
-  const int nB = meta[1];
-  const bool hasState = meta[10 + 2] > meta[2 + 2];                      // a level-2 count pass wrote the states
-  for (int i = threadIdx.x; i < (nB + 1) / 2; i += 1024) tc2[i] = 0;
-  __syncthreads();
-  const u8* s = srcAll + (int64_t)b * stride;
-  const u32* state = stateAll + (int64_t)b * A.NS;
-  const u32* info = T.info + (int64_t)b * T.MN * 256;
-  u32* rank = A.rank + (int64_t)b * A.NS;
-  const u64 lowMask = (1ULL << bitsG) - 1ULL;
-  u64 el[ITEMS_]; u32 bp[ITEMS_];                                  // element, bucket | position in (tile, bucket) << 16
-  // three rounds of loads for the tile's eight items per thread, each round issued for all items before its results are used
-  // (state -> info -> text is a dependent chain; one item after the other was 24 memory round trips per thread, the kernel's time)
-  u32 stv[ITEMS_];
-#pragma unroll
-  for (int r = 0; r < ITEMS_; r++) {
-    const int i = tbase + r * 1024 + threadIdx.x;
-    stv[r] = 0xC0000000u;
-    if (i < n) stv[r] = hasState ? state[i] : ((u32)s[i] | (1u << 16));
-  }
-  u32 cb[ITEMS_];
-#pragma unroll
-  for (int r = 0; r < ITEMS_; r++) {
-    const int i = tbase + r * 1024 + threadIdx.x;
-    cb[r] = 0;
-    if (i < n && (stv[r] >> 30) == 0) cb[r] = tr_byte(s, i + (int)((stv[r] >> 16) & 7u), n);
-  }
-#pragma unroll
-  for (int r = 0; r < ITEMS_; r++) {
-    const int i = tbase + r * 1024 + threadIdx.x;
-    if (i < n && (stv[r] >> 30) == 0) stv[r] = info[(stv[r] & 0xFFFFu) * 256 + cb[r]];
-  }
-  u64 kv[ITEMS_];
-#pragma unroll
-  for (int r = 0; r < ITEMS_; r++) {
-    const int i = tbase + r * 1024 + threadIdx.x;
-    kv[r] = 0;
-    if (i < n && (stv[r] >> 30) != TR_K_TERM) {
-      const int at = i + (int)((stv[r] >> 16) & 7u);
-      u64 k = __builtin_bswap64(*(const bw_u64_unaligned*)(s + at));
-      const int rem = n - at;
-      if (rem < 8) k = rem <= 0 ? 0ULL : (k & (~0ULL << (8 * (8 - rem))));
-      kv[r] = k;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < ITEMS_; r++) {
-    const int i = tbase + r * 1024 + threadIdx.x;
-    bp[r] = 0xFFFFFFFFu;
-    el[r] = 0;
-    if (i < n) {
-      const u32 st = stv[r];
-      if ((st >> 30) == TR_K_TERM) rank[i] = (st & 0xFFFFFFu) | BW_LIVE;
-      else {
-        const u32 bk = st & 0xFFFFu;
-        el[r] = (kv[r] & ~lowMask) | (u64)(u32)i;
-        const u32 old = atomicAdd(&tc2[bk >> 1], (bk & 1u) ? 65536u : 1u);
-        const u32 pos = (bk & 1u) ? (old >> 16) : (old & 0xFFFFu);
-        bp[r] = bk | (pos << 16);
-      }
-    }
-  }
-  __syncthreads();
-  // exclusive scan of the tile's bucket counts (a thread owns whole words); buckets present reserve their run in the bucket's slot range
-  {
-    const int per = 2 * ((nB + 2047) / 2048);
-    const int j0 = threadIdx.x * per;
-    u32 mine = 0;
-    for (int j = j0; j < j0 + per && j < nB; j += 2) { const u32 w = tc2[j >> 1]; mine += (w & 0xFFFFu) + (w >> 16); }
-    u32 total;
-    u32 run = kz_wg_excl_sum(mine, scan, &total);
-    const u32* bStart = T.bStart + (int64_t)b * T.MB;
-    u32* bFill = T.bFill + (int64_t)b * T.MB;
-    for (int j = j0; j < j0 + per && j < nB; j += 2) {
-      const u32 w = tc2[j >> 1];
-      const u32 c0 = w & 0xFFFFu, c1 = w >> 16;
-      if (c0) gdelta[j] = bStart[j] + atomicAdd(&bFill[j], c0) - run;
-      const u32 r1 = run + c0;
-      if (c1) gdelta[j + 1] = bStart[j + 1] + atomicAdd(&bFill[j + 1], c1) - r1;
-      tc2[j >> 1] = run | (r1 << 16);                                    // tile-local start of both buckets (< 8192 unless the bucket is empty)
-      run = r1 + c1;
-    }
-    if (threadIdx.x == 0) scan[31] = total;
-  }
-  __syncthreads();
-  const u32 total = scan[31];
-#pragma unroll
-  for (int r = 0; r < ITEMS_; r++) {
-    if (bp[r] != 0xFFFFFFFFu) {
-      const u32 bk = bp[r] & 0xFFFFu;
-      const u32 w = tc2[bk >> 1];
-      const u32 slot = ((bk & 1u) ? (w >> 16) : (w & 0xFFFFu)) + (bp[r] >> 16);
-      stage[slot] = el[r]; stageB[slot] = (uint16_t)bk;
-    }
-  }
-  __syncthreads();
-  u64* elem = elemAll + (int64_t)b * A.NS;
-#pragma unroll
-  for (int r = 0; r < ITEMS_; r++) {
-    const u32 slot = (u32)r * 1024 + threadIdx.x;
-    if (slot < total) elem[gdelta[stageB[slot]] + slot] = stage[slot];
-  }
-}
-
-__global__ __launch_bounds__(1024) void k_tr_scatter(const u8* __restrict__ srcAll, int64_t stride, const u32* __restrict__ stateAll,
-                                                      u64* __restrict__ elemAll, BwtArrays A, TrieArrays T, int bitsG) { tr_scatter_body<TRS_TILE, TR_MAXB, false>(srcAll, stride, stateAll, elemAll, A, T, bitsG); }
-__global__ __launch_bounds__(1024) void k_tr_scatter_f(const u8* __restrict__ srcAll, int64_t stride, const u32* __restrict__ stateAll,
-                                                        u64* __restrict__ elemAll, BwtArrays A, TrieArrays T, int bitsG) { tr_scatter_body<TRS_TILE / 2, TRS_FASTB, true>(srcAll, stride, stateAll, elemAll, A, T, bitsG); }
-
-// round 0: a block whose trie has only the 256 depth-1 nodes (see the lazy ranks of k_tr_sort)
-__device__ __forceinline__ bool tr_lazy_candidate(const int32_t* meta) { return meta[0] == 256 && meta[18] == 0; }
-// one bucket at a time in LDS: sort by the key bits that differ, groups of equal keys, ranks and final suffixes
-#define TRQ_WAVES 16
-#define TRQ_ROWS 8
-template <bool KEYS>
-__device__ __forceinline__ void tr_sort_body(const u64* __restrict__ elemAll, const BwtArrays& A, const TrieArrays& T, int bitsG, int lazyMode) {
-  const int b = bw_row_block(A, blockIdx.y);
-  const int nB = T.meta[(int64_t)b * TR_META + 1];
-  // LAZY RANKS (round 0 only).  A block without a single expanded node (no 2-byte prefix above TR_CAP suffixes: high-entropy data)
-  // almost always leaves round 0 with every suffix final, and then nobody reads its ranks except k_bwt_emit (the 8 primary indexes):
-  // the scattered 4-byte rank stores are a quarter of this kernel's time on such blocks.  Pass 1 (lazyMode 1) sorts such a block,
-  // writes its final suffixes and the 8 ranks k_bwt_emit reads, and COUNTS the live suffixes in meta[20]; pass 2 (lazyMode 2) runs the
-  // blocks whose count is not zero again, storing every rank (the elements are untouched by pass 1; the sa stores repeat).
-  // k_live_emit skips the blocks pass 1 finished.
-  const bool lazyCand = !KEYS && lazyMode != 0 && tr_lazy_candidate(T.meta + (int64_t)b * TR_META);
-  if (!KEYS && lazyMode == 2 && !(lazyCand && T.meta[(int64_t)b * TR_META + 20] > 0)) return;
-  const bool lazy = lazyCand && lazyMode == 1;
-  u32 pstep = 0;
-  if (lazy) { const int n = A.d_n[b]; const int st = n >> 3; pstep = (u32)((st * 8 != n) ? st + 1 : st); }   // k_bwt_emit: primary index k = rank[k * step]
-  u32 liveMine = 0;
-  __shared__ u64 buf[TR_CAP];
-  __shared__ uint16_t cw[TRQ_WAVES][BK_DBINS];
-  __shared__ u32 wsum[BK_DBINS / 64];
-  __shared__ u32 wH[TRQ_WAVES], wS[TRQ_WAVES];
-  __shared__ u64 redO[TRQ_WAVES], redA[TRQ_WAVES];
-  __shared__ int skip[8];
-  const int wave = threadIdx.x >> 6, lane = kz_lane();
-  const int64_t off = (int64_t)b * A.NS;
-  const u64* elem = elemAll + off;
-  u32* rank = A.rank + off;
-  u32* sa = A.sa + off;
-  const uint64_t lt = kz_lanemask_lt();
-  const uint64_t le = lt | (1ULL << lane);
-  const u64 vmask = (1ULL << bitsG) - 1ULL;
-  for (int d = blockIdx.x; d < nB; d += gridDim.x) {
-    const u32 bcs = T.bCount[(int64_t)b * T.MB + d];
-    const int cnt = (int)(bcs & 0xFFFFu);
-    const int skipB = (int)(bcs >> 16);                                  // bytes of common prefix in front of the bucket's key fragment
-    const u32 bo = T.bStart[(int64_t)b * T.MB + d];
-    const u32 aux = KEYS ? T.bAux[(int64_t)b * T.MB + d] : 0u;
-    const u32 gOne = KEYS ? T.bG[(int64_t)b * T.MB + d] : 0u;
-    const int rows = (cnt + 63) >> 6;
-    const int R = (rows + TRQ_WAVES - 1) / TRQ_WAVES;                    // rows per wave, 1..TRQ_ROWS (uniform)
-    const int base = wave * R * 64;
-    u64 k[TRQ_ROWS]; u32 dr[TRQ_ROWS];
-    u64 vo = 0, va = ~0ULL;
-#pragma unroll
-    for (int r = 0; r < TRQ_ROWS; r++) {
-      const int idx = base + r * 64 + lane;
-      k[r] = ~0ULL;
-      if (r < R && idx < cnt) { k[r] = elem[bo + idx]; vo |= k[r]; va &= k[r]; }
-    }
-    for (int dd = 32; dd > 0; dd >>= 1) { vo |= __shfl_xor(vo, dd, 64); va &= __shfl_xor(va, dd, 64); }
-    if (threadIdx.x < 8) skip[threadIdx.x] = 0;
-    if (lane == 0) { redO[wave] = vo; redA[wave] = va; }
-    __syncthreads();
-    vo = 0; va = ~0ULL;
-#pragma unroll
-    for (int w = 0; w < TRQ_WAVES; w++) { vo |= redO[w]; va &= redA[w]; }
-    const u64 diff = (vo ^ va) >> bitsG;                                 // key bits that differ inside the bucket
-    int passes = 0, lowBit = 0;
-    if (diff) {
-      lowBit = (int)__builtin_ctzll(diff);
-      const int hiBit = 63 - (int)__builtin_clzll(diff);
-      passes = (hiBit - lowBit + BK_DBITS) / BK_DBITS;
-    }
-    for (int p = 0; p < passes; p++) {
-      const int shift = bitsG + lowBit + BK_DBITS * p;
-      for (int i = threadIdx.x; i < TRQ_WAVES * BK_DBINS / 2; i += TRQ_WAVES * 64) ((u32*)&cw[0][0])[i] = 0;
-      __syncthreads();
-#pragma unroll
-      for (int r = 0; r < TRQ_ROWS; r++) {
-        if (r < R) {
-          const int idx = base + r * 64 + lane;
-          const bool valid = idx < cnt;
-          const u32 dg = (u32)(k[r] >> shift) & (BK_DBINS - 1);
-          const uint64_t vm = kz_ballot(valid);
-          if (vm == 0) continue;
-          const u32 d0 = (u32)__builtin_amdgcn_readfirstlane((int)dg);
-          const bool uni = kz_ballot(valid && dg == d0) == vm;
-          const uint64_t peers = uni ? (valid ? vm : 0ULL) : bw_match<BK_DBITS>(dg, valid);
-          u32 pre = 0;
-          if (valid) pre = cw[wave][dg];
-          const u32 rnk = pre + (u32)__popcll(peers & lt);
-          if (valid && (peers >> lane) == 1ULL) cw[wave][dg] = (uint16_t)(pre + (u32)__popcll(peers));
-          dr[r] = dg | (rnk << 16);
-        }
-      }
-      __syncthreads();
-      static_assert(BK_DBINS <= TRQ_WAVES * 64, "one digit per thread");
-      u32 mine = 0;                                                      // thread = digit (the threads behind carry zero)
-      if (threadIdx.x < BK_DBINS) {
-#pragma unroll
-        for (int w = 0; w < TRQ_WAVES; w++) mine += cw[w][threadIdx.x];
-        if (mine == (u32)cnt) skip[p] = 1;
-      }
-      const u32 inc = kz_wave_incl_sum(mine);
-      if (lane == 63 && wave < BK_DBINS / 64) wsum[wave] = inc;
-      __syncthreads();
-      if (skip[p]) continue;                                             // uniform: one digit value for the whole bucket, nothing moves
-      if (threadIdx.x < BK_DBINS) {
-        u32 run = inc - mine;
-        for (int w = 0; w < wave; w++) run += wsum[w];
-#pragma unroll
-        for (int w = 0; w < TRQ_WAVES; w++) { const u32 cv = cw[w][threadIdx.x]; cw[w][threadIdx.x] = (uint16_t)run; run += cv; }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int r = 0; r < TRQ_ROWS; r++) {
-        if (r < R) {
-          const int idx = base + r * 64 + lane;
-          if (idx < cnt) buf[cw[wave][dr[r] & 0xFFFF] + (dr[r] >> 16)] = k[r];
-        }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int r = 0; r < TRQ_ROWS; r++) {
-        if (r < R) {
-          const int idx = base + r * 64 + lane;
-          if (idx < cnt) k[r] = buf[idx];
-        }
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int r = 0; r < TRQ_ROWS; r++) {
-      if (r < R) {
-        const int idx = base + r * 64 + lane;
-        if (idx < cnt) buf[idx] = k[r];
-      }
-    }
-    __syncthreads();
-    // groups of equal keys; key rounds with skip < 3 also need the OLD groups (the first 3 - skip key bytes): an element's slot
-    // is g + its index inside its old group, a new group's rank g + the index of its first element inside the old group
-    const bool segs = KEYS && skipB < 3;
-    const int gsh = 64 - 8 * (3 - skipB);                                 // element >> gsh = the bytes of g the fragment holds
-    u32 mh = 0, ms = 0;
-#pragma unroll
-    for (int r = 0; r < TRQ_ROWS; r++) {
-      if (r < R) {
-        const int idx = base + r * 64 + lane;
-        const bool valid = idx < cnt;
-        const u64 prev = (valid && idx > 0) ? buf[idx - 1] : 0;
-        const bool head = valid && (idx == 0 || (k[r] >> bitsG) != (prev >> bitsG));
-        const uint64_t hbr = kz_ballot(head);
-        if (hbr) mh = (u32)(base + r * 64 + 63 - (int)__builtin_clzll(hbr)) + 1;
-        if (segs) {
-          const uint64_t sbr = kz_ballot(head && (idx == 0 || (k[r] >> gsh) != (prev >> gsh)));
-          if (sbr) ms = (u32)(base + r * 64 + 63 - (int)__builtin_clzll(sbr)) + 1;
-        }
-      }
-    }
-    if (lane == 0) { wH[wave] = mh; wS[wave] = ms; }
-    __syncthreads();
-    u32 carH = 0, carS = 0;
-    for (int w = 0; w < wave; w++) { carH = max(carH, wH[w]); carS = max(carS, wS[w]); }
-#pragma unroll
-    for (int r = 0; r < TRQ_ROWS; r++) {
-      if (r < R) {
-        const int rowBase = base + r * 64;
-        const int idx = rowBase + lane;
-        const bool valid = idx < cnt;
-        const u64 prev = (valid && idx > 0) ? buf[idx - 1] : 0;
-        const bool head = valid && (idx == 0 || (k[r] >> bitsG) != (prev >> bitsG));
-        const uint64_t hbr = kz_ballot(head);
-        const uint64_t hbl = hbr & le;
-        const u32 hh = hbl ? (u32)(rowBase + 63 - (int)__builtin_clzll(hbl)) : carH - 1;
-        uint64_t sbr = 0;
-        u32 ss = 0;
-        if (segs) {
-          sbr = kz_ballot(head && (idx == 0 || (k[r] >> gsh) != (prev >> gsh)));
-          const uint64_t sbl = sbr & le;
-          ss = sbl ? (u32)(rowBase + 63 - (int)__builtin_clzll(sbl)) : carS - 1;
-        }
-        if (valid) {
-          const u64 nextk = (idx + 1 < cnt) ? buf[idx + 1] : 0;
-          const bool headN = (idx + 1 >= cnt) || ((nextk >> bitsG) != (k[r] >> bitsG));
-          const bool live = !(hh == (u32)idx && headN);
-          const u32 sv = (u32)(k[r] & vmask);
-          if (!KEYS) {
-            if (!lazy) rank[sv] = (bo + hh) | (live ? BW_LIVE : 0u);
-            else {
-              const u32 q = sv / pstep;
-              if (q * pstep == sv && q < 8u) rank[sv] = (bo + hh) | (live ? BW_LIVE : 0u);
-              liveMine += live ? 1u : 0u;
-            }
-            if (!live) sa[bo + (u32)idx] = sv;
-          } else {
-            u32 g, headSlot, slot;
-            if (segs) {
-              g = (aux << (8 * (3 - skipB))) | (u32)(k[r] >> gsh);
-              headSlot = g + (hh - ss); slot = g + ((u32)idx - ss);
-            } else { g = gOne; headSlot = aux + hh; slot = aux + (u32)idx; }
-            // the first new group of an old group keeps the old head slot: while it stays LIVE its members' ranks do not change
-            if (!(live && headSlot == g)) rank[sv] = headSlot | (live ? BW_LIVE : 0u);
-            if (!live) sa[slot] = sv;
-          }
-        }
-        if (hbr) carH = (u32)(rowBase + 63 - (int)__builtin_clzll(hbr)) + 1;
-        if (sbr) carS = (u32)(rowBase + 63 - (int)__builtin_clzll(sbr)) + 1;
-      }
-    }
-    __syncthreads();
-  }
-  if (!KEYS && lazy) {
-    if (kz_ballot(liveMine != 0) != 0) {
-      for (int dd = 32; dd > 0; dd >>= 1) liveMine += __shfl_xor(liveMine, dd, 64);
-      if (lane == 0) atomicAdd(&T.meta[(int64_t)b * TR_META + 20], (int32_t)liveMine);
-    }
-  }
-}
-// (two workgroups per CU at 64 VGPRs with 16 registers spilled beat one workgroup without spills: 45 vs 50 ms per 357 uniform blocks)
-__global__ __launch_bounds__(1024, 8) void k_tr_sort(const u64* __restrict__ elemAll, BwtArrays A, TrieArrays T, int bitsG, int lazyMode) { tr_sort_body<false>(elemAll, A, T, bitsG, lazyMode); }
-__global__ __launch_bounds__(1024, 8) void k_trk_sort(const u64* __restrict__ elemAll, BwtArrays A, TrieArrays T, int bitsG) { tr_sort_body<true>(elemAll, A, T, bitsG, 0); }
-
-// ---------------------------------------------------------------------------------------------
-// KEY rounds: the same trie round over the WINDOW of a doubling round -- the compact pairs (old group g << bitsR | secondary key r2,
-// suffix) of the buckets too large for the LDS kernels (groups of many thousand suffixes: six full LSD passes over HBM and the
-// k_seg_* kernels until round 3).  The digits are the six bytes of K48 = g : 24 | r2 : 24; the first three bytes are the old
-// group, so a child of depth 3 IS an old group and its start in the sorted window is where the group's elements begin: an
-// element at sorted position pos of group g takes slot g + (pos - group start).  A child that is still large after all six
-// bytes holds equal keys only: one new group, no sorting (terminal).  Buckets of merged small siblings above depth 3 hold whole
-// old groups (k_trk_sort finds their boundaries in the sorted fragment), buckets below depth 3 lie inside one group.
-struct KeySrc { const u64* key; const u32* val; int bitsR; };
-__device__ __forceinline__ u64 trk_k48(u64 key, int bitsR) { return ((key >> bitsR) << 24) | (key & ((1ULL << bitsR) - 1ULL)); }
-
-__global__ __launch_bounds__(1024) void k_trk_hist16(KeySrc X, BwtArrays A, TrieArrays T) {
-  const int b = bw_row_block(A, blockIdx.y);
-  const int w0 = A.d_w[b];
-  const int W = max(0, A.d_m[b] - w0);                                  // an empty window still writes its (zero) counts: k_tr_assign reads them
-  const u32 half = blockIdx.x;
-  __shared__ u32 hist[32768];
-  for (int i = threadIdx.x; i < 32768; i += 1024) hist[i] = 0;
-  __syncthreads();
-  const u64* key = X.key + (int64_t)b * A.NS + w0;
-  const int lane = kz_lane();
-  for (int j0 = 0; j0 < W; j0 += 1024) {
-    const int j = j0 + threadIdx.x;
-    u32 tgt = 0xFFFFFFFFu;
-    if (j < W) {
-      const u32 pair = (u32)(trk_k48(key[j], X.bitsR) >> 32);
-      if ((pair >> 15) == half) tgt = pair & 32767u;
-    }
-    const uint64_t am = kz_ballot(tgt != 0xFFFFFFFFu);                   // the window is grouped by bucket: most rows hit one counter
-    if (am) {
-      const int l0 = (int)__builtin_ctzll(am);
-      const u32 t0 = (u32)__shfl((int)tgt, l0, 64);
-      const uint64_t same = kz_ballot(tgt == t0);
-      if (lane == l0) atomicAdd(&hist[t0], (u32)__popcll(same));
-      else if (tgt != 0xFFFFFFFFu && tgt != t0) atomicAdd(&hist[tgt], 1u);
-    }
-  }
-  __syncthreads();
-  u32* out = T.cnt + (int64_t)b * T.MN * 256 + half * 32768;
-  for (int i = threadIdx.x; i < 32768; i += 1024) out[i] = hist[i];
-}
-
-__global__ __launch_bounds__(1024) void k_trk_count(KeySrc X, u32* __restrict__ stateAll, BwtArrays A, TrieArrays T, int L) {
-  const int b = bw_row_block(A, blockIdx.y);
-  const int32_t* meta = T.meta + (int64_t)b * TR_META;
-  const int lo = meta[2 + L], hi = meta[10 + L];
-  if (hi <= lo) return;
-  const int w0 = A.d_w[b];
-  const int W = A.d_m[b] - w0;
-  __shared__ u32 lds[TR_NODECHUNK * 256];
-  const u64* key = X.key + (int64_t)b * A.NS + w0;
-  u32* state = stateAll + (int64_t)b * A.NS;
-  const u32* info = T.info + (int64_t)b * T.MN * 256;
-  u32* cnt = T.cnt + (int64_t)b * T.MN * 256;
-  const int P = gridDim.x;
-  const int per = (((W + P - 1) / P) + 1023) & ~1023;
-  const int pbeg = blockIdx.x * per, pend = min(W, pbeg + per);
-  for (int chunk = 0; lo + chunk * TR_NODECHUNK < hi; chunk++) {
-    for (int i = threadIdx.x; i < TR_NODECHUNK * 256; i += 1024) lds[i] = 0;
-    __syncthreads();
-    const int nlo = lo + chunk * TR_NODECHUNK;
-    // a thread takes four CONSECUTIVE items (two 16-byte key loads, one 16-byte state access); equal targets in a row are added once;
-    // TRC_U such quads are in flight per thread: all their loads, then all their info lookups, then the counters
-    for (int i0 = pbeg; i0 < pend; i0 += TRC_U * 4096) {
-      u64 kq[TRC_U][4]; u32 stq[TRC_U][4]; bool act[TRC_U];
-#pragma unroll
-      for (int u = 0; u < TRC_U; u++) {
-        const int i = i0 + u * 4096 + (int)threadIdx.x * 4;
-        act[u] = i < pend;
-#pragma unroll
-        for (int q = 0; q < 4; q++) { stq[u][q] = 0xC0000000u; kq[u][q] = 0; }
-        if (!act[u]) continue;
-        if (!(L == 2 && chunk == 0)) {                                     // settled items (most of a late level's window) cost one state read
-          const uint4 sv = *(const uint4*)(state + i);
-          stq[u][0] = sv.x; stq[u][1] = sv.y; stq[u][2] = sv.z; stq[u][3] = sv.w;
-          if ((stq[u][0] >> 30) && (stq[u][1] >> 30) && (stq[u][2] >> 30) && (stq[u][3] >> 30)) { act[u] = false; continue; }
-        }
-        if (i + 4 <= pend && ((((uintptr_t)(key + i)) & 15) == 0)) {
-          const uint4 a = *(const uint4*)(key + i), c = *(const uint4*)(key + i + 2);
-          kq[u][0] = ((u64)a.y << 32) | a.x; kq[u][1] = ((u64)a.w << 32) | a.z; kq[u][2] = ((u64)c.y << 32) | c.x; kq[u][3] = ((u64)c.w << 32) | c.z;
-        } else {
-#pragma unroll
-          for (int q = 0; q < 4; q++) kq[u][q] = (i + q < pend) ? key[i + q] : 0ULL;
-        }
-      }
-      u32 e[TRC_U][4]; bool look[TRC_U][4]; u64 k48[TRC_U][4];
-#pragma unroll
-      for (int u = 0; u < TRC_U; u++) {
-        const int i = i0 + u * 4096 + (int)threadIdx.x * 4;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          k48[u][q] = trk_k48(kq[u][q], X.bitsR);
-          if (L == 2 && chunk == 0) stq[u][q] = (act[u] && i + q < pend) ? ((1u << 16) | (u32)(k48[u][q] >> 40)) : 0xC0000000u;
-          look[u][q] = act[u] && (i + q < pend) && (stq[u][q] >> 30) == 0 && ((stq[u][q] >> 16) & 7u) != (u32)L;
-          e[u][q] = 0;
-          if (look[u][q]) e[u][q] = info[(stq[u][q] & 0xFFFFu) * 256 + (u32)((k48[u][q] >> (40 - 8 * (L - 1))) & 0xFFu)];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < TRC_U; u++) {
-        if (!act[u]) continue;
-        const int i = i0 + u * 4096 + (int)threadIdx.x * 4;
-        bool changed = false;
-        u32 runT = 0xFFFFFFFFu, runC = 0;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          u32 tgt = 0xFFFFFFFFu;
-          if ((i + q < pend) && (stq[u][q] >> 30) == 0) {
-            if (look[u][q]) { stq[u][q] = ((e[u][q] >> 30) == TR_K_EXP) ? ((e[u][q] & 0xFFFFu) | ((u32)L << 16)) : e[u][q]; changed = true; }
-            if ((stq[u][q] >> 30) == 0) {
-              const int k = (int)(stq[u][q] & 0xFFFFu) - nlo;
-              if (k >= 0 && k < TR_NODECHUNK) tgt = (u32)k * 256 + (u32)((k48[u][q] >> (40 - 8 * L)) & 0xFFu);
-            }
-          }
-          if (tgt == runT) runC++;
-          else { if (runC && runT != 0xFFFFFFFFu) atomicAdd(&lds[runT], runC); runT = tgt; runC = 1; }
-        }
-        if (runC && runT != 0xFFFFFFFFu) atomicAdd(&lds[runT], runC);
-        if (changed) *(uint4*)(state + i) = make_uint4(stq[u][0], stq[u][1], stq[u][2], stq[u][3]);
-      }
-    }
-    __syncthreads();
-    for (int j = threadIdx.x; j < TR_NODECHUNK * 256; j += 1024) {
-      const u32 v = lds[j];
-      if (v && nlo + (j >> 8) < hi) atomicAdd(&cnt[(int64_t)(nlo + (j >> 8)) * 256 + (j & 255)], v);
-    }
-    __syncthreads();
-  }
-}
-
-template <int TILE_, int MAXB_, bool FAST>
-__device__ __forceinline__ void trk_scatter_body(const KeySrc& X, const u32* __restrict__ stateAll, u64* __restrict__ elemAll, const BwtArrays& A, const TrieArrays& T, int bitsG) {
-  constexpr int ITEMS_ = TILE_ / 1024;
-  const int b = bw_row_block(A, blockIdx.y);
-  if ((T.meta[(int64_t)b * TR_META + 1] <= TRS_FASTB) != FAST) return;
-  const int w0 = A.d_w[b];
-  const int W = A.d_m[b] - w0;
-  const int tbase = blockIdx.x * TILE_;
-  if (tbase >= W) return;
-  __shared__ u32 tc2[MAXB_ / 2];
-  __shared__ u32 gdelta[MAXB_];
-  __shared__ u64 stage[TILE_];
-  __shared__ uint16_t stageB[TILE_];
-  __shared__ u32 scan[32];
-  const int32_t* meta = T.meta + (int64_t)b * TR_META;
-  const int nB = meta[1];
-  const bool hasState = meta[10 + 2] > meta[2 + 2];
-  for (int i = threadIdx.x; i < (nB + 1) / 2; i += 1024) tc2[i] = 0;
-  __syncthreads();
-  const u64* key = X.key + (int64_t)b * A.NS + w0;
-  const u32* val = X.val + (int64_t)b * A.NS + w0;
-  const u32* state = stateAll + (int64_t)b * A.NS;
-  const u32* info = T.info + (int64_t)b * T.MN * 256;
-  u32* rank = A.rank + (int64_t)b * A.NS;
-  const u64 lowMask = (1ULL << bitsG) - 1ULL;
-  u64 el[ITEMS_]; u32 bp[ITEMS_];
-  // loads in rounds, as in k_tr_scatter: keys / suffixes / states of all items, then all info lookups
-  u64 k48v[ITEMS_]; u32 svv[ITEMS_], stv[ITEMS_];
-#pragma unroll
-  for (int r = 0; r < ITEMS_; r++) {
-    const int i = tbase + r * 1024 + threadIdx.x;
-    k48v[r] = 0; svv[r] = 0; stv[r] = 0xC0000000u;
-    if (i < W) {
-      k48v[r] = trk_k48(key[i], X.bitsR);
-      svv[r] = val[i];
-      stv[r] = hasState ? state[i] : ((1u << 16) | (u32)(k48v[r] >> 40));
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < ITEMS_; r++) {
-    const int i = tbase + r * 1024 + threadIdx.x;
-    if (i < W && (stv[r] >> 30) == 0) stv[r] = info[(stv[r] & 0xFFFFu) * 256 + (u32)((k48v[r] >> (40 - 8 * (int)((stv[r] >> 16) & 7u))) & 0xFFu)];
-  }
-#pragma unroll
-  for (int r = 0; r < ITEMS_; r++) {
-    const int i = tbase + r * 1024 + threadIdx.x;
-    bp[r] = 0xFFFFFFFFu;
-    el[r] = 0;
-    if (i < W) {
-      const u64 k48 = k48v[r];
-      const u32 sv = svv[r];
-      const u32 st = stv[r];
-      if ((st >> 30) == TR_K_TERM) {                                       // a new group of equal keys: its members' ranks, nothing to sort
-        if (!(st & TR_UNCHANGED)) rank[sv] = (st & 0xFFFFFFu) | BW_LIVE;
-      } else {
-        const u32 bk = st & 0xFFFFu;
-        const int skip = (int)((st >> 16) & 7u);
-        el[r] = (((k48 << 16) << (8 * skip)) & ~lowMask) | (u64)sv;
-        const u32 old = atomicAdd(&tc2[bk >> 1], (bk & 1u) ? 65536u : 1u);
-        bp[r] = bk | (((bk & 1u) ? (old >> 16) : (old & 0xFFFFu)) << 16);
-      }
-    }
-  }
-  __syncthreads();
-  {
-    const int per = 2 * ((nB + 2047) / 2048);
-    const int j0 = threadIdx.x * per;
-    u32 mine = 0;
-    for (int j = j0; j < j0 + per && j < nB; j += 2) { const u32 w = tc2[j >> 1]; mine += (w & 0xFFFFu) + (w >> 16); }
-    u32 total;
-    u32 run = kz_wg_excl_sum(mine, scan, &total);
-    const u32* bStart = T.bStart + (int64_t)b * T.MB;
-    u32* bFill = T.bFill + (int64_t)b * T.MB;
-    for (int j = j0; j < j0 + per && j < nB; j += 2) {
-      const u32 w = tc2[j >> 1];
-      const u32 c0 = w & 0xFFFFu, c1 = w >> 16;
-      if (c0) gdelta[j] = bStart[j] + atomicAdd(&bFill[j], c0) - run;
-      const u32 r1 = run + c0;
-      if (c1) gdelta[j + 1] = bStart[j + 1] + atomicAdd(&bFill[j + 1], c1) - r1;
-      tc2[j >> 1] = run | (r1 << 16);
-      run = r1 + c1;
-    }
-    if (threadIdx.x == 0) scan[31] = total;
-  }
-  __syncthreads();
-  const u32 total = scan[31];
-#pragma unroll
-  for (int r = 0; r < ITEMS_; r++) {
-    if (bp[r] != 0xFFFFFFFFu) {
-      const u32 bk = bp[r] & 0xFFFFu;
-      const u32 w = tc2[bk >> 1];
-      const u32 slot = ((bk & 1u) ? (w >> 16) : (w & 0xFFFFu)) + (bp[r] >> 16);
-      stage[slot] = el[r]; stageB[slot] = (uint16_t)bk;
-    }
-  }
-  __syncthreads();
-  u64* elem = elemAll + (int64_t)b * A.NS;
-#pragma unroll
-  for (int r = 0; r < ITEMS_; r++) {
-    const u32 slot = (u32)r * 1024 + threadIdx.x;
-    if (slot < total) elem[gdelta[stageB[slot]] + slot] = stage[slot];
-  }
-}
-
-__global__ __launch_bounds__(1024) void k_trk_scatter(KeySrc X, const u32* __restrict__ stateAll, u64* __restrict__ elemAll, BwtArrays A, TrieArrays T, int bitsG) { trk_scatter_body<TRS_TILE, TR_MAXB, false>(X, stateAll, elemAll, A, T, bitsG); }
-__global__ __launch_bounds__(1024) void k_trk_scatter_f(KeySrc X, const u32* __restrict__ stateAll, u64* __restrict__ elemAll, BwtArrays A, TrieArrays T, int bitsG) { trk_scatter_body<TRS_TILE / 2, TRS_FASTB, true>(X, stateAll, elemAll, A, T, bitsG); }
 
 // ---------------------------------------------------------------------------------------------
 // emit: header + BWT bytes (BWTBlockCodec.java:90-126, DivSufSort.java:217-224)
@@ -1799,248 +878,210 @@ __global__ void k_bwt_emit(const u8* __restrict__ src, int64_t srcStride, u8* __
 }
 
 // ---------------------------------------------------------------------------------------------
-// The trie round is used for blocks of 64 KiB .. 4 MiB (+ slack).  Table bounds (n = block length, C = TR_CAP):
-//   nodes: 256 of depth 1 + at most n / (C + 1) expanded children per level, levels 2 .. TR_DMAX_LIMIT - 1;
-//   buckets: children above TR_MERGE (<= n / (TR_MERGE + 1)) + merged ones: two neighbours of a run hold more than C suffixes
-//   together (<= 2n / C + 1 per run) and a run starts at a node or behind a breaker (nodes + children above TR_MERGE + terminals).
-#define TR_DMAX_LIMIT 7
-#define TR_MIN_N 65536
-#define TR_MAX_N ((4 << 20) + 65536)
-static inline int tr_max_nodes(int maxN) { return 257 + (TR_DMAX_LIMIT - 2) * (maxN / (int)(TR_CAP + 1) + 1); }
-static inline int tr_max_buckets(int maxN) {
-  const int med = maxN / (int)(TR_MERGE + 1) + 1, big = maxN / (int)(TR_CAP + 1) + 1;
-  return med + 2 * (maxN / (int)TR_CAP) + 2 + tr_max_nodes(maxN) + med + (TR_DMAX_LIMIT - 2) * big + big;
-}
-static inline bool tr_applies(int maxN) {                          // (KZ_BWT_TRIE=0 switches the trie rounds off at the call: ctx->sw.bwtTrie)
-  return maxN >= TR_MIN_N && maxN <= TR_MAX_N && tr_max_buckets(maxN) <= TR_MAXB && tr_max_nodes(maxN) <= 65535;
-}
-
+// host: the arena of a batch, term by term what bwt_alloc_arrays (and bwt_trie_alloc) take
 size_t kz_bwt_forward_scratch(int B, int maxN) {
   const int64_t NS = (int64_t)kz_align((size_t)maxN, RS_TILE);
   const int T = (int)(NS / RS_TILE);
-  size_t per = (size_t)NS * (8 * 2 + 4 * 2 + 4 + 4) + (size_t)(T + 4) * (256 * 4 + 12) + 2 * MSD_BINS * 4 + 64 + 11 * 256;
-  if (tr_applies(maxN)) per += (size_t)tr_max_nodes(maxN) * (2 * 1024 + 12) + (size_t)TR_MAXB * 20 + TR_META * 4 + 9 * 256;
+  size_t per = (size_t)NS * (8 * 2 + 4 * 2)      // key[2], val[2]
+             + (size_t)NS * (4 + 4)              // rank, sa
+             + (size_t)(T + 4) * 256 * 4         // tileHist: HS = radix tiles x MSD_BINS words, RSORT_TILE = 4 RS_TILE
+             + 2 * MSD_BINS * 4                  // digitBase, bucketCnt
+             + (size_t)(T + 4) * 12              // tileA, tileB, tileLive
+             + 64                                // d_w, d_big, d_m, d_m2, d_act
+             + 11 * 256;                         // the allocations' alignment
+  if (tr_applies(maxN)) per += bwt_trie_scratch(maxN);
   return kz_align(per * (size_t)B + 4096 * 16, 4096) + (1 << 20);
 }
+static bool bwt_alloc_arrays(BwtRun& R) {
+  BwtArrays& A = R.A;
+  const size_t B = (size_t)R.B, NS = (size_t)R.NS, T = (size_t)R.T;
+  bool ok = true;
+  auto take = [&](size_t bytes) { void* p = kz_arena_alloc(R.ctx, bytes); ok = ok && p != nullptr; return p; };
+  for (int i = 0; i < 2; i++) { A.key[i] = (u64*)take(NS * B * 8); A.val[i] = (u32*)take(NS * B * 4); }
+  A.rank = (u32*)take(NS * B * 4);
+  A.sa = (u32*)take(NS * B * 4);
+  A.tileHist = (u32*)take((size_t)A.HS * B * 4);
+  A.digitBase = (u32*)take(B * MSD_BINS * 4);
+  A.bucketCnt = (u32*)take(B * MSD_BINS * 4);
+  A.d_w = (int32_t*)take(B * 4);
+  A.d_big = (int32_t*)take(B * 4);
+  A.tileA = (u32*)take(T * B * 4);
+  A.tileB = (u32*)take(T * B * 4);
+  A.tileLive = (u32*)take(T * B * 4);
+  A.d_m = (int32_t*)take(B * 4);
+  A.d_m2 = (int32_t*)take(B * 4);
+  R.d_act = (int32_t*)take(B * 4);
+  return ok;
+}
 
-static inline int gridFor(int n, int per) { int g = (n + per - 1) / per; return g < 1 ? 1 : g; }
+static const int BW_K0 = 7;                                        // bytes of the first-round key
+static const int BW_BUCKET_MIN = 4096;                             // below: the whole list is a handful of LSD tiles
 
-// one pass of the stage; *trieOverflow is set (and nothing of the batch changed) when a trie table overflowed in any round
-static int bwt_forward_run(kz_ctx* ctx, kz_batch& bt, bool allowTrie, bool* trieOverflow) {
-  const int B = bt.B;
-  int maxN = 0;
-  for (int b = 0; b < B; b++) if (bt.h_len[b] > maxN) maxN = bt.h_len[b];
-  const int64_t NS = (int64_t)kz_align((size_t)(maxN > 0 ? maxN : 1), RS_TILE);
-  const int T = (int)(NS / RS_TILE);
-  BwtArrays A;
-  A.NS = NS; A.T = T; A.HS = (int64_t)((NS + RSORT_TILE - 1) / RSORT_TILE) * MSD_BINS;
-  for (int i = 0; i < 2; i++) {
-    A.key[i] = (u64*)kz_arena_alloc(ctx, (size_t)NS * B * 8);
-    A.val[i] = (u32*)kz_arena_alloc(ctx, (size_t)NS * B * 4);
-  }
-  A.rank = (u32*)kz_arena_alloc(ctx, (size_t)NS * B * 4);
-  A.sa = (u32*)kz_arena_alloc(ctx, (size_t)NS * B * 4);
-  A.tileHist = (u32*)kz_arena_alloc(ctx, (size_t)A.HS * B * 4);
-  A.digitBase = (u32*)kz_arena_alloc(ctx, (size_t)B * MSD_BINS * 4);
-  A.bucketCnt = (u32*)kz_arena_alloc(ctx, (size_t)B * MSD_BINS * 4);
-  A.d_w = (int32_t*)kz_arena_alloc(ctx, (size_t)B * 4);
-  A.d_big = (int32_t*)kz_arena_alloc(ctx, (size_t)B * 4);
-  A.tileA = (u32*)kz_arena_alloc(ctx, (size_t)T * B * 4);
-  A.tileB = (u32*)kz_arena_alloc(ctx, (size_t)T * B * 4);
-  A.tileLive = (u32*)kz_arena_alloc(ctx, (size_t)T * B * 4);
-  A.d_m = (int32_t*)kz_arena_alloc(ctx, (size_t)B * 4);
-  A.d_m2 = (int32_t*)kz_arena_alloc(ctx, (size_t)B * 4);
-  int32_t* d_act = (int32_t*)kz_arena_alloc(ctx, (size_t)B * 4);
-  A.act = nullptr;
-  if (!d_act || !A.d_m2 || !A.tileB || !A.tileLive || !A.sa || !A.d_big || !A.bucketCnt) { snprintf(ctx->err, sizeof(ctx->err), "bwt_forward: arena overflow"); return -KZ_ERR_DEVICE; }
-  bool useTrie = allowTrie && ctx->sw.bwtTrie != 0 && tr_applies(maxN);
-  TrieArrays TR;
-  memset(&TR, 0, sizeof(TR));
-  const size_t markTrie = ctx->arenaTop;
-  if (useTrie) {
-    TR.MN = tr_max_nodes(maxN); TR.MB = TR_MAXB;
-    TR.cnt = (u32*)kz_arena_alloc(ctx, (size_t)B * TR.MN * 1024);
-    TR.info = (u32*)kz_arena_alloc(ctx, (size_t)B * TR.MN * 1024);
-    TR.nodeStart = (u32*)kz_arena_alloc(ctx, (size_t)B * TR.MN * 4);
-    TR.bStart = (u32*)kz_arena_alloc(ctx, (size_t)B * TR.MB * 4);
-    TR.bCount = (u32*)kz_arena_alloc(ctx, (size_t)B * TR.MB * 4);
-    TR.bFill = (u32*)kz_arena_alloc(ctx, (size_t)B * TR.MB * 4);
-    TR.bAux = (u32*)kz_arena_alloc(ctx, (size_t)B * TR.MB * 4);
-    TR.bG = (u32*)kz_arena_alloc(ctx, (size_t)B * TR.MB * 4);
-    TR.nodePfx = (u32*)kz_arena_alloc(ctx, (size_t)B * TR.MN * 4);
-    TR.nodeGS = (u32*)kz_arena_alloc(ctx, (size_t)B * TR.MN * 4);
-    TR.meta = (int32_t*)kz_arena_alloc(ctx, (size_t)B * TR_META * 4);
-    TR.err = (int32_t*)kz_arena_alloc(ctx, 256);
-    if (!TR.cnt || !TR.info || !TR.nodeStart || !TR.bStart || !TR.bCount || !TR.bFill || !TR.bAux || !TR.bG || !TR.nodePfx || !TR.nodeGS || !TR.meta || !TR.err) {
-      // the caller sized the arena for the longest block the CHAIN can hand over, which may lie outside the trie rounds' range while
-      // this batch's blocks are inside: the LSD rounds need no tables
-      ctx->arenaTop = markTrie;
-      useTrie = false;
-    }
-  }
-  A.d_n = bt.d_len;
-  hipStream_t st = ctx->stream;
-  const u8* src = bt.buf[bt.cur];
-  u8* dst = bt.buf[bt.cur ^ 1];
-
-  int bitsR = 1;
-  while ((1LL << bitsR) < 2 * (int64_t)maxN + 2) bitsR++;         // secondary key < n + h + 1 <= 2n + 1
-  int bitsG = 1;
-  while ((1LL << bitsG) < (int64_t)maxN) bitsG++;
-
-  const int K0 = 7;                                                // bytes of the first-round key
-  u64 *kC = A.key[0], *kF = A.key[1];
-  u32 *vC = A.val[0], *vF = A.val[1];
-  KZ_LAUNCH(ctx, KID_BWT_INIT, k_bwt_init, dim3((B + 255) / 256), dim3(256), A, B);
-  const TextSrc X0 = {src, bt.stride, K0};
-  int mMax = maxN;
-  int h = 0;
+// geometry, switches and arrays of one pass over the batch
+static int bwt_plan(BwtRun& R, kz_ctx* ctx, kz_batch& bt, bool allowTrie) {
+  R.ctx = ctx; R.bt = &bt; R.B = bt.B;
+  for (int b = 0; b < bt.B; b++) if (bt.h_len[b] > R.maxN) R.maxN = bt.h_len[b];
+  const int maxN = R.maxN;
+  R.NS = (int64_t)kz_align((size_t)(maxN > 0 ? maxN : 1), RS_TILE);
+  R.T = (int)(R.NS / RS_TILE);
+  R.A.NS = R.NS; R.A.T = R.T; R.A.HS = (int64_t)((R.NS + RSORT_TILE - 1) / RSORT_TILE) * MSD_BINS;
+  if (!bwt_alloc_arrays(R)) { snprintf(ctx->err, sizeof(ctx->err), "bwt_forward: arena overflow"); return -KZ_ERR_DEVICE; }
+  // the caller sized the arena for the longest block the CHAIN can hand over, which may lie outside the trie rounds' range while
+  // this batch's blocks are inside: the LSD rounds need no tables
+  R.useTrie = allowTrie && ctx->sw.bwtTrie != 0 && tr_applies(maxN) && bwt_trie_alloc(ctx, bt.B, maxN, R.TR);
+  R.A.d_n = bt.d_len;
+  R.bitsR = 1;
+  while ((1LL << R.bitsR) < 2 * (int64_t)maxN + 2) R.bitsR++;       // secondary key < n + h + 1 <= 2n + 1
+  R.bitsG = 1;
+  while ((1LL << R.bitsG) < (int64_t)maxN) R.bitsG++;
   // bucket path of the later rounds: the packed LDS element needs BK_BITS + bitsR + bitsG <= 64
-  const bool useBuckets = (BK_BITS + bitsR + bitsG <= 64) && (1 << (bitsG > BK_BITS ? bitsG - BK_BITS : 0)) <= MSD_BINS && ctx->sw.bwtBuckets != 0;
-  const int nBuckets = 1 << (bitsG > BK_BITS ? bitsG - BK_BITS : 0);
-  const int bucketMin = 4096;                                      // below: the whole list is a handful of LSD tiles
-  bool windowed = false;
-  const u32 gmax = (u32)BK_GMAX;
-  const int tilesN = gridFor(maxN, RS_TILE);
-  // the context's switches (kz_switches: read when the context was created)
-  const int Dmax = (ctx->sw.bwtDmax >= 6 && ctx->sw.bwtDmax <= TR_DMAX_LIMIT) ? ctx->sw.bwtDmax : 6;
-  const bool noRetire = ctx->sw.bwtRetire == 0;                      // A/B switch: every block rides through every round, as before
-  const bool trieWinOff = ctx->sw.bwtTrieWin == 0;
-  const bool lazyRank = ctx->sw.bwtLazyRank != 0;
-  const bool trace = ctx->sw.bwtTrace != 0;
-  const int forceOvfRound = ctx->sw.bwtTestTrieOverflow;             // tests: pretend the tables overflowed in round <digit>
-  if (useTrie) KZ_HIP(hipMemsetAsync(TR.err, 0, 4, st));
-  int nAct = B;                                                      // grid rows of the later rounds: blocks with live suffixes (A.act)
-  int32_t* const h_act = ctx->hpin + B + 16;                         // their indices, host side (pipe_setup reserves 9 B + 64 ints)
-  for (int round = 0; round < 64 && mMax > 0; round++) {
-    // ---- sort (kC,vC) and apply.  Later rounds of blocks up to 4 MiB: bucket partition + one LDS sort per bucket, the
-    //      LSD passes only for the window of oversized buckets; otherwise LSD radix over the whole compact list ----
-    const int nbits = (round == 0) ? 8 * K0 : bitsR + bitsG;
-    const int passes = (nbits + 7) / 8;
-    const int gshift = (round == 0) ? 64 : bitsR;
-    const bool buckets = useBuckets && round > 0 && mMax >= bucketMin;
-    int wMax = mMax;                                               // largest LSD window of the batch
-    if (round == 0 && useTrie) {
-      // ---- the trie round: count level by level, move once, finish the buckets in LDS (elements in key[0], states in val[0]) ----
-      KZ_HIP(hipMemsetAsync(TR.bFill, 0, (size_t)B * TR.MB * 4, st));
-      KZ_HIP(hipMemsetAsync(TR.meta, 0, (size_t)B * TR_META * 4, st));
-      KZ_LAUNCH(ctx, KID_TR_HIST16, k_tr_hist16, dim3(2, B), dim3(1024), src, bt.stride, A, TR);
-      KZ_LAUNCH(ctx, KID_TR_ASSIGN, k_tr_assign, dim3(B), dim3(256), A, TR, 1, Dmax, 0);
-      const int P = B >= 2048 ? 1 : (B >= 1024 ? 2 : 8);
-      for (int L = 2; L < Dmax; L++) {
-        KZ_LAUNCH(ctx, KID_TR_COUNT, k_tr_count, dim3(P, B), dim3(1024), src, bt.stride, A.val[0], A, TR, L);
-        KZ_LAUNCH(ctx, KID_TR_ASSIGN, k_tr_assign, dim3(B), dim3(256), A, TR, L, Dmax, 0);
-      }
-      KZ_LAUNCH(ctx, KID_TR_SCATTER, k_tr_scatter_f, dim3(gridFor(maxN, TRS_TILE / 2), B), dim3(1024), src, bt.stride, A.val[0], A.key[0], A, TR, bitsG);
-      KZ_LAUNCH(ctx, KID_TR_SCATTER, k_tr_scatter, dim3(gridFor(maxN, TRS_TILE), B), dim3(1024), src, bt.stride, A.val[0], A.key[0], A, TR, bitsG);
-      const int G = std::max(16, std::min(1024, 8192 / B));
-      KZ_LAUNCH(ctx, KID_TR_SORT, k_tr_sort, dim3(G, B), dim3(1024), A.key[0], A, TR, bitsG, lazyRank ? 1 : 0);
-      if (lazyRank) KZ_LAUNCH(ctx, KID_TR_SORT, k_tr_sort, dim3(G, B), dim3(1024), A.key[0], A, TR, bitsG, 2);   // the blocks pass 1 guessed wrong (workgroups of the others leave at once)
-      wMax = 0;
-    } else
-    if (buckets) {
-      const int rt = gridFor(mMax, RSORT_TILE);
-      const int sh = bitsR + BK_BITS;
-      KZ_LAUNCH(ctx, KID_MSD_HIST, k_msd_hist, dim3(rt, nAct), dim3(KZ_WG), kC, A, sh);
-      KZ_LAUNCH(ctx, KID_MSD_SCAN, k_msd_scan, dim3(nAct), dim3(MSD_BINS), A);
-      KZ_HIP(hipMemcpyAsync(ctx->hpin, A.d_big, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-      KZ_LAUNCH(ctx, KID_MSD_SCATTER, k_msd_scatter, dim3(rt, nAct), dim3(RSC_WG), kC, vC, kF, vF, A, sh);
-      { u64* tk = kC; kC = kF; kF = tk; u32* tv = vC; vC = vF; vF = tv; }
-      KZ_LAUNCH(ctx, KID_BUCKET_COUNT_S, k_bucket_count_s, dim3(nBuckets, nAct), dim3(256), kC, vC, A, bitsR, bitsG, gmax);
-      KZ_LAUNCH(ctx, KID_BUCKET_COUNT, k_bucket_count, dim3(nBuckets, nAct), dim3(1024), kC, vC, A, bitsR, bitsG, gmax);
-      KZ_LAUNCH(ctx, KID_BUCKET_SORT, k_bucket_sort, dim3(nBuckets, nAct), dim3(1024), kC, vC, A, bitsR, bitsG);
-      KZ_HIP(kz_stream_sync(ctx, st));
-      wMax = 0;                                                      // (a retired block's d_big is stale: only the live rows count)
-      for (int r = 0; r < nAct; r++) { const int b = A.act ? h_act[r] : r; if (ctx->hpin[b] > wMax) wMax = ctx->hpin[b]; }
-      windowed = true;
-      if (trace) {
-        long long tot = 0; for (int r = 0; r < nAct; r++) tot += ctx->hpin[A.act ? h_act[r] : r];
-        fprintf(stderr, "[bwt] round %d: %lld suffixes in oversized buckets, max per block %d\n", round, tot, wMax);
-      }
-    } else if (windowed) {
-      KZ_HIP(hipMemsetAsync(A.d_w, 0, (size_t)B * 4, st));
-      windowed = false;
+  R.nBuckets = 1 << (R.bitsG > BK_BITS ? R.bitsG - BK_BITS : 0);
+  R.useBuckets = (BK_BITS + R.bitsR + R.bitsG <= 64) && R.nBuckets <= MSD_BINS && ctx->sw.bwtBuckets != 0;
+  R.Dmax = (ctx->sw.bwtDmax >= 6 && ctx->sw.bwtDmax <= TR_DMAX_LIMIT) ? ctx->sw.bwtDmax : 6;
+  R.noRetire = ctx->sw.bwtRetire == 0;                              // A/B switch: every block rides through every round, as before
+  R.trieWinOff = ctx->sw.bwtTrieWin == 0;
+  R.lazyRank = ctx->sw.bwtLazyRank != 0;
+  R.trace = ctx->sw.bwtTrace != 0;
+  R.forceOvfRound = ctx->sw.bwtTestTrieOverflow;                    // tests: pretend the tables overflowed in round <digit>
+  R.kC = R.A.key[0]; R.kF = R.A.key[1]; R.vC = R.A.val[0]; R.vF = R.A.val[1];
+  R.nAct = bt.B;
+  R.h_act = ctx->hpin + bt.B + 16;                                  // (pipe_setup reserves 9 B + 64 ints)
+  R.mMax = maxN;
+  return 0;
+}
+
+// a later round of blocks up to 4 MiB: bucket partition + one LDS kernel per bucket; what is left for the window comes back in wMax
+static int bwt_round_buckets(BwtRun& R, int round) {
+  kz_ctx* ctx = R.ctx; BwtArrays& A = R.A;
+  const int nAct = R.nAct, nBuckets = R.nBuckets;
+  const int rt = gridFor(R.mMax, RSORT_TILE);
+  const int sh = R.bitsR + BK_BITS;
+  KZ_LAUNCH(ctx, KID_MSD_HIST, k_msd_hist, dim3(rt, nAct), dim3(KZ_WG), R.kC, A, sh);
+  KZ_LAUNCH(ctx, KID_MSD_SCAN, k_msd_scan, dim3(nAct), dim3(MSD_BINS), A);
+  KZ_HIP(hipMemcpyAsync(ctx->hpin, A.d_big, (size_t)R.B * 4, hipMemcpyDeviceToHost, ctx->stream));
+  KZ_LAUNCH(ctx, KID_MSD_SCATTER, k_msd_scatter, dim3(rt, nAct), dim3(RSC_WG), R.kC, R.vC, R.kF, R.vF, A, sh);
+  R.swap();
+  KZ_LAUNCH(ctx, KID_BUCKET_COUNT_S, k_bucket_count_s, dim3(nBuckets, nAct), dim3(256), R.kC, R.vC, A, R.bitsR, R.bitsG, (u32)BK_GMAX);
+  KZ_LAUNCH(ctx, KID_BUCKET_COUNT, k_bucket_count, dim3(nBuckets, nAct), dim3(1024), R.kC, R.vC, A, R.bitsR, R.bitsG, (u32)BK_GMAX);
+  KZ_LAUNCH(ctx, KID_BUCKET_SORT, k_bucket_sort, dim3(nBuckets, nAct), dim3(1024), R.kC, R.vC, A, R.bitsR, R.bitsG);
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  R.wMax = 0;                                                      // (a retired block's d_big is stale: only the live rows count)
+  long long tot = 0;
+  for (int r = 0; r < nAct; r++) { const int w = ctx->hpin[A.act ? R.h_act[r] : r]; tot += w; if (w > R.wMax) R.wMax = w; }
+  R.windowed = true;
+  if (R.trace) fprintf(stderr, "[bwt] round %d: %lld suffixes in oversized buckets, max per block %d\n", round, tot, R.wMax);
+  return 0;
+}
+
+// LSD radix over the window [d_w, d_m) of the compact list (the whole list without buckets), then SA order: new groups, ranks, final suffixes
+static int bwt_round_lsd(BwtRun& R, int round) {
+  kz_ctx* ctx = R.ctx; const BwtArrays& A = R.A;
+  const int nAct = R.nAct;
+  const int nbits = (round == 0) ? 8 * BW_K0 : R.bitsR + R.bitsG;
+  const int passes = (nbits + 7) / 8;
+  const int gshift = (round == 0) ? 64 : R.bitsR;
+  const int tiles = gridFor(R.wMax, RS_TILE);
+  const int rtiles = gridFor(R.wMax, RSORT_TILE);
+  for (int p = 0; p < passes; p++) {
+    if (round == 0 && p == 0) {                                    // keys straight from the text
+      const TextSrc X0 = {R.bt->buf[R.bt->cur], R.bt->stride, BW_K0};
+      KZ_LAUNCH(ctx, KID_RADIX_HIST, k_radix_hist0, dim3(rtiles, nAct), dim3(KZ_WG), A, X0);
+      KZ_LAUNCH(ctx, KID_RADIX_SCAN, k_radix_scan, dim3(nAct), dim3(256), A);
+      KZ_LAUNCH(ctx, KID_RADIX_SCATTER, k_radix_scatter0, dim3(rtiles, nAct), dim3(RSC_WG), R.kF, R.vF, A, X0);
+    } else {
+      KZ_LAUNCH(ctx, KID_RADIX_HIST, k_radix_hist, dim3(rtiles, nAct), dim3(KZ_WG), R.kC, A, p * 8);
+      KZ_LAUNCH(ctx, KID_RADIX_SCAN, k_radix_scan, dim3(nAct), dim3(256), A);
+      KZ_LAUNCH(ctx, KID_RADIX_SCATTER, k_radix_scatter, dim3(rtiles, nAct), dim3(RSC_WG), R.kC, R.vC, R.kF, R.vF, A, p * 8);
     }
-    const bool trieWindow = useTrie && buckets && wMax > 0 && bitsR <= 24 && bitsG <= 24 && !trieWinOff;
-    if (trieWindow) {
-      // ---- the window of oversized buckets through a KEY trie round (k_trk_*): count by key byte, move once, finish in LDS ----
-      const KeySrc XK = {kC, vC, bitsR};
-      KZ_HIP(hipMemsetAsync(TR.bFill, 0, (size_t)B * TR.MB * 4, st));
-      KZ_HIP(hipMemsetAsync(TR.meta, 0, (size_t)B * TR_META * 4, st));
-      KZ_LAUNCH(ctx, KID_TR_HIST16, k_trk_hist16, dim3(2, nAct), dim3(1024), XK, A, TR);
-      KZ_LAUNCH(ctx, KID_TR_ASSIGN, k_tr_assign, dim3(nAct), dim3(256), A, TR, 1, 6, 1);
-      const int PW = nAct >= 1024 ? 1 : (nAct >= 256 ? 2 : 4);
-      for (int L = 2; L < 6; L++) {
-        KZ_LAUNCH(ctx, KID_TR_COUNT, k_trk_count, dim3(PW, nAct), dim3(1024), XK, vF, A, TR, L);
-        KZ_LAUNCH(ctx, KID_TR_ASSIGN, k_tr_assign, dim3(nAct), dim3(256), A, TR, L, 6, 1);
-      }
-      KZ_LAUNCH(ctx, KID_TR_SCATTER, k_trk_scatter_f, dim3(gridFor(wMax, TRS_TILE / 2), nAct), dim3(1024), XK, vF, kF, A, TR, bitsG);
-      KZ_LAUNCH(ctx, KID_TR_SCATTER, k_trk_scatter, dim3(gridFor(wMax, TRS_TILE), nAct), dim3(1024), XK, vF, kF, A, TR, bitsG);
-      const int G = std::max(16, std::min(1024, 8192 / nAct));
-      KZ_LAUNCH(ctx, KID_TR_SORT, k_trk_sort, dim3(G, nAct), dim3(1024), kF, A, TR, bitsG);
-    } else
-    if (wMax > 0) {
-      const int tiles = gridFor(wMax, RS_TILE);
-      const int rtiles = gridFor(wMax, RSORT_TILE);
-      for (int p = 0; p < passes; p++) {
-        if (round == 0 && p == 0) {                                  // keys straight from the text
-          KZ_LAUNCH(ctx, KID_RADIX_HIST, k_radix_hist0, dim3(rtiles, nAct), dim3(KZ_WG), A, X0);
-          KZ_LAUNCH(ctx, KID_RADIX_SCAN, k_radix_scan, dim3(nAct), dim3(256), A);
-          KZ_LAUNCH(ctx, KID_RADIX_SCATTER, k_radix_scatter0, dim3(rtiles, nAct), dim3(RSC_WG), kF, vF, A, X0);
-        } else {
-        KZ_LAUNCH(ctx, KID_RADIX_HIST, k_radix_hist, dim3(rtiles, nAct), dim3(KZ_WG), kC, A, p * 8);
-        KZ_LAUNCH(ctx, KID_RADIX_SCAN, k_radix_scan, dim3(nAct), dim3(256), A);
-        KZ_LAUNCH(ctx, KID_RADIX_SCATTER, k_radix_scatter, dim3(rtiles, nAct), dim3(RSC_WG), kC, vC, kF, vF, A, p * 8);
-        }
-        u64* tk = kC; kC = kF; kF = tk;
-        u32* tv = vC; vC = vF; vF = tv;
-      }
-      // ---- SA order: new groups, ranks, final suffixes ----
-      KZ_LAUNCH(ctx, KID_SEG_REDUCE, k_seg_reduce, dim3(tiles, nAct), dim3(KZ_WG), kC, A, gshift);
-      KZ_LAUNCH(ctx, KID_SEG_SCAN, k_seg_scan, dim3(nAct), dim3(64), A);
-      KZ_LAUNCH(ctx, KID_SEG_APPLY, k_seg_apply, dim3(tiles, nAct), dim3(KZ_WG), kC, vC, A, gshift);
-    }
-    // ---- text order: compact the live suffixes, keys for the next round ----
-    h = (round == 0) ? (useTrie ? 6 : K0) : h * 2;
-    KZ_HIP(hipMemsetAsync(A.d_m2, 0, (size_t)B * 4, st));
-    KZ_LAUNCH(ctx, KID_LIVE_EMIT, k_live_emit, dim3(tilesN, nAct), dim3(KZ_WG), kF, vF, A, h, bitsR, round == 0 ? 1 : 0, (round == 0 && useTrie && lazyRank) ? TR.meta : (const int32_t*)nullptr);
-    { u64* tk = kC; kC = kF; kF = tk; u32* tv = vC; vC = vF; vF = tv; }
-    // ---- read back the next compact sizes ----
-    KZ_HIP(hipMemcpyAsync(ctx->hpin, A.d_m2, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    // the trie tables' overflow flag rides along, every round that ran a trie (round 0 and the key rounds of the window): an
-    // overflow dropped buckets, the ranks of this pass are void (the bounds of tr_max_nodes / tr_max_buckets say it cannot happen)
-    ctx->hpin[B] = 0;
-    if (useTrie) KZ_HIP(hipMemcpyAsync(ctx->hpin + B, TR.err, 4, hipMemcpyDeviceToHost, st));
-    KZ_HIP(kz_stream_sync(ctx, st));
-    mMax = 0;
-    for (int b = 0; b < B; b++) if (ctx->hpin[b] > mMax) mMax = ctx->hpin[b];
-    if (useTrie && (ctx->hpin[B] != 0 || round == forceOvfRound)) { *trieOverflow = true; return 0; }
-    if (trace) {                                   // diagnostic: live suffixes left after every doubling round
-      long long tot = 0, totN = 0; for (int b = 0; b < B; b++) { tot += ctx->hpin[b]; totN += bt.h_len[b]; }
-      fprintf(stderr, "[bwt] round %d h=%d: live %lld of %lld (%.1f%%), max per block %d\n", round, h, tot, totN, 100.0 * tot / (totN ? totN : 1), mMax);
-    }
-    int32_t* tm = A.d_m; A.d_m = A.d_m2; A.d_m2 = tm;
-    // ---- retire the blocks that are done: the next round's grids get one row per block that still has live suffixes ----
-    if (mMax > 0 && !noRetire) {
-      int cnt = 0;
-      for (int b = 0; b < B; b++) if (ctx->hpin[b] > 0) h_act[cnt++] = b;     // (hpin[0 .. B) is read before the next copy lands: in-order stream)
-      if (cnt < B) {
-        KZ_HIP(hipMemcpyAsync(d_act, h_act, (size_t)cnt * 4, hipMemcpyHostToDevice, st));
-        A.act = d_act;
-        nAct = cnt;
-      }
-    }
+    R.swap();
   }
-  if (mMax > 0) { snprintf(ctx->err, sizeof(ctx->err), "bwt_forward: suffix sort did not converge"); return -KZ_ERR_PROCESS_BLOCK; }
-  {
-    const int rows8 = (B + 7) / 8 * 8;
-    const bool xcd = rows8 <= KZ_MAX_BATCH;
-    KZ_LAUNCH(ctx, KID_BWT_EMIT, k_bwt_emit, dim3(gridFor(maxN, 256 * 8), xcd ? rows8 : B), dim3(256), src, bt.stride, dst, bt.stride, A, bt.d_len2, bt.d_flag, xcd ? B : -1);
+  KZ_LAUNCH(ctx, KID_SEG_REDUCE, k_seg_reduce, dim3(tiles, nAct), dim3(KZ_WG), R.kC, A, gshift);
+  KZ_LAUNCH(ctx, KID_SEG_SCAN, k_seg_scan, dim3(nAct), dim3(64), A);
+  KZ_LAUNCH(ctx, KID_SEG_APPLY, k_seg_apply, dim3(tiles, nAct), dim3(KZ_WG), R.kC, R.vC, A, gshift);
+  return 0;
+}
+
+// text order: compact the live suffixes with their keys for the next round, and read the next compact sizes back
+static int bwt_compact_and_read_back(BwtRun& R, int round, bool* trieOverflow) {
+  kz_ctx* ctx = R.ctx; BwtArrays& A = R.A;
+  const int B = R.B;
+  hipStream_t st = ctx->stream;
+  R.h = (round == 0) ? (R.useTrie ? 6 : BW_K0) : R.h * 2;
+  KZ_HIP(hipMemsetAsync(A.d_m2, 0, (size_t)B * 4, st));
+  KZ_LAUNCH(ctx, KID_LIVE_EMIT, k_live_emit, dim3(gridFor(R.maxN, RS_TILE), R.nAct), dim3(KZ_WG), R.kF, R.vF, A, R.h, R.bitsR, round == 0 ? 1 : 0,
+            (round == 0 && R.useTrie && R.lazyRank) ? R.TR.meta : (const int32_t*)nullptr);
+  R.swap();
+  KZ_HIP(hipMemcpyAsync(ctx->hpin, A.d_m2, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+  // the trie tables' overflow flag rides along, every round that ran a trie (round 0 and the key rounds of the window): an
+  // overflow dropped buckets, the ranks of this pass are void (the bounds of tr_max_nodes / tr_max_buckets say it cannot happen)
+  ctx->hpin[B] = 0;
+  if (R.useTrie) KZ_HIP(hipMemcpyAsync(ctx->hpin + B, R.TR.err, 4, hipMemcpyDeviceToHost, st));
+  KZ_HIP(kz_stream_sync(ctx, st));
+  R.mMax = 0;
+  for (int b = 0; b < B; b++) if (ctx->hpin[b] > R.mMax) R.mMax = ctx->hpin[b];
+  if (R.useTrie && (ctx->hpin[B] != 0 || round == R.forceOvfRound)) { *trieOverflow = true; return 0; }
+  if (R.trace) {                                   // diagnostic: live suffixes left after every doubling round
+    long long tot = 0, totN = 0; for (int b = 0; b < B; b++) { tot += ctx->hpin[b]; totN += R.bt->h_len[b]; }
+    fprintf(stderr, "[bwt] round %d h=%d: live %lld of %lld (%.1f%%), max per block %d\n", round, R.h, tot, totN, 100.0 * tot / (totN ? totN : 1), R.mMax);
   }
+  std::swap(A.d_m, A.d_m2);
+  return 0;
+}
+
+// retire the blocks that are done: the next round's grids get one row per block that still has live suffixes
+static int bwt_retire(BwtRun& R) {
+  kz_ctx* ctx = R.ctx;
+  if (R.mMax <= 0 || R.noRetire) return 0;
+  int cnt = 0;
+  for (int b = 0; b < R.B; b++) if (ctx->hpin[b] > 0) R.h_act[cnt++] = b;     // (hpin[0 .. B) is read before the next copy lands: in-order stream)
+  if (cnt < R.B) {
+    KZ_HIP(hipMemcpyAsync(R.d_act, R.h_act, (size_t)cnt * 4, hipMemcpyHostToDevice, ctx->stream));
+    R.A.act = R.d_act;
+    R.nAct = cnt;
+  }
+  return 0;
+}
+
+static int bwt_emit(BwtRun& R) {
+  kz_ctx* ctx = R.ctx; kz_batch& bt = *R.bt;
+  const int B = R.B;
+  const int rows8 = (B + 7) / 8 * 8;
+  const bool xcd = rows8 <= KZ_MAX_BATCH;
+  KZ_LAUNCH(ctx, KID_BWT_EMIT, k_bwt_emit, dim3(gridFor(R.maxN, 256 * 8), xcd ? rows8 : B), dim3(256), bt.buf[bt.cur], bt.stride, bt.buf[bt.cur ^ 1], bt.stride,
+            R.A, bt.d_len2, bt.d_flag, xcd ? B : -1);
   KZ_HIP(hipGetLastError());
   bt.cur ^= 1;
-  { int32_t* t = bt.d_len; bt.d_len = bt.d_len2; bt.d_len2 = t; }
+  std::swap(bt.d_len, bt.d_len2);
   return 0;
+}
+
+// one pass of the stage; *trieOverflow is set (and nothing of the batch changed) when a trie table overflowed in any round.
+// A round sorts (kC, vC) and applies the new groups by ONE of four paths -- the trie round over the text (round 0), else the bucket
+// partition with the window of oversized buckets through a key trie round or through the LSD passes, else the LSD passes over the
+// whole compact list -- and then compacts what is still live.
+static int bwt_forward_run(kz_ctx* ctx, kz_batch& bt, bool allowTrie, bool* trieOverflow) {
+  BwtRun R{};
+  int rc = bwt_plan(R, ctx, bt, allowTrie);
+  if (rc) return rc;
+  KZ_LAUNCH(ctx, KID_BWT_INIT, k_bwt_init, dim3((R.B + 255) / 256), dim3(256), R.A, R.B);
+  if (R.useTrie) KZ_HIP(hipMemsetAsync(R.TR.err, 0, 4, ctx->stream));
+  for (int round = 0; round < 64 && R.mMax > 0; round++) {
+    const bool buckets = R.useBuckets && round > 0 && R.mMax >= BW_BUCKET_MIN;
+    R.wMax = R.mMax;
+    if (round == 0 && R.useTrie) { rc = bwt_trie_text_round(R); R.wMax = 0; }
+    else if (buckets) rc = bwt_round_buckets(R, round);
+    else if (R.windowed) { KZ_HIP(hipMemsetAsync(R.A.d_w, 0, (size_t)R.B * 4, ctx->stream)); R.windowed = false; }
+    if (rc) return rc;
+    const bool trieWindow = R.useTrie && buckets && R.wMax > 0 && R.bitsR <= 24 && R.bitsG <= 24 && !R.trieWinOff;
+    if (trieWindow) rc = bwt_trie_key_round(R);
+    else if (R.wMax > 0) rc = bwt_round_lsd(R, round);
+    if (rc) return rc;
+    rc = bwt_compact_and_read_back(R, round, trieOverflow);
+    if (rc || *trieOverflow) return rc;
+    if ((rc = bwt_retire(R)) != 0) return rc;
+  }
+  if (R.mMax > 0) { snprintf(ctx->err, sizeof(ctx->err), "bwt_forward: suffix sort did not converge"); return -KZ_ERR_PROCESS_BLOCK; }
+  return bwt_emit(R);
 }
 
 int kz_stage_bwt_forward(kz_ctx* ctx, kz_batch& bt) {
