@@ -530,6 +530,68 @@ int64_t kz_read_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n,
                              const int64_t* rangeOff /* host */, const int64_t* rangeLen /* host */, int32_t nRanges,
                              uint8_t* d_dst, int64_t dstCap, int64_t* got /* host, out */);
 
+/* ---- many-stream index and byte-addressed reads: N streams in one call -----------------------------
+ * kz_knz_index_device and kz_read_bytes_device for the N streams that kz_compress_many_device wrote (or any others): a store of
+ * compressed objects in HBM is indexed once and then asked for records of several objects at a time.  Streams are described as in
+ * kz_decompress_many_device: stream s is d_src[srcOff[s] .. srcOff[s] + srcLen[s]), offsets non-negative and relative to d_src.
+ * The single-stream calls define every result.
+ *
+ * kz_knz_index_many_device: status[s] = the stream's block count or its negative code, the header fields of stream s (written
+ * whenever its header parses, as the single call does) and the entries [indexFirst[s], indexFirst[s + 1]) of blockBitOff / blockBits
+ * are what kz_knz_index_device gives for segment s alone with a large enough cap.  Bit offsets count from the stream's own first bit.
+ * A stream that fails contributes no entries; its fault lives in status[s] only.
+ *
+ * kz_read_bytes_many_device: range i asks for bytes [rangeOff[i], rangeOff[i] + rangeLen[i]) of the original data of stream
+ * rangeStream[i].  Stream s's index is the entries [indexFirst[s], indexFirst[s + 1]) of blockBitOff / blockBits (one
+ * kz_knz_index_many_device call gives all three arrays); its table of block starts, if it has one (tableFirst[s] >= 0), is the index
+ * length + 1 entries of blockByteOff from tableFirst[s] on and means what it means for kz_read_bytes_device.  The destination is
+ * packed by requested length over all ranges in call order: range i owns d_dst[D[i] .. D[i] + rangeLen[i]), D[i] = the sum of
+ * rangeLen[j] for j < i.  got[i] and the first got[i] bytes of slot i are what kz_read_bytes_device gives for that stream alone when
+ * asked that stream's ranges in their call order: the cut at the end of data, ends past int64, repeats and overlaps, the
+ * -KZ_ERR_INVALID_FILE rule on block lengths, and a block's own fault in got[i] of the ranges that touch it.  What is a fault of the
+ * whole call in the single-stream form (the stream header's code, a refused table, a first used index entry that does not match the
+ * stream) is the fault of that stream alone here: it goes to got[i] of every range of that stream and to streamStatus[s] (0 for
+ * every other stream), and every other stream is delivered as if the failing one were not there.
+ *
+ *   addresses   d_src, d_dst: any address, any alignment; d_dst must not overlap a stream.  All arrays and out-pointers are host memory.
+ *   read        nothing outside a stream's own segment (every table entry of the kernels carries its own stream's bounds).  The
+ *               index call reads each stream's header and prefixes; the read call only the header and the touched blocks of the
+ *               streams that some range names: a stream no range names is not opened at all.
+ *   written     the index call: status[0 .. nStreams), indexFirst[0 .. nStreams], the entries below cap.  The read call: nothing
+ *               outside the slots; of slot i the first got[i] bytes, the tail of a cut slot is untouched; got[0 .. nRanges) and
+ *               streamStatus[0 .. nStreams) (may be NULL) whenever the call returns a size.
+ *   returns     kz_knz_index_many_device: the total number of entries, which may exceed cap: indexFirst is complete all the same
+ *               and only the entries below cap are written (cap == 0: blockBitOff and blockBits may be NULL); the caller calls
+ *               again with that many.  kz_read_bytes_many_device: D[nRanges].  Or a negative code for a fault of the call itself, in
+ *               this order: -KZ_ERR_INVALID_PARAM for bad arguments (null pointers with nStreams > 0 resp. nRanges > 0, a negative
+ *               count, offset, length or capacity, rangeStream[i] outside [0, nStreams), an indexFirst that descends, a tableFirst[s]
+ *               below -1); -KZ_ERR_WRITE_FILE for D[nRanges] > dstCap, decided before anything is written; -KZ_ERR_DEVICE.
+ *               nStreams == 0 (index) returns 0 and touches nothing, nRanges == 0 (read) returns 0.  kz_last_error: the text of the
+ *               first failing stream in stream order.
+ *   chunks      the index call is three launches and three host waits whatever nStreams is: the heads of all streams in one copy
+ *               (parsed on the host), a count pass and a fill pass with one lane per stream.  The read call merges the distinct
+ *               covering blocks of all named streams into one list ordered by header group (the streams with equal transform word,
+ *               entropy id, block size and checksum kind, in order of first appearance), then stream, then block.  Every used entry
+ *               is checked against its own stream in launches of 2^18 entries before anything is unpacked.  The list goes in chunks
+ *               of kz_compress_device's size for the group's block size (KZ_STREAM_CHUNK=<blocks> overrides), each inside one header
+ *               group: one unpack launch, one batched decode under that group's header and checksum kind, and one copy launch per
+ *               2^20 segments for the segments of all the chunk's streams.  So N streams of one header cost the launches and waits of
+ *               one single-stream call over the same number of blocks.  Tables: 40 bytes per row of a chunk, 56 per checked entry
+ *               of a launch, 32 per segment of a launch, pinned and in HBM; host memory proportional to the segments, the rows and
+ *               nStreams.
+ *   stream      the calls are synchronous and run on the context's stream.
+ */
+int64_t kz_knz_index_many_device(kz_ctx* ctx, const uint8_t* d_src, const int64_t* srcOff /* host */, const int64_t* srcLen /* host */, int32_t nStreams,
+                                 uint64_t* transformType, uint32_t* entropyType, int32_t* blockSize, int64_t* inputSize, int32_t* checksumBits, /* host [nStreams], each may be NULL */
+                                 int32_t* status /* host [nStreams] */, int64_t* indexFirst /* host [nStreams + 1] */,
+                                 int64_t* blockBitOff /* host */, int64_t* blockBits /* host */, int64_t cap);
+int64_t kz_read_bytes_many_device(kz_ctx* ctx, const uint8_t* d_src, const int64_t* srcOff /* host */, const int64_t* srcLen /* host */, int32_t nStreams,
+                                  const int64_t* indexFirst /* host [nStreams + 1] */, const int64_t* blockBitOff /* host */, const int64_t* blockBits /* host */,
+                                  const int64_t* tableFirst /* host: NULL, or [nStreams] with -1 for a stream without a table */,
+                                  const int64_t* blockByteOff /* host: NULL when tableFirst is */,
+                                  const int32_t* rangeStream /* host */, const int64_t* rangeOff /* host */, const int64_t* rangeLen /* host */, int32_t nRanges,
+                                  uint8_t* d_dst, int64_t dstCap, int64_t* got /* host, out [nRanges] */, int32_t* streamStatus /* host, out [nStreams] or NULL */);
+
 /* ---- byte-addressed writes: many ranges of the original data replaced in one call ------------------
  * "Replace bytes [rangeOff[i], rangeOff[i] + rangeLen[i]) of the original data by these new bytes, for nRanges ranges at once, and
  * give me the new stream", on host memory and on device memory.  The result is a NEW stream in a separate buffer, as with the splice:

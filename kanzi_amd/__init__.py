@@ -125,6 +125,8 @@ def load_library():
         "kz_decode_indexed_device": (c.c_int32, [vp, u8p, c.c_int64, i64p, i64p, c.c_int32, u8p, c.c_int64, vp]),
         "kz_read_bytes": (c.c_int64, [vp, u8p, c.c_int64, i64p, i64p, i64p, c.c_int32, i64p, i64p, c.c_int32, u8p, c.c_int64, i64p]),
         "kz_read_bytes_device": (c.c_int64, [vp, u8p, c.c_int64, i64p, i64p, i64p, c.c_int32, i64p, i64p, c.c_int32, u8p, c.c_int64, i64p]),
+        "kz_knz_index_many_device": (c.c_int64, [vp, u8p, i64p, i64p, c.c_int32, vp, vp, vp, vp, vp, i32p, i64p, i64p, i64p, c.c_int64]),
+        "kz_read_bytes_many_device": (c.c_int64, [vp, u8p, i64p, i64p, c.c_int32, i64p, i64p, i64p, i64p, i64p, i32p, i64p, i64p, c.c_int32, u8p, c.c_int64, i64p, i32p]),
         "kz_write_bytes_bound": (c.c_int64, [i64p, c.c_int32, c.c_int32]),
         "kz_write_bytes": (c.c_int64, [vp, u8p, c.c_int64, i64p, i64p, i64p, c.c_int32, i64p, i64p, c.c_int32, u8p, c.c_int64, u8p, c.c_int64, i64p, i64p]),
         "kz_write_bytes_device": (c.c_int64, [vp, u8p, c.c_int64, i64p, i64p, i64p, c.c_int32, i64p, i64p, c.c_int32, u8p, c.c_int64, u8p, c.c_int64, i64p, i64p]),
@@ -161,7 +163,7 @@ ABI_SYMBOLS = ["kz_abi_version", "kz_ctx_create", "kz_ctx_destroy", "kz_last_err
                "kz_compress_device", "kz_decompress_device", "kz_knz_assemble_device", "kz_knz_index_device",
                "kz_compress_many_bound", "kz_compress_many_device", "kz_decompress_many_device",
                "kz_decompress_range", "kz_decompress_range_device", "kz_decode_indexed", "kz_decode_indexed_device",
-               "kz_read_bytes", "kz_read_bytes_device",
+               "kz_read_bytes", "kz_read_bytes_device", "kz_knz_index_many_device", "kz_read_bytes_many_device",
                "kz_write_bytes_bound", "kz_write_bytes", "kz_write_bytes_device",
                "kz_knz_splice_bound", "kz_knz_splice", "kz_knz_splice_device",
                "kz_knz_scan", "kz_knz_scan_device",
@@ -1407,6 +1409,149 @@ class KnzReader:
         torch.cuda.current_stream(dev).synchronize()                 # the call runs on the context's own stream
         size, _ = write_bytes_device(self.ctx, self.src.data_ptr(), self.src.numel(), self.blocks, offsets, sizes, data.data_ptr(), out.data_ptr(), cap, self.byte_offsets)
         return KnzReader(self.ctx, out[:size], self.byte_offsets)
+
+
+# ---- many-stream index and byte-addressed reads (kz_knz_index_many_device / kz_read_bytes_many_device) ----
+def knz_index_many_device(ctx, src, src_off, src_len):
+    """kz_knz_index_many_device: knz_index_device for stream s = the src_len[s] bytes at device address src + src_off[s], all in one
+    call -> a list with, per stream, the dict knz_index_device returns and "status" (its block count), or {"status": negative code}
+    for a stream that fails.  A fault of the call itself raises."""
+    so = np.ascontiguousarray(src_off, dtype=np.int64)
+    sl = np.ascontiguousarray(src_len, dtype=np.int64)
+    if len(so) != len(sl):
+        raise ValueError("src_off and src_len must have one length")
+    n = len(so)
+    if n == 0:
+        return []
+    tt, et, bs = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.int32)
+    isz, chk, status, first = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n + 1, dtype=np.int64)
+    cap = max(16, int(sl.sum()) // 256)
+    while True:
+        off, bits = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int64)
+        total = int(ctx.check(ctx.lib.kz_knz_index_many_device(ctx.h, _ptr(src), so.ctypes.data, sl.ctypes.data, n, tt.ctypes.data, et.ctypes.data, bs.ctypes.data,
+                                                               isz.ctypes.data, chk.ctypes.data, status.ctypes.data, first.ctypes.data, off.ctypes.data, bits.ctypes.data, cap)))
+        if total <= cap:
+            break
+        cap = total                                             # a second call with that many
+    out = []
+    for s in range(n):
+        if status[s] < 0:
+            out.append({"status": int(status[s])})
+            continue
+        a, b = int(first[s]), int(first[s + 1])
+        out.append({"status": int(status[s]), "transform": int(tt[s]), "entropy": int(et[s]), "blockSize": int(bs[s]), "inputSize": int(isz[s]), "checksum": int(chk[s]),
+                    "blocks": [(int(o), int(w)) for o, w in zip(off[a:b], bits[a:b])]})
+    return out
+
+
+def _store_arrays(indices, byte_offsets):
+    """indices: per stream its blocks [(bit offset, bits)] (or the dict that holds them, or None for a stream without an index);
+    byte_offsets: None, or per stream None / its table -> (indexFirst, blockBitOff, blockBits, tableFirst or None, blockByteOff or None)"""
+    blocks = [[] if i is None else (i.get("blocks", []) if isinstance(i, dict) else list(i)) for i in indices]
+    first = np.zeros(len(blocks) + 1, dtype=np.int64)
+    first[1:] = np.cumsum([len(b) for b in blocks])
+    off = np.ascontiguousarray([b[0] for bl in blocks for b in bl], dtype=np.int64)
+    w = np.ascontiguousarray([b[1] for bl in blocks for b in bl], dtype=np.int64)
+    if byte_offsets is None or all(t is None for t in byte_offsets):
+        return first, off, w, None, None
+    if len(byte_offsets) != len(blocks):
+        raise ValueError("byte_offsets needs one entry per stream")
+    tfirst, tab = np.full(len(blocks), -1, dtype=np.int64), []
+    for s, t in enumerate(byte_offsets):
+        if t is None:
+            continue
+        if len(t) != len(blocks[s]) + 1:
+            raise ValueError("byte_offsets[%d] needs one entry more than the stream has blocks" % s)
+        tfirst[s] = len(tab)
+        tab += [int(x) for x in t]
+    return first, off, w, tfirst, np.ascontiguousarray(tab, dtype=np.int64)
+
+
+def read_bytes_many_device(ctx, src, src_off, src_len, indices, streams, offsets, sizes, dst, cap, byte_offsets=None):
+    """kz_read_bytes_many_device: range i = bytes [offsets[i], offsets[i] + sizes[i]) of the original data of stream streams[i]
+    (stream s = the src_len[s] bytes at device address src + src_off[s]); it goes to device address dst + sum(sizes[:i]) (capacity
+    `cap` >= sum(sizes)).  indices: per stream its index as knz_index_many_device returns it (or its "blocks"); byte_offsets: None, or
+    per stream None / its table of block starts -> (got, stream status), lists of ints."""
+    so = np.ascontiguousarray(src_off, dtype=np.int64)
+    sl = np.ascontiguousarray(src_len, dtype=np.int64)
+    if not len(so) == len(sl) == len(indices):
+        raise ValueError("src_off, src_len and indices must have one length")
+    first, off, w, tfirst, tab = _store_arrays(indices, byte_offsets)
+    rs = np.ascontiguousarray(streams, dtype=np.int32)
+    ro = np.ascontiguousarray(offsets, dtype=np.int64)
+    rl = np.ascontiguousarray(sizes, dtype=np.int64)
+    if not len(rs) == len(ro) == len(rl):
+        raise ValueError("streams, offsets and sizes differ in length")
+    got, status = np.zeros(max(len(ro), 1), dtype=np.int64), np.zeros(max(len(so), 1), dtype=np.int32)
+    ctx.check(ctx.lib.kz_read_bytes_many_device(ctx.h, _ptr(src), _arg(so), _arg(sl), len(so), first.ctypes.data, _arg(off), _arg(w),
+                                                None if tfirst is None else tfirst.ctypes.data, None if tab is None else _arg(tab),
+                                                _arg(rs), _arg(ro), _arg(rl), len(ro), _ptr(dst), int(cap), got.ctypes.data, status.ctypes.data))
+    return [int(g) for g in got[:len(ro)]], [int(c) for c in status[:len(so)]]
+
+
+class KnzStore:
+    """Many .knz streams in one torch.uint8 device tensor (what compress_many_device leaves behind), read by byte address: the
+    indices of all streams come from ONE knz_index_many_device call, every read after that is one read_bytes_many_device call over
+    records of any of the streams.  byte_offsets: None, or per stream None / its table of block starts (block_byte_offsets), for
+    streams with short blocks in the middle.  A stream that cannot be indexed is kept with its code (status[s] < 0) and fails the
+    reads that name it."""
+
+    def __init__(self, ctx, buf, src_off, src_len, byte_offsets=None):
+        import torch
+        self.ctx = ctx
+        self.src = _byte_view(buf)
+        self.src_off = [int(o) for o in src_off]
+        self.src_len = [int(n) for n in src_len]
+        if len(self.src_off) != len(self.src_len):
+            raise ValueError("src_off and src_len must have one length")
+        for o, n in zip(self.src_off, self.src_len):
+            if o < 0 or n < 0 or o + n > self.src.numel():
+                raise ValueError("a stream lies outside the buffer")
+        self.byte_offsets = None if byte_offsets is None else [None if t is None else [int(b) for b in t] for t in byte_offsets]
+        torch.cuda.current_stream(self.src.device).synchronize()     # the calls run on the context's own stream
+        self.index = knz_index_many_device(ctx, self.src.data_ptr(), self.src_off, self.src_len)
+        self.status = [i["status"] for i in self.index]
+
+    @classmethod
+    def from_compress_many(cls, ctx, dst, dst_off, sizes, byte_offsets=None):
+        """the store of the streams that compress_many_device wrote into the tensor `dst`: its dst_off argument and its result"""
+        for s, n in enumerate(sizes):
+            if n < 0:
+                raise KanziError(-n, "KnzStore: stream %d was not written" % s)
+        return cls(ctx, dst, dst_off, sizes, byte_offsets)
+
+    def __len__(self):
+        return len(self.src_off)
+
+    def read_many(self, streams, offsets, sizes, out=None):
+        """bytes [offsets[i], offsets[i] + sizes[i]) of the original data of stream streams[i] for all i in one call -> (packed, got):
+        record i is packed[sum(sizes[:i]) :][:got[i]], cut at the end of its stream's data as a slice is.  out: a torch.uint8 device
+        tensor of at least sum(sizes) bytes to write into.  A record of a stream or a block that fails raises KanziError."""
+        import torch
+        streams, offsets, sizes = [int(s) for s in streams], [int(o) for o in offsets], [int(n) for n in sizes]
+        if not len(streams) == len(offsets) == len(sizes):
+            raise ValueError("streams, offsets and sizes differ in length")
+        if any(o < 0 for o in offsets) or any(n < 0 for n in sizes):
+            raise ValueError("offset and size must not be negative")
+        if any(not 0 <= s < len(self) for s in streams):
+            raise IndexError("stream out of range")
+        total = sum(sizes)
+        if out is None:
+            out = torch.empty(max(total, 1), dtype=torch.uint8, device=self.src.device)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < total or out.device != self.src.device:
+            raise ValueError("out must be a contiguous torch.uint8 tensor of sum(sizes) bytes on the store's device")
+        torch.cuda.current_stream(self.src.device).synchronize()
+        got, _ = read_bytes_many_device(self.ctx, self.src.data_ptr(), self.src_off, self.src_len, self.index, streams, offsets, sizes,
+                                        out.data_ptr(), total, self.byte_offsets)
+        for i, g in enumerate(got):
+            if g < 0:
+                raise KanziError(-g, "range %d (stream %d)" % (i, streams[i]))
+        return out[:total], got
+
+    def read(self, stream, off, size):
+        """bytes [off, off + size) of the original data of one stream -> a device tensor"""
+        out, got = self.read_many([stream], [off], [size])
+        return out[:got[0]]
 
 
 # ---- splice: a new .knz stream out of blocks of existing ones, without recoding (kz_knz_splice / kz_knz_splice_device) ----

@@ -6,6 +6,8 @@
 // where they are in their source streams, with the check of every piece against its own source in front of it (kz_knz_splice_device);
 // and the copy of the byte-addressed reads: many (range x block) segments of decoded rows to their places in one launch (k_knz_read),
 // with its mirror image for the byte-addressed writes: segments of new bytes into decoded rows (k_knz_write).
+// For the byte-addressed read of many streams (kz_read_bytes_many_device) the check of index entries has a form over rows of many
+// streams that also brings the block-header words (k_knz_check_rows).
 // Last, the scan (kz_knz_scan_device): the reader's acceptance test at every bit position of a stream and the link step over the
 // accepted positions (k_knz_scan_*), which finds a stream's blocks without the walk and behind damage.
 // The callers (kz_stream_device.hip: kz_compress_device / kz_decompress_device / kz_decompress_range_device / kz_decode_indexed_device /
@@ -251,6 +253,18 @@ __global__ void __launch_bounds__(256) k_knz_check_many(const u8* __restrict__ s
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= np) return;
   bad[i] = knz_entry_ok(src + pc[i].seg, pc[i].n, pc[i].hdrEnd, pc[i].off, pc[i].bits) ? 0 : 1;
+}
+// both at once for the index entries of many streams (kz_read_bytes_many_device): entry i is (t[i].off, t[i].bits) against its own
+// stream src[t[i].seg .. + t[i].n), whose header ends at bit t[i].hdrEnd.  bad[i] = 0 / 1 by the same rule, hdr[i] = the payload's
+// first 8 bytes, left aligned, as k_knz_check gives them (0 for a bad entry).  Nothing outside that segment is read.
+__global__ void __launch_bounds__(256) k_knz_check_rows(const u8* __restrict__ src, const KnzCheckRow* __restrict__ t, int nr, u64* __restrict__ hdr, int64_t* __restrict__ bad) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nr) return;
+  const KnzCheckRow r = t[i];
+  const u8* s = src + r.seg;
+  const bool ok = knz_entry_ok(s, r.n, r.hdrEnd, r.off, r.bits);
+  hdr[i] = ok ? knz_peek64(s, r.n, r.off) : 0;
+  bad[i] = ok ? 0 : 1;
 }
 
 // ---- unpack: container -> byte-aligned rows ------------------------------------------------------------------------------------
@@ -727,6 +741,12 @@ int kz_knz_unpack(kz_ctx* ctx, const uint8_t* d_src, int64_t n, const int64_t* d
 int kz_knz_check_many(kz_ctx* ctx, const uint8_t* d_src, const KnzPiece* d_pc, int np, int32_t* d_bad) {
   if (np <= 0) return 0;
   KZ_LAUNCH(ctx, KID_KNZ_CHECK_MANY, k_knz_check_many, dim3((np + 255) / 256), dim3(256), d_src, d_pc, np, d_bad);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_check_rows(kz_ctx* ctx, const uint8_t* d_src, const KnzCheckRow* d_t, int nr, uint64_t* d_hdr, int64_t* d_bad) {
+  if (nr <= 0) return 0;
+  KZ_LAUNCH(ctx, KID_KNZ_CHECK_ROWS, k_knz_check_rows, dim3((nr + 255) / 256), dim3(256), d_src, d_t, nr, (u64*)d_hdr, d_bad);
   KZ_HIP(hipGetLastError());
   return 0;
 }

@@ -1,6 +1,6 @@
 // kz_knz_host.h -- the host-only core of the .knz container: bit I/O, the stream header, the chain of block length prefixes, the
-// block-header precheck and the check of an index entry, the scan's rule, link step and host loop, the plan of a splice and its host copy, the plan of a byte-addressed read
-// and that of a byte-addressed write, and the container's rules that every call must share, each written once.
+// block-header precheck and the check of an index entry, the scan's rule, link step and host loop, the plan of a splice and its host copy, the plan of a byte-addressed read,
+// the merged plan of such a read over many streams, and the plan of a byte-addressed write, and the container's rules that every call must share, each written once.
 // This is the part that parses untrusted input.  It needs no GPU and no HIP header, so that a plain C++ program can run it under
 // the sanitizers (tools/knz_host_check.cpp, tools/knz_scan_check.cpp, tools/knz_read_check.cpp, tools/knz_write_check.cpp); kz_stream.hip and kz_stream_device.hip are its users.
 // Layout: K/io/CompressedOutputStream.java (writeHeader :236-313, ordered block emission :1024-1035, end marker :483-493) and
@@ -552,6 +552,43 @@ template <class F> static inline void knz_cut_at_blocks(const int64_t* B, int32_
     at += len; left -= len;
   }
 }
+// The segments of one range: bytes [o, o + len) of data that ends at `end`, cut at block ends, for the destination from byte d on.
+// They go behind all (in dst order when the ranges come in dst order), the block of each behind blk.  A range of no bytes and one that
+// starts at or behind `end` has no segment.
+static inline void knz_read_cut(const int64_t* B, int32_t nIndex, int32_t blockSize, int64_t end, int64_t o, int64_t len, int64_t d, int32_t range,
+                                std::vector<KnzReadSeg>& all, std::vector<int32_t>& blk) {
+  const int64_t left = o < end ? std::min<int64_t>(len, end - o) : 0;
+  if (left <= 0) return;
+  knz_cut_at_blocks(B, blockSize, knz_block_of(B, nIndex, blockSize, o), o, left, [&](int64_t k, int64_t off, int64_t l) {
+    all.push_back(KnzReadSeg{d, 0, 0, (int32_t)off, (int32_t)l, range});
+    blk.push_back((int32_t)k);
+    d += l;
+  });
+}
+// The segments `all` (in dst order) split by chunk, stably: dst order stays inside every chunk.  place(i, c, slot): the chunk and the
+// row in it of segment i's block.  Fills segs, first[0 .. nChunks] and units[0 .. nChunks) as KnzReadPlan holds them.
+template <class F> static inline void knz_read_split(const std::vector<KnzReadSeg>& all, int64_t nChunks, int dstPhase, F place, std::vector<KnzReadSeg>& segs,
+                                                     std::vector<int64_t>& first, std::vector<int64_t>& units) {
+  first.assign((size_t)nChunks + 1, 0);
+  units.assign((size_t)nChunks, 0);
+  std::vector<int64_t> chunk(all.size());
+  std::vector<int32_t> slot(all.size());
+  for (size_t i = 0; i < all.size(); i++) {
+    place(i, chunk[i], slot[i]);
+    first[(size_t)chunk[i] + 1]++;
+  }
+  for (int64_t c = 0; c < nChunks; c++) first[(size_t)c + 1] += first[(size_t)c];
+  std::vector<int64_t> fill(first.begin(), first.end() - 1);
+  segs.resize(all.size());
+  for (size_t i = 0; i < all.size(); i++) {
+    const int64_t c = chunk[i];
+    KnzReadSeg s = all[i];
+    s.slot = slot[i];
+    s.unit0 = units[(size_t)c];
+    units[(size_t)c] += knz_read_units((dstPhase + s.dst) & 15, s.len);
+    segs[(size_t)fill[(size_t)c]++] = s;
+  }
+}
 // The plan.  The arguments have passed knz_read_args and knz_read_table; CH >= 1 = blocks per chunk; dstPhase = dst's address mod
 // 16 (the host form passes 0: unit0 is the kernel's).  Ranges of no bytes and ranges that start at or behind P.end have no segment.
 static inline void knz_read_plan(const int64_t* B, int32_t nIndex, int32_t blockSize, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges,
@@ -562,54 +599,122 @@ static inline void knz_read_plan(const int64_t* B, int32_t nIndex, int32_t block
   std::vector<int32_t> blk;                                        // the block of all[i]
   int64_t D = 0;
   for (int32_t i = 0; i < nRanges; i++) {
-    const int64_t o = rangeOff[i];
-    const int64_t left = o < P.end ? std::min<int64_t>(rangeLen[i], P.end - o) : 0;
-    int64_t d = D;
+    knz_read_cut(B, nIndex, blockSize, P.end, rangeOff[i], rangeLen[i], D, i, all, blk);
     D += rangeLen[i];                                              // (<= dstCap: knz_read_total)
-    if (left <= 0) continue;
-    knz_cut_at_blocks(B, blockSize, knz_block_of(B, nIndex, blockSize, o), o, left, [&](int64_t k, int64_t off, int64_t len) {
-      all.push_back(KnzReadSeg{d, 0, 0, (int32_t)off, (int32_t)len, i});
-      blk.push_back((int32_t)k);
-      d += len;
-    });
   }
   P.blocks = blk;
   std::sort(P.blocks.begin(), P.blocks.end());
   P.blocks.erase(std::unique(P.blocks.begin(), P.blocks.end()), P.blocks.end());
   const int64_t nChunks = ((int64_t)P.blocks.size() + CH - 1) / CH;
-  P.first.assign((size_t)nChunks + 1, 0);
-  P.units.assign((size_t)nChunks, 0);
-  std::vector<int32_t> rank(all.size());                           // the block's place among the distinct blocks
-  for (size_t i = 0; i < all.size(); i++) {
-    rank[i] = (int32_t)(std::lower_bound(P.blocks.begin(), P.blocks.end(), blk[i]) - P.blocks.begin());
-    P.first[(size_t)(rank[i] / CH) + 1]++;
-  }
-  for (int64_t c = 0; c < nChunks; c++) P.first[(size_t)c + 1] += P.first[(size_t)c];
-  std::vector<int64_t> fill(P.first.begin(), P.first.end() - 1);
-  P.segs.resize(all.size());
-  for (size_t i = 0; i < all.size(); i++) {                        // a stable split by chunk: dst order stays inside every chunk
-    const int64_t c = rank[i] / CH;
-    KnzReadSeg s = all[i];
-    s.slot = rank[i] % CH;
-    s.unit0 = P.units[(size_t)c];
-    P.units[(size_t)c] += knz_read_units((dstPhase + s.dst) & 15, s.len);
-    P.segs[(size_t)fill[(size_t)c]++] = s;
-  }
+  knz_read_split(all, nChunks, dstPhase, [&](size_t i, int64_t& c, int32_t& slot) {
+    const int32_t rank = (int32_t)(std::lower_bound(P.blocks.begin(), P.blocks.end(), blk[i]) - P.blocks.begin());   // the block's place among the distinct blocks
+    c = rank / CH; slot = rank % CH;
+  }, P.segs, P.first, P.units);
 }
-// After chunk c has been decoded (res[j]: the result of its block j, rows of blockSize bytes): the length check of every block, the
-// segments cut to what their blocks hold (a failed block's to nothing; unit0 stays, the kernel skips the units that fall away), and
-// got[]: the bytes delivered, or the status of the first failing block a range touches, in block order.  got[] starts as zeros.
-static inline void knz_read_settle(KnzReadPlan& P, int64_t c, int CH, const int64_t* B, int32_t nIndex, int32_t blockSize, kz_block_result* res, int64_t* got) {
-  const int64_t b0 = c * CH, cnt = std::min<int64_t>(CH, (int64_t)P.blocks.size() - b0);
+// After cnt rows have been decoded (res[j]: the result of block blk[j] of a stream whose table is B): the length check of every block.
+static inline void knz_read_settle_blocks(const int32_t* blk, int64_t cnt, const int64_t* B, int32_t nIndex, int32_t blockSize, kz_block_result* res) {
   for (int64_t j = 0; j < cnt; j++)
-    if (!res[j].status) res[j].status = knz_block_len_check(B, nIndex, blockSize, P.blocks[(size_t)(b0 + j)], res[j].length);
-  for (int64_t i = P.first[(size_t)c]; i < P.first[(size_t)c + 1]; i++) {
-    KnzReadSeg& s = P.segs[(size_t)i];
+    if (!res[j].status) res[j].status = knz_block_len_check(B, nIndex, blockSize, blk[j], res[j].length);
+}
+// Behind it, the segments segs[s0 .. s1) of those rows (res[slot]) cut to what their blocks hold (a failed block's to nothing; unit0
+// stays, the kernel skips the units that fall away), and got[]: the bytes delivered, or the status of the first failing block a range
+// touches, in block order.
+static inline void knz_read_settle_segs(KnzReadSeg* segs, int64_t s0, int64_t s1, const kz_block_result* res, int64_t* got) {
+  for (int64_t i = s0; i < s1; i++) {
+    KnzReadSeg& s = segs[i];
     const kz_block_result& r = res[s.slot];
     s.len = r.status ? 0 : (int32_t)std::max<int64_t>(0, std::min<int64_t>(s.len, (int64_t)r.length - s.off));
     if (got[s.range] < 0) continue;
     if (r.status) got[s.range] = r.status; else got[s.range] += s.len;
   }
+}
+// After chunk c has been decoded (res[j]: the result of its block j, rows of blockSize bytes): both steps.  got[] starts as zeros.
+static inline void knz_read_settle(KnzReadPlan& P, int64_t c, int CH, const int64_t* B, int32_t nIndex, int32_t blockSize, kz_block_result* res, int64_t* got) {
+  const int64_t b0 = c * CH, cnt = std::min<int64_t>(CH, (int64_t)P.blocks.size() - b0);
+  knz_read_settle_blocks(&P.blocks[(size_t)b0], cnt, B, nIndex, blockSize, res);
+  knz_read_settle_segs(P.segs.data(), P.first[(size_t)c], P.first[(size_t)c + 1], res, got);
+}
+
+// ---- byte-addressed reads of many streams in one call (kz_read_bytes_many_device) ----
+// Stream s is src[srcOff[s] .. + srcLen[s]) with the index entries [indexFirst[s], indexFirst[s + 1]) of blockBitOff / blockBits and,
+// where tableFirst[s] >= 0, the table of block starts blockByteOff[tableFirst[s] ..] (its index length + 1 entries); range i asks
+// stream rangeStream[i].  The arguments of the call, checked before anything else happens.
+static inline int knz_many_src_args(const void* src, const int64_t* srcOff, const int64_t* srcLen, int32_t nStreams) {
+  if (nStreams < 0 || (nStreams > 0 && (!src || !srcOff || !srcLen))) return -KZ_ERR_INVALID_PARAM;
+  for (int32_t s = 0; s < nStreams; s++) if (srcOff[s] < 0 || srcLen[s] < 0) return -KZ_ERR_INVALID_PARAM;
+  return 0;
+}
+static inline int knz_read_many_args(const void* src, const int64_t* srcOff, const int64_t* srcLen, int32_t nStreams, const int64_t* indexFirst,
+                                     const int64_t* blockBitOff, const int64_t* blockBits, const int64_t* tableFirst, const int64_t* blockByteOff,
+                                     const int32_t* rangeStream, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges, const void* dst, int64_t dstCap,
+                                     const int64_t* got) {
+  if (nRanges < 0 || dstCap < 0) return -KZ_ERR_INVALID_PARAM;
+  { const int rc = knz_many_src_args(src, srcOff, srcLen, nStreams); if (rc) return rc; }
+  if (nStreams > 0) {
+    if (!indexFirst || indexFirst[0] < 0) return -KZ_ERR_INVALID_PARAM;
+    for (int32_t s = 0; s < nStreams; s++)                         // ascending, and a stream's index has an int32 length as in the single call
+      if (indexFirst[s + 1] < indexFirst[s] || indexFirst[s + 1] - indexFirst[s] > 0x7FFFFFFF) return -KZ_ERR_INVALID_PARAM;
+    if (indexFirst[nStreams] > 0 && (!blockBitOff || !blockBits)) return -KZ_ERR_INVALID_PARAM;
+    if (tableFirst)
+      for (int32_t s = 0; s < nStreams; s++) if (tableFirst[s] < -1 || (tableFirst[s] >= 0 && !blockByteOff)) return -KZ_ERR_INVALID_PARAM;
+  }
+  if (nRanges > 0 && (!rangeStream || !rangeOff || !rangeLen || !dst || !got)) return -KZ_ERR_INVALID_PARAM;
+  for (int32_t i = 0; i < nRanges; i++)
+    if (rangeStream[i] < 0 || rangeStream[i] >= nStreams || rangeOff[i] < 0 || rangeLen[i] < 0) return -KZ_ERR_INVALID_PARAM;
+  return 0;
+}
+// What the plan needs to know of a stream: whether its ranges are read at all (a stream that no range names, or one with a fault of
+// its own, is not), its header group (the streams with equal transform word, entropy id, block size and checksum kind, numbered in
+// order of first appearance), its index length and block size, and its table of block starts (null: none).
+struct KnzManyStreamIn { bool use; int32_t group; int32_t nIndex, blockSize; const int64_t* B; };
+// The merged plan of the call: the distinct covering blocks of all streams that are read in one list of rows ordered by header group,
+// then stream, then block; the rows cut into chunks, each inside one group and of at most that group's chunk size (chunkBlocks[g]
+// >= 1); the range x block segments grouped by chunk as in KnzReadPlan, slot = the row's place in its chunk, dst = the range's place in
+// the destination of the whole call (D[i] = the running sum of all requested lengths in call order).
+struct KnzManyReadPlan {
+  std::vector<int32_t> rowStream, rowBlock;   // the merged list
+  std::vector<int64_t> chunkRow;              // chunk c = rows [chunkRow[c], chunkRow[c + 1])
+  std::vector<int32_t> chunkGroup;            // its header group
+  std::vector<KnzReadSeg> segs;               // chunk by chunk; inside a chunk by dst
+  std::vector<int64_t> first;                 // chunk c owns segs[first[c] .. first[c + 1])
+  std::vector<int64_t> units;                 // units[c] = the destination units of chunk c
+};
+static inline void knz_read_many_plan(const KnzManyStreamIn* st, int32_t nStreams, const int32_t* rangeStream, const int64_t* rangeOff, const int64_t* rangeLen,
+                                      int32_t nRanges, const int* chunkBlocks, int dstPhase, KnzManyReadPlan& P) {
+  (void)nStreams;
+  P.rowStream.clear(); P.rowBlock.clear(); P.chunkGroup.clear();
+  std::vector<KnzReadSeg> all;                                     // in range order: by dst
+  std::vector<int32_t> blk, str;                                  // the block and the stream of all[i]
+  int64_t D = 0;
+  for (int32_t i = 0; i < nRanges; i++) {
+    const int32_t s = rangeStream[i];
+    const KnzManyStreamIn& S = st[s];
+    if (S.use) {
+      const int64_t end = S.B ? S.B[S.nIndex] : (int64_t)S.nIndex * S.blockSize;
+      knz_read_cut(S.B, S.nIndex, S.blockSize, end, rangeOff[i], rangeLen[i], D, i, all, blk);
+      str.resize(blk.size(), s);
+    }
+    D += rangeLen[i];                                              // (<= dstCap: knz_read_total)
+  }
+  struct Key { int32_t g, s, k; };
+  auto less = [](const Key& a, const Key& b) { return a.g != b.g ? a.g < b.g : (a.s != b.s ? a.s < b.s : a.k < b.k); };
+  std::vector<Key> rows(all.size());
+  for (size_t i = 0; i < all.size(); i++) rows[i] = Key{st[str[i]].group, str[i], blk[i]};
+  std::sort(rows.begin(), rows.end(), less);
+  rows.erase(std::unique(rows.begin(), rows.end(), [](const Key& a, const Key& b) { return a.g == b.g && a.s == b.s && a.k == b.k; }), rows.end());
+  std::vector<int64_t> rowChunk(rows.size());
+  P.chunkRow.clear();
+  for (size_t r = 0; r < rows.size(); r++) {
+    P.rowStream.push_back(rows[r].s); P.rowBlock.push_back(rows[r].k);
+    const bool open = !P.chunkGroup.empty() && P.chunkGroup.back() == rows[r].g && (int64_t)r - P.chunkRow.back() < chunkBlocks[rows[r].g];
+    if (!open) { P.chunkRow.push_back((int64_t)r); P.chunkGroup.push_back(rows[r].g); }   // (a chunk never holds rows of two groups)
+    rowChunk[r] = (int64_t)P.chunkGroup.size() - 1;
+  }
+  P.chunkRow.push_back((int64_t)rows.size());
+  knz_read_split(all, (int64_t)P.chunkGroup.size(), dstPhase, [&](size_t i, int64_t& c, int32_t& slot) {
+    const size_t r = (size_t)(std::lower_bound(rows.begin(), rows.end(), Key{st[str[i]].group, str[i], blk[i]}, less) - rows.begin());
+    c = rowChunk[r]; slot = (int32_t)((int64_t)r - P.chunkRow[(size_t)c]);
+  }, P.segs, P.first, P.units);
 }
 
 // ---- byte-addressed writes: many ranges of the original data replaced in one call (kz_write_bytes / kz_write_bytes_device) ----

@@ -1,6 +1,7 @@
 // kz_stream_device.hip -- the .knz container with source and destination in HBM: the same streams as kz_stream.hip's calls write and
 // read, whole, by block range, by index, and many at a time, edits them without recoding (the splice), and reads and rewrites byte
-// ranges of their data (kz_read_bytes_device, kz_write_bytes_device).  The kernels are in kz_knz_gpu.hip; what stays on the host is what
+// ranges of their data (kz_read_bytes_device, kz_write_bytes_device), and indexes and reads many of them in one call
+// (kz_knz_index_many_device, kz_read_bytes_many_device).  The kernels are in kz_knz_gpu.hip; what stays on the host is what
 // kz_compress / kz_decompress do there as well and costs nothing: the stream header (kz_knz_host.h, on a copy of at most 26 bytes),
 // the bit-offset arithmetic over results[] (host arrays anyway), and the block checks on the 8 header bytes per block that the walk
 // kernel brings back.  The rules shared with the host-buffer calls are in kz_knz_host.h and kz_knz_stream.h.
@@ -722,6 +723,117 @@ extern "C" int32_t kz_decompress_many_device(kz_ctx* ctx, const uint8_t* d_src, 
   return flush();
 }
 
+namespace {
+// the first bytes of the streams ids[0 .. nn) of a many-stream call in one table, one copy (k_knz_heads): stream ids[k]'s 32 bytes are
+// at knzPin + tBytes + 32 k when the call returns, behind the nn KnzSrc entries (tBytes = those, in whole 64 bytes), which stay the caller's
+int knz_many_heads(kz_ctx* ctx, const uint8_t* d_src, const int64_t* srcOff, const int64_t* srcLen, const int32_t* ids, int nn, size_t tBytes) {
+  KnzSrc* t = (KnzSrc*)ctx->knzPin.p;
+  for (int k = 0; k < nn; k++) t[k] = KnzSrc{srcOff[ids[k]], srcLen[ids[k]], 0, 0, 0, 0};
+  KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, t, (size_t)nn * sizeof(KnzSrc), hipMemcpyHostToDevice, ctx->stream));
+  { const int rc = kz_knz_heads(ctx, d_src, (const KnzSrc*)ctx->knzAux.p, nn, ctx->knzAux.p + tBytes); if (rc) return rc; }
+  KZ_HIP(hipMemcpyAsync(ctx->knzPin.p + tBytes, ctx->knzAux.p + tBytes, (size_t)nn * 32, hipMemcpyDeviceToHost, ctx->stream));
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  return 0;
+}
+// The faults of single streams of a many-stream reading call: code[s], and the text of the first failing stream in stream order,
+// whichever step of the call finds it.
+struct KnzStreamFaults {
+  std::vector<int> code; int first; char text[256];
+  explicit KnzStreamFaults(int ns) : code((size_t)ns, 0), first(-1) { text[0] = 0; }
+  void fail(int s, int c, const char* call, const char* why) {
+    code[(size_t)s] = c;
+    if (first >= 0 && first < s) return;
+    first = s;
+    snprintf(text, sizeof(text), "%s: stream %d: %s (%d)", call, s, why, c);
+  }
+  void tell(kz_ctx* ctx) const { if (first >= 0) snprintf(ctx->err, sizeof(ctx->err), "%s", text); }
+};
+}  // namespace
+
+// kz_knz_index_device for N streams: the heads in one copy (k_knz_heads) and the host's header parse, then decompress_group's two walk
+// passes with a lane per stream (k_knz_walk_many): the count pass, and the fill pass with the exclusive scan of the counts as the base.
+// Three launches and three waits whatever nStreams is.  Of a call whose cap is below the total only the entries below cap are filled.
+extern "C" int64_t kz_knz_index_many_device(kz_ctx* ctx, const uint8_t* d_src, const int64_t* srcOff, const int64_t* srcLen, int32_t nStreams,
+                                            uint64_t* transformType, uint32_t* entropyType, int32_t* blockSize, int64_t* inputSize, int32_t* checksumBits,
+                                            int32_t* status, int64_t* indexFirst, int64_t* blockBitOff, int64_t* blockBits, int64_t cap) {
+  if (!ctx) return -KZ_ERR_INVALID_PARAM;
+  { const int rc = knz_many_src_args(d_src, srcOff, srcLen, nStreams); if (rc) return rc; }
+  if (nStreams == 0) return 0;
+  if (!status || !indexFirst || cap < 0 || (cap > 0 && (!blockBitOff || !blockBits))) return -KZ_ERR_INVALID_PARAM;
+  KZ_HIP(hipSetDevice(ctx->device));
+  const int ns = nStreams;
+  const char* call = "kz_knz_index_many_device";
+  const int maxBlocks = 0x7FFFFFFF - 16384;                        // kz_knz_index_device's bound on a stream's blocks
+  KnzStreamFaults F(ns);
+  const size_t tBytes = kz_align((size_t)ns * sizeof(KnzSrc), 64);
+  { const int rc = knz_tables(ctx, tBytes + (size_t)ns * 32); if (rc) return rc; }
+  std::vector<int32_t> ids((size_t)ns);
+  for (int s = 0; s < ns; s++) ids[(size_t)s] = s;
+  { const int rc = knz_many_heads(ctx, d_src, srcOff, srcLen, ids.data(), ns, tBytes); if (rc) return rc; }
+  KnzSrc* t = (KnzSrc*)ctx->knzPin.p;
+  for (int s = 0; s < ns; s++) {
+    t[s].maxCount = 0;                                             // (a stream with a fault is not walked)
+    if (srcLen[s] < 20) { F.fail(s, -KZ_ERR_INVALID_FILE, call, "shorter than a stream header"); continue; }
+    HostBitsIn bs{ctx->knzPin.p + tBytes + (size_t)s * 32, (uint64_t)std::min<int64_t>(srcLen[s], 26) * 8, 0, false};
+    KnzHeader h;
+    char why[96] = "";
+    const int hrc = read_stream_header(bs, h, why, sizeof(why));
+    if (hrc) { F.fail(s, hrc, call, why[0] ? why : "not a stream header"); continue; }
+    knz_header_out(h, transformType ? transformType + s : nullptr, entropyType ? entropyType + s : nullptr, blockSize ? blockSize + s : nullptr,
+                   inputSize ? inputSize + s : nullptr, checksumBits ? checksumBits + s : nullptr);
+    t[s].startBit = (int64_t)bs.pos; t[s].maxCount = maxBlocks;
+  }
+  // ---- count pass (cap = 0: res only) ----
+  const KnzSrc* d_t = (const KnzSrc*)ctx->knzAux.p;
+  KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, t, (size_t)ns * sizeof(KnzSrc), hipMemcpyHostToDevice, ctx->stream));
+  { const int rc = kz_knz_walk_many(ctx, d_src, d_t, ns, nullptr, nullptr, nullptr, (int64_t*)(ctx->knzAux.p + tBytes)); if (rc) return rc; }
+  KZ_HIP(hipMemcpyAsync(ctx->knzPin.p + tBytes, ctx->knzAux.p + tBytes, (size_t)ns * 24, hipMemcpyDeviceToHost, ctx->stream));
+  KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+  kz_ktimer_flush(ctx);
+  int64_t E = 0;
+  {
+    const int64_t* res = (const int64_t*)(ctx->knzPin.p + tBytes);
+    for (int s = 0; s < ns; s++) {
+      indexFirst[s] = E;
+      if (F.code[(size_t)s]) { status[s] = F.code[(size_t)s]; continue; }
+      const int64_t cnt = res[3 * s], why = res[3 * s + 2];
+      if (cnt < 0 || cnt > maxBlocks) { snprintf(ctx->err, sizeof(ctx->err), "knz walk: bad count"); return -KZ_ERR_DEVICE; }
+      if (why == KNZ_WALK_PREFIX || why == KNZ_WALK_PAYLOAD) F.fail(s, -KZ_ERR_READ_FILE, call, "a block does not fit in the stream");
+      else if (why != KNZ_WALK_END) F.fail(s, -KZ_ERR_INVALID_FILE, call, "too many blocks");
+      status[s] = F.code[(size_t)s] ? F.code[(size_t)s] : (int32_t)cnt;
+      if (!F.code[(size_t)s]) E += cnt;
+    }
+    indexFirst[ns] = E;
+  }
+  // ---- fill pass: stream s's entries from index indexFirst[s] on, those below cap ----
+  const int64_t M = std::min(E, cap);
+  if (M > 0) {
+    std::vector<KnzSrc> keep(t, t + ns);                           // (the tables may move when they grow)
+    const size_t outBytes = (size_t)ns * 24 + (size_t)M * 24;
+    { const int rc = knz_tables(ctx, tBytes + outBytes); if (rc) return rc; }
+    t = (KnzSrc*)ctx->knzPin.p;
+    for (int s = 0; s < ns; s++) {
+      t[s] = keep[(size_t)s];
+      t[s].base = indexFirst[s];
+      t[s].maxCount = status[s] > 0 ? status[s] : 0;
+      t[s].cap = (int32_t)std::max<int64_t>(0, std::min<int64_t>(t[s].maxCount, M - indexFirst[s]));
+    }
+    const KnzTable T(ctx, M, tBytes, (size_t)ns * 24);             // behind the KnzSrc entries: res[3 ns], then off[M], bits[M], hdr[M]
+    KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, t, (size_t)ns * sizeof(KnzSrc), hipMemcpyHostToDevice, ctx->stream));
+    { const int rc = kz_knz_walk_many(ctx, d_src, (const KnzSrc*)ctx->knzAux.p, ns, T.d_off(), T.d_bits(), T.d_hdr(), T.d_head()); if (rc) return rc; }
+    KZ_HIP(hipMemcpyAsync(T.pin, T.dev, T.bytes(2), hipMemcpyDeviceToHost, ctx->stream));
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));
+    kz_ktimer_flush(ctx);
+    for (int s = 0; s < ns; s++)                                   // the same streams, walked twice: the same counts
+      if (status[s] > 0 && T.head()[3 * s] != status[s]) { snprintf(ctx->err, sizeof(ctx->err), "knz walk: the fill pass counts other blocks than the count pass"); return -KZ_ERR_DEVICE; }
+    memcpy(blockBitOff, T.off(), (size_t)M * 8);
+    memcpy(blockBits, T.bits(), (size_t)M * 8);
+  }
+  F.tell(ctx);
+  return E;
+}
+
 
 // =================================================================================================
 // indexed reads: blocks of a stream by their (bit offset, bit length) pairs, as kz_knz_index / kz_knz_index_device return them, in
@@ -764,27 +876,39 @@ template <class F> int knz_check_entries(kz_ctx* ctx, const KnzTable& T, const u
 // unpack of the entries that pass into staging rows (ctx->devIn[0], P.iS apart), their decode into rows `stride` apart at d_out.  An
 // entry with leftOut[i] (may be null) is not looked at: its res[i] is the caller's, with a status that is not 0.  A chunk in which
 // nothing passes launches nothing.
-int knz_chunk_decode(kz_ctx* ctx, const KnzTable& T, const uint8_t* d_src, int64_t n, const KnzPlan& P, const int64_t* off, const int64_t* W, const uint64_t* hdrs,
-                     const uint8_t* leftOut, int cnt, uint8_t* d_out, int64_t stride, kz_block_result* res) {
+// The rows may come from one stream or from many of one header (P: what that header gives; its hdrEnd and its batch are not looked
+// at): bytesOf(i) = the bytes of row i's stream, put(i, off, bits) enters the row in the caller's pinned table (bits == 0: a row of
+// no bits, nothing of it is unpacked), unpack(maxBytes) sends the table up and launches the unpack into ctx->devIn[0].
+template <class N, class E, class U>
+int knz_chunk_decode_rows(kz_ctx* ctx, const KnzPlan& P, N bytesOf, const int64_t* off, const int64_t* W, const uint64_t* hdrs, const uint8_t* leftOut, int cnt,
+                          E put, U unpack, uint8_t* d_out, int64_t stride, kz_block_result* res) {
   int64_t maxBytes = 0;
   for (int i = 0; i < cnt; i++) {
-    T.off()[i] = off[i];
-    T.bits()[i] = 0;                                                // a row of no bits: nothing of it is unpacked
-    if (leftOut && leftOut[i]) continue;
-    const int rc = knz_check_walked(hdrs[i], (uint64_t)W[i], (uint64_t)off[i], (uint64_t)n * 8, P);
+    if (leftOut && leftOut[i]) { put(i, off[i], (int64_t)0); continue; }
+    const int rc = knz_check_walked(hdrs[i], (uint64_t)W[i], (uint64_t)off[i], (uint64_t)bytesOf(i) * 8, P);
     memset(&res[i], 0, sizeof(res[i]));
     res[i].bits = W[i]; res[i].status = rc;
-    if (!rc) { T.bits()[i] = W[i]; maxBytes = std::max<int64_t>(maxBytes, (W[i] + 7) >> 3); }
+    put(i, off[i], rc ? (int64_t)0 : W[i]);
+    if (!rc) maxBytes = std::max<int64_t>(maxBytes, (W[i] + 7) >> 3);
   }
   if (maxBytes == 0) return 0;
-  KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-  KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
   { const int rc = kz_stage_reserve(ctx, ctx->devIn[0], (size_t)cnt * P.iS, false); if (rc) return rc; }
-  { const int rc = kz_knz_unpack(ctx, d_src, n, T.d_off(), T.d_bits(), cnt, maxBytes, ctx->devIn[0].p, P.iS); if (rc) return rc; }
+  { const int rc = unpack(maxBytes); if (rc) return rc; }
   { const int rc = indexed_decode_runs(ctx, P, ctx->devIn[0].p, W, cnt, d_out, stride, res, KZ_MEM_DEVICE); if (rc) return rc; }
   KZ_HIP(kz_stream_sync(ctx, ctx->stream));                        // the pinned table is the caller's again
   kz_ktimer_flush(ctx);
   return 0;
+}
+// the rows of one stream d_src[0 .. n): the table is T's (off, bits) columns, the unpack k_knz_unpack
+int knz_chunk_decode(kz_ctx* ctx, const KnzTable& T, const uint8_t* d_src, int64_t n, const KnzPlan& P, const int64_t* off, const int64_t* W, const uint64_t* hdrs,
+                     const uint8_t* leftOut, int cnt, uint8_t* d_out, int64_t stride, kz_block_result* res) {
+  return knz_chunk_decode_rows(ctx, P, [&](int) { return n; }, off, W, hdrs, leftOut, cnt,
+    [&](int i, int64_t o, int64_t bits) { T.off()[i] = o; T.bits()[i] = bits; },
+    [&](int64_t maxBytes) -> int {
+      KZ_HIP(hipMemcpyAsync(T.d_off(), T.off(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+      KZ_HIP(hipMemcpyAsync(T.d_bits(), T.bits(), (size_t)cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+      return kz_knz_unpack(ctx, d_src, n, T.d_off(), T.d_bits(), cnt, maxBytes, ctx->devIn[0].p, P.iS);
+    }, d_out, stride, res);
 }
 }  // namespace
 
@@ -956,6 +1080,187 @@ extern "C" int64_t kz_read_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int64
       kz_ktimer_flush(ctx);
     }
   }
+  return total;
+}
+
+// kz_read_bytes_device for ranges of N streams in one call.  The open is the many-stream decoder's (k_knz_heads over the streams that
+// some range names, one copy, parsed here); the plan is the merged one (kz_knz_host.h: every stream's distinct covering blocks in one
+// list of rows by header group, stream and block, cut into chunks inside a group); every used entry is checked against its own stream
+// (k_knz_check_rows, which brings the block-header words); a chunk is the indexed calls' decode step over rows of many streams
+// (k_knz_unpack_many), the per-stream settle and the read's own copy launch.  A fault that ends the single-stream call ends only its
+// stream here: the stream leaves the plan, and the others are planned as if it were not there.
+namespace {
+const int KNZ_CHECK_LAUNCH = 1 << 18;                              // entries per k_knz_check_rows launch: bounds its table at 14 MiB
+}
+extern "C" int64_t kz_read_bytes_many_device(kz_ctx* ctx, const uint8_t* d_src, const int64_t* srcOff, const int64_t* srcLen, int32_t nStreams,
+                                             const int64_t* indexFirst, const int64_t* blockBitOff, const int64_t* blockBits,
+                                             const int64_t* tableFirst, const int64_t* blockByteOff,
+                                             const int32_t* rangeStream, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges,
+                                             uint8_t* d_dst, int64_t dstCap, int64_t* got, int32_t* streamStatus) {
+  if (!ctx) return -KZ_ERR_INVALID_PARAM;
+  {
+    const int rc = knz_read_many_args(d_src, srcOff, srcLen, nStreams, indexFirst, blockBitOff, blockBits, tableFirst, blockByteOff, rangeStream, rangeOff, rangeLen,
+                                      nRanges, d_dst, dstCap, got);
+    if (rc) return rc;
+  }
+  const char* call = "kz_read_bytes_many_device";
+  const int64_t total = knz_read_total(rangeLen, nRanges, dstCap);
+  if (total < 0) { snprintf(ctx->err, sizeof(ctx->err), "%s: destination too small", call); return total; }
+  if (streamStatus) for (int s = 0; s < nStreams; s++) streamStatus[s] = 0;
+  if (nRanges == 0) return 0;
+  KZ_HIP(hipSetDevice(ctx->device));
+  const int ns = nStreams;
+  // ---- the streams that some range names, ascending; their heads in one copy; per stream the single call's open and table check ----
+  std::vector<int32_t> ids;
+  {
+    std::vector<uint8_t> named((size_t)ns, 0);
+    for (int32_t i = 0; i < nRanges; i++) named[(size_t)rangeStream[i]] = 1;
+    for (int s = 0; s < ns; s++) if (named[(size_t)s]) ids.push_back(s);
+  }
+  const int nn = (int)ids.size();
+  KnzStreamFaults F(ns);
+  std::vector<KnzManyStreamIn> st((size_t)ns, KnzManyStreamIn{false, -1, 0, 0, nullptr});
+  std::vector<KnzPlan> plan((size_t)ns);
+  {
+    const size_t tBytes = kz_align((size_t)nn * sizeof(KnzSrc), 64);
+    { const int rc = knz_tables(ctx, tBytes + (size_t)nn * 32); if (rc) return rc; }
+    { const int rc = knz_many_heads(ctx, d_src, srcOff, srcLen, ids.data(), nn, tBytes); if (rc) return rc; }
+    for (int k = 0; k < nn; k++) {
+      const int s = ids[(size_t)k];
+      HostBitsIn bs{ctx->knzPin.p + tBytes + (size_t)k * 32, (uint64_t)std::min<int64_t>(srcLen[s], 26) * 8, 0, false};
+      KnzHeader h;
+      char why[96] = "";
+      const int hrc = read_stream_header(bs, h, why, sizeof(why));
+      if (hrc) { F.fail(s, hrc, call, why[0] ? why : "not a stream header"); continue; }
+      plan[(size_t)s] = knz_plan(ctx, h, srcLen[s], (int64_t)bs.pos);
+      KnzManyStreamIn& S = st[(size_t)s];
+      S.nIndex = (int32_t)(indexFirst[s + 1] - indexFirst[s]);
+      S.blockSize = h.blockSize;
+      S.B = (tableFirst && tableFirst[s] >= 0) ? blockByteOff + tableFirst[s] : nullptr;
+      if (knz_read_table(S.B, S.nIndex, S.blockSize)) { F.fail(s, -KZ_ERR_INVALID_PARAM, call, "blockByteOff is not a table of block starts"); continue; }
+      S.use = true;
+    }
+  }
+  KnzManyReadPlan R;
+  std::vector<KnzPlan> groups;                                     // a group's plan: its first stream's (the header's four fields, the staging row)
+  std::vector<int> chunkBlocks;
+  std::vector<uint64_t> hdrs;
+  // ---- the plan, and every entry it uses against its own stream before anything is unpacked.  A stream with an entry that does not
+  //      match leaves the plan, which is then made again without it (and checked again: the rows have other places) ----
+  for (;;) {
+    groups.clear(); chunkBlocks.clear();
+    for (int k = 0; k < nn; k++) {
+      const int s = ids[(size_t)k];
+      if (!st[(size_t)s].use) continue;
+      const KnzHeader& h = plan[(size_t)s].h;
+      size_t g = 0;
+      for (; g < groups.size(); g++) if (groups[g].h.transformType == h.transformType && groups[g].h.entropyType == h.entropyType && groups[g].h.blockSize == h.blockSize && groups[g].h.chkKind == h.chkKind) break;
+      if (g == groups.size()) { groups.push_back(plan[(size_t)s]); chunkBlocks.push_back(knz_chunk_blocks(ctx, h.blockSize)); }
+      st[(size_t)s].group = (int32_t)g;
+    }
+    knz_read_many_plan(st.data(), ns, rangeStream, rangeOff, rangeLen, nRanges, chunkBlocks.data(), (int)((uintptr_t)d_dst & 15), R);
+    const int64_t nr = (int64_t)R.rowStream.size();
+    hdrs.assign((size_t)nr, 0);
+    const int CK = (int)std::min<int64_t>(KNZ_CHECK_LAUNCH, nr);
+    const size_t rowBytes = kz_align((size_t)CK * sizeof(KnzCheckRow), 64);
+    { const int rc = knz_tables(ctx, rowBytes + (size_t)CK * 16); if (rc) return rc; }
+    bool dropped = false;
+    for (int64_t r0 = 0; r0 < nr; r0 += CK) {
+      const int cnt = (int)std::min<int64_t>(CK, nr - r0);
+      KnzCheckRow* t = (KnzCheckRow*)ctx->knzPin.p;
+      for (int i = 0; i < cnt; i++) {
+        const int s = R.rowStream[(size_t)(r0 + i)];
+        const int64_t e = indexFirst[s] + R.rowBlock[(size_t)(r0 + i)];
+        t[i] = KnzCheckRow{srcOff[s], srcLen[s], blockBitOff[e], blockBits[e], plan[(size_t)s].hdrEnd};
+      }
+      uint64_t* d_hdr = (uint64_t*)(ctx->knzAux.p + rowBytes);
+      KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, t, (size_t)cnt * sizeof(KnzCheckRow), hipMemcpyHostToDevice, ctx->stream));
+      { const int rc = kz_knz_check_rows(ctx, d_src, (const KnzCheckRow*)ctx->knzAux.p, cnt, d_hdr, (int64_t*)(d_hdr + CK)); if (rc) return rc; }
+      KZ_HIP(hipMemcpyAsync(ctx->knzPin.p + rowBytes, ctx->knzAux.p + rowBytes, (size_t)CK * 8 + (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+      KZ_HIP(kz_stream_sync(ctx, ctx->stream));                    // the pinned table is the next launch's
+      kz_ktimer_flush(ctx);
+      const uint64_t* hw = (const uint64_t*)(ctx->knzPin.p + rowBytes);
+      const int64_t* bad = (const int64_t*)(hw + CK);
+      for (int i = 0; i < cnt; i++) {
+        const int s = R.rowStream[(size_t)(r0 + i)];
+        hdrs[(size_t)(r0 + i)] = hw[i];
+        if (!bad[i] || !st[(size_t)s].use) continue;               // (of a stream's bad entries the first in block order is named)
+        char why[96];
+        snprintf(why, sizeof(why), "index entry %d does not match the stream", (int)R.rowBlock[(size_t)(r0 + i)]);
+        F.fail(s, -KZ_ERR_INVALID_PARAM, call, why);
+        st[(size_t)s].use = false;
+        dropped = true;
+      }
+    }
+    if (!dropped) break;
+  }
+  for (int32_t i = 0; i < nRanges; i++) got[i] = F.code[(size_t)rangeStream[i]];   // 0, or the fault of the range's stream
+  if (streamStatus) for (int s = 0; s < ns; s++) streamStatus[s] = F.code[(size_t)s];
+  F.tell(ctx);
+  const int64_t nChunks = (int64_t)R.chunkGroup.size();
+  if (nChunks == 0) return total;
+  // ---- staging and tables for the largest chunk ----
+  int cmax = 0;
+  int64_t segMax = 0;
+  size_t inMax = 0, outMax = 0;
+  for (int64_t c = 0; c < nChunks; c++) {
+    const int cnt = (int)(R.chunkRow[(size_t)c + 1] - R.chunkRow[(size_t)c]);
+    const KnzPlan& G = groups[(size_t)R.chunkGroup[(size_t)c]];
+    cmax = std::max(cmax, cnt);
+    inMax = std::max(inMax, (size_t)cnt * (size_t)G.iS);
+    outMax = std::max(outMax, (size_t)cnt * (size_t)G.h.blockSize);
+    segMax = std::max(segMax, std::min<int64_t>(R.first[(size_t)c + 1] - R.first[(size_t)c], KNZ_READ_LAUNCH));
+  }
+  {
+    int rc = kz_stage_reserve(ctx, ctx->devIn[0], inMax, false);
+    if (!rc) rc = kz_stage_reserve(ctx, ctx->devOut[0], outMax, false);
+    if (!rc) rc = knz_tables(ctx, std::max((size_t)cmax * sizeof(KnzRow), (size_t)segMax * sizeof(KnzReadSeg)));
+    if (rc) return rc;
+  }
+  // ---- chunks: the decode of the chunk's rows under its group's header, the settle per stream, the copy of the chunk's segments ----
+  ChecksumScope chk(ctx, ctx->checksum);                           // each chunk decodes under its own group's kind
+  std::vector<kz_block_result> res((size_t)cmax);
+  std::vector<int64_t> W((size_t)cmax), off((size_t)cmax);
+  for (int64_t c = 0; c < nChunks; c++) {
+    const int64_t r0 = R.chunkRow[(size_t)c];
+    const int cnt = (int)(R.chunkRow[(size_t)c + 1] - r0);
+    const KnzPlan& G = groups[(size_t)R.chunkGroup[(size_t)c]];
+    const int32_t blockSize = G.h.blockSize;
+    ctx->checksum = G.h.chkKind;
+    for (int i = 0; i < cnt; i++) {
+      const int s = R.rowStream[(size_t)(r0 + i)];
+      const int64_t e = indexFirst[s] + R.rowBlock[(size_t)(r0 + i)];
+      off[(size_t)i] = blockBitOff[e]; W[(size_t)i] = blockBits[e];
+    }
+    KnzRow* t = (KnzRow*)(ctx->knzPin.p + 64);
+    // (behind it the pinned table becomes the segments')
+    const int rc = knz_chunk_decode_rows(ctx, G, [&](int i) { return srcLen[R.rowStream[(size_t)(r0 + i)]]; }, off.data(), W.data(), &hdrs[(size_t)r0], nullptr, cnt,
+      [&](int i, int64_t o, int64_t bits) { const int s = R.rowStream[(size_t)(r0 + i)]; t[i] = KnzRow{srcOff[s], srcLen[s], o, bits, (int64_t)i * G.iS}; },
+      [&](int64_t maxBytes) -> int {
+        KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + 64, t, (size_t)cnt * sizeof(KnzRow), hipMemcpyHostToDevice, ctx->stream));
+        return kz_knz_unpack_many(ctx, d_src, (const KnzRow*)(ctx->knzAux.p + 64), cnt, maxBytes, ctx->devIn[0].p);
+      }, ctx->devOut[0].p, blockSize, res.data());
+    if (rc) return rc;
+    for (int i = 0; i < cnt;) {                                    // the rows of a stream lie side by side
+      const int s = R.rowStream[(size_t)(r0 + i)];
+      int j = i + 1;
+      while (j < cnt && R.rowStream[(size_t)(r0 + j)] == s) j++;
+      knz_read_settle_blocks(&R.rowBlock[(size_t)(r0 + i)], j - i, st[(size_t)s].B, st[(size_t)s].nIndex, blockSize, res.data() + i);
+      i = j;
+    }
+    knz_read_settle_segs(R.segs.data(), R.first[(size_t)c], R.first[(size_t)c + 1], res.data(), got);
+    for (int64_t s0 = R.first[(size_t)c]; s0 < R.first[(size_t)c + 1]; s0 += KNZ_READ_LAUNCH) {
+      const int nseg = (int)std::min<int64_t>(KNZ_READ_LAUNCH, R.first[(size_t)c + 1] - s0);
+      const int64_t uEnd = s0 + nseg < R.first[(size_t)c + 1] ? R.segs[(size_t)(s0 + nseg)].unit0 : R.units[(size_t)c];
+      memcpy(ctx->knzPin.p + 64, &R.segs[(size_t)s0], (size_t)nseg * sizeof(KnzReadSeg));
+      KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + 64, ctx->knzPin.p + 64, (size_t)nseg * sizeof(KnzReadSeg), hipMemcpyHostToDevice, ctx->stream));
+      const int rrc = kz_knz_read(ctx, ctx->devOut[0].p, blockSize, blockSize, (const KnzReadSeg*)(ctx->knzAux.p + 64), nseg, d_dst, R.segs[(size_t)s0].unit0, uEnd - R.segs[(size_t)s0].unit0);
+      if (rrc) return rrc;
+      KZ_HIP(kz_stream_sync(ctx, ctx->stream));                    // the pinned table is the next launch's
+      kz_ktimer_flush(ctx);
+    }
+  }
+  F.tell(ctx);                                                     // (a decode may have left a block's text there)
   return total;
 }
 
