@@ -670,6 +670,67 @@ int64_t kz_write_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int64_t n,
                               const uint8_t* d_data, int64_t dataLen,
                               uint8_t* d_dst, int64_t dstCap, int64_t* newBitOff /* host, out */, int64_t* newBits /* host, out */);
 
+/* ---- many-stream byte-addressed writes: ranges of N streams in one call ----------------------------
+ * kz_write_bytes_device for records of several of the N streams of a store at a time: the counterpart of kz_read_bytes_many_device.
+ * Streams, indices and tables are described exactly as there; slots exactly as for kz_compress_many_device: the new stream s goes to
+ * d_dst[dstOff[s] .. dstOff[s] + dstCap[s]).  Slots overlap neither each other, nor any source segment, nor d_data: that is the
+ * caller's duty.  The new bytes are packed over ALL ranges in call order: range i brings d_data[D[i] .. D[i] + rangeLen[i]), D[i] = the
+ * sum of rangeLen[j] for j < i, and dataLen must equal D[nRanges].
+ *
+ * The single-stream call defines every result.  A stream is NAMED if at least one range names it (a zero-length range counts).  For a
+ * named stream s take what kz_write_bytes_device returns and writes when called on that stream alone with that stream's ranges in
+ * their call order, its own slot and dstCap[s]: dstLen[s] is that return value, the first dstLen[s] bytes of slot s are those bytes,
+ * and the entries [indexFirst[s], indexFirst[s + 1]) of newBitOff / newBits are that call's new index.  So the later range wins,
+ * ranges buried whole under later ones touch nothing, a wholly covered block with a table is neither decoded nor checked, block
+ * lengths are checked, and a copy of the stream results when no byte survives.  A stream no range names is not opened: its dstLen[s]
+ * is 0, its slot and its new* entries are untouched.
+ *
+ * A fault stays with its stream.  What fails the whole single-stream call (the header's code, a refused table, "range %d ends behind
+ * the data", "index entry %d does not match the stream", a touched block's own fault, -KZ_ERR_WRITE_FILE for a stream that outgrows
+ * its slot) goes to dstLen[s] of that stream alone here, and every other stream comes out byte for byte as if the failing one were not
+ * in the call.  The range number in a text is the range's number in the call.  Of a stream with several faults the one this call
+ * meets first is reported: a block's fault before the room of the chunk it is in.
+ *
+ * kz_write_bytes_many_bound needs no context: slotCap[s] (may be NULL) = kz_write_bytes_bound of stream s's entries and blockSize[s];
+ * it returns their sum, or -KZ_ERR_INVALID_PARAM.
+ *
+ *   addresses   d_src, d_data, d_dst: any address, any alignment.  All arrays and out-pointers are host memory.
+ *   read        nothing outside a named stream's own segment and d_data[0 .. dataLen); of a stream what the single call reads.
+ *   written     nothing outside the slots of the named streams.  A failed stream's slot is unspecified inside its own bounds; a slot
+ *               behind its dstLen[s] bytes likewise.  dstLen[0 .. nStreams) whenever the arguments pass.
+ *   returns     0, or a negative code for a fault of the call itself, decided before anything is read from the device:
+ *               -KZ_ERR_INVALID_PARAM for bad arguments (null pointers with a positive count, a negative count, offset, length or
+ *               capacity, rangeStream[i] outside [0, nStreams), an indexFirst that descends, a tableFirst[s] below -1, dataLen !=
+ *               D[nRanges], only one of newBitOff / newBits); -KZ_ERR_DEVICE.  nRanges == 0 returns 0, sets every dstLen[s] to 0 and
+ *               touches nothing else.  kz_last_error: the text of the first failing stream in stream order.
+ *   chunks      the touched blocks of all named streams, covered ones included, form one list ordered by header group (equal
+ *               transform word, entropy id, block size and checksum kind, in order of first appearance), then stream, then block,
+ *               cut into chunks of kz_compress_device's size for the group's block size (KZ_STREAM_CHUNK=<blocks> overrides), each
+ *               inside one group.  Every used entry, the kept blocks' and the decoded ones', is checked against its own stream in
+ *               launches of 2^18 entries before anything is unpacked.  Per chunk: one unpack launch and one batched decode, the
+ *               patch (k_knz_write, one launch per 2^20 segments of all the chunk's streams), one batched encode (the rows of a
+ *               stream that failed in the chunk are left out, which may split it), and the emit: k_knz_splice_many, one launch per
+ *               chunk's size of pieces, writes for every stream with rows in the chunk its kept blocks since its last emission and
+ *               its recoded ones behind its own last bit, the stream header with its first emission, the kept tail and the end
+ *               marker with its last.  A named stream with no touched block is a whole copy in the first emit launch with room.
+ *               So N streams of one header cost the launches and host waits of one single-stream call over as many blocks.
+ *               Device staging is bounded by one chunk; tables: 40 bytes per row, 32 per segment of a launch, 72 per span and 48
+ *               per piece of an emit launch, pinned and in HBM.  Host memory proportional to the ranges, the segments, the touched
+ *               blocks and nStreams.
+ *   cost        the touched blocks' decode and encode and a bit copy of the rest of the named streams.
+ *   stream      the call is synchronous and runs on the context's stream.
+ */
+int64_t kz_write_bytes_many_bound(const int64_t* indexFirst /* [nStreams + 1] */, const int64_t* blockBits, const int32_t* blockSize /* [nStreams] */, int32_t nStreams,
+                                  int64_t* slotCap /* out [nStreams], may be NULL */);
+int32_t kz_write_bytes_many_device(kz_ctx* ctx, const uint8_t* d_src, const int64_t* srcOff /* host */, const int64_t* srcLen /* host */, int32_t nStreams,
+                                   const int64_t* indexFirst /* host [nStreams + 1] */, const int64_t* blockBitOff /* host */, const int64_t* blockBits /* host */,
+                                   const int64_t* tableFirst /* host: NULL, or [nStreams] with -1 for a stream without a table */,
+                                   const int64_t* blockByteOff /* host: NULL when tableFirst is */,
+                                   const int32_t* rangeStream /* host */, const int64_t* rangeOff /* host */, const int64_t* rangeLen /* host */, int32_t nRanges,
+                                   const uint8_t* d_data, int64_t dataLen,
+                                   uint8_t* d_dst, const int64_t* dstOff /* host */, const int64_t* dstCap /* host */, int64_t* dstLen /* host, out [nStreams] */,
+                                   int64_t* newBitOff /* host, out */, int64_t* newBits /* host, out: laid out by indexFirst, both or neither NULL */);
+
 /* ---- splice: a new .knz stream out of blocks of existing ones, without recoding -------------------
  * Blocks are independent of one another, and a stream is its header, then per block 5 + lw prefix bits and W payload bits, then the
  * end marker (:1024-1035, :483-493): a stream made of blocks taken from existing streams is a bit-granular copy.  One call joins the

@@ -130,6 +130,9 @@ def load_library():
         "kz_write_bytes_bound": (c.c_int64, [i64p, c.c_int32, c.c_int32]),
         "kz_write_bytes": (c.c_int64, [vp, u8p, c.c_int64, i64p, i64p, i64p, c.c_int32, i64p, i64p, c.c_int32, u8p, c.c_int64, u8p, c.c_int64, i64p, i64p]),
         "kz_write_bytes_device": (c.c_int64, [vp, u8p, c.c_int64, i64p, i64p, i64p, c.c_int32, i64p, i64p, c.c_int32, u8p, c.c_int64, u8p, c.c_int64, i64p, i64p]),
+        "kz_write_bytes_many_bound": (c.c_int64, [i64p, i64p, i32p, c.c_int32, i64p]),
+        "kz_write_bytes_many_device": (c.c_int32, [vp, u8p, i64p, i64p, c.c_int32, i64p, i64p, i64p, i64p, i64p, i32p, i64p, i64p, c.c_int32, u8p, c.c_int64,
+                                                   u8p, i64p, i64p, i64p, i64p, i64p]),
         "kz_knz_splice_bound": (c.c_int64, [i64p, c.c_int32]),
         "kz_knz_splice": (c.c_int64, [u8p, i64p, i64p, c.c_int32, i32p, i64p, i64p, c.c_int32, c.c_int64, u8p, c.c_int64]),
         "kz_knz_splice_device": (c.c_int64, [vp, u8p, i64p, i64p, c.c_int32, i32p, i64p, i64p, c.c_int32, c.c_int64, u8p, c.c_int64]),
@@ -164,7 +167,7 @@ ABI_SYMBOLS = ["kz_abi_version", "kz_ctx_create", "kz_ctx_destroy", "kz_last_err
                "kz_compress_many_bound", "kz_compress_many_device", "kz_decompress_many_device",
                "kz_decompress_range", "kz_decompress_range_device", "kz_decode_indexed", "kz_decode_indexed_device",
                "kz_read_bytes", "kz_read_bytes_device", "kz_knz_index_many_device", "kz_read_bytes_many_device",
-               "kz_write_bytes_bound", "kz_write_bytes", "kz_write_bytes_device",
+               "kz_write_bytes_bound", "kz_write_bytes", "kz_write_bytes_device", "kz_write_bytes_many_bound", "kz_write_bytes_many_device",
                "kz_knz_splice_bound", "kz_knz_splice", "kz_knz_splice_device",
                "kz_knz_scan", "kz_knz_scan_device",
                "kz_set_timing", "kz_get_stage_count", "kz_get_stage_ms", "kz_get_stage_alg_bytes", "kz_reset_timing",
@@ -1489,6 +1492,53 @@ def read_bytes_many_device(ctx, src, src_off, src_len, indices, streams, offsets
     return [int(g) for g in got[:len(ro)]], [int(c) for c in status[:len(so)]]
 
 
+# ---- many-stream byte-addressed writes (kz_write_bytes_many_bound / kz_write_bytes_many_device) ----
+def write_bytes_many_bound(indices, block_sizes):
+    """kz_write_bytes_many_bound: per stream a slot capacity that suffices for any write to it (write_bytes_bound of its index and
+    block size) -> (their sum, the list of capacities)."""
+    first, _, w, _, _ = _store_arrays(indices, None)
+    bs = np.ascontiguousarray(block_sizes, dtype=np.int32)
+    if len(bs) != len(first) - 1:
+        raise ValueError("indices and block_sizes must have one length")
+    caps = np.zeros(max(len(bs), 1), dtype=np.int64)
+    bits = np.ascontiguousarray(np.clip(w, 0, (1 << 34) - 1), dtype=np.int64)
+    rc = int(load_library().kz_write_bytes_many_bound(first.ctypes.data, _arg(bits), _arg(bs), len(bs), caps.ctypes.data))
+    if rc < 0:
+        raise KanziError(-rc, "write_bytes_many_bound")
+    return rc, [int(x) for x in caps[:len(bs)]]
+
+
+def write_bytes_many_device(ctx, src, src_off, src_len, indices, streams, offsets, sizes, data, dst, dst_off, dst_cap, byte_offsets=None):
+    """kz_write_bytes_many_device: range i = bytes [offsets[i], offsets[i] + sizes[i]) of the original data of stream streams[i]
+    (stream s = the src_len[s] bytes at device address src + src_off[s]) is replaced by the sizes[i] bytes at device address data +
+    sum(sizes[:i]); the new stream s goes to device address dst + dst_off[s] (capacity dst_cap[s]; write_bytes_many_bound suffices).
+    indices, byte_offsets: as for read_bytes_many_device -> (dst_len, new_indices): per stream the new stream's size, 0 for a stream
+    that no range names or its negative code, and its new index (None unless the stream was written)."""
+    so = np.ascontiguousarray(src_off, dtype=np.int64)
+    sl = np.ascontiguousarray(src_len, dtype=np.int64)
+    do = np.ascontiguousarray(dst_off, dtype=np.int64)
+    dc = np.ascontiguousarray(dst_cap, dtype=np.int64)
+    if not len(so) == len(sl) == len(indices) == len(do) == len(dc):
+        raise ValueError("src_off, src_len, indices, dst_off and dst_cap must have one length")
+    first, off, w, tfirst, tab = _store_arrays(indices, byte_offsets)
+    rs = np.ascontiguousarray(streams, dtype=np.int32)
+    ro = np.ascontiguousarray(offsets, dtype=np.int64)
+    rl = np.ascontiguousarray(sizes, dtype=np.int64)
+    if not len(rs) == len(ro) == len(rl):
+        raise ValueError("streams, offsets and sizes differ in length")
+    n = len(so)
+    dl = np.zeros(max(n, 1), dtype=np.int64)
+    new_off, new_w = np.zeros(max(len(off), 1), dtype=np.int64), np.zeros(max(len(off), 1), dtype=np.int64)
+    ctx.check(ctx.lib.kz_write_bytes_many_device(ctx.h, _ptr(src), _arg(so), _arg(sl), n, first.ctypes.data, _arg(off), _arg(w),
+                                                 None if tfirst is None else tfirst.ctypes.data, None if tab is None else _arg(tab),
+                                                 _arg(rs), _arg(ro), _arg(rl), len(ro), _ptr(data), int(rl.sum()) if len(rl) else 0,
+                                                 _ptr(dst), _arg(do), _arg(dc), dl.ctypes.data, new_off.ctypes.data, new_w.ctypes.data))
+    dst_len = [int(x) for x in dl[:n]]
+    new = [[(int(o), int(b)) for o, b in zip(new_off[int(first[s]):int(first[s + 1])], new_w[int(first[s]):int(first[s + 1])])] if dst_len[s] > 0 else None
+           for s in range(n)]
+    return dst_len, new
+
+
 class KnzStore:
     """Many .knz streams in one torch.uint8 device tensor (what compress_many_device leaves behind), read by byte address: the
     indices of all streams come from ONE knz_index_many_device call, every read after that is one read_bytes_many_device call over
@@ -1552,6 +1602,54 @@ class KnzStore:
         """bytes [off, off + size) of the original data of one stream -> a device tensor"""
         out, got = self.read_many([stream], [off], [size])
         return out[:got[0]]
+
+    def write_many(self, streams, offsets, payloads):
+        """the store with bytes [offsets[i], offsets[i] + len(payloads[i])) of the original data of stream streams[i] replaced by
+        payloads[i] (bytes, or torch.uint8 tensors) for all i in ONE write_bytes_many_device call; where ranges of a stream overlap
+        the later one wins -> a NEW KnzStore in a tensor of its own, with the same byte_offsets: the streams that no record names are
+        copied verbatim.  This store is unchanged.  A stream that fails raises KanziError."""
+        import torch
+        streams, offsets = [int(s) for s in streams], [int(o) for o in offsets]
+        if not len(streams) == len(offsets) == len(payloads):
+            raise ValueError("streams, offsets and payloads differ in length")
+        if any(o < 0 for o in offsets):
+            raise ValueError("offset must not be negative")
+        if any(not 0 <= s < len(self) for s in streams):
+            raise IndexError("stream out of range")
+        dev = self.src.device
+        is_named = set(streams)
+        named = sorted(is_named)
+        for s in named:
+            if self.status[s] < 0:
+                raise KanziError(-self.status[s], "KnzStore: stream %d has no index" % s)
+        parts = [_byte_view(p).to(dev) if isinstance(p, torch.Tensor) else torch.from_numpy(np.frombuffer(bytes(p), dtype=np.uint8).copy()).to(dev) for p in payloads]
+        sizes = [int(p.numel()) for p in parts]
+        data = torch.cat(parts) if sum(sizes) else torch.zeros(1, dtype=torch.uint8, device=dev)
+        indices = [self.index[s] if s in is_named else None for s in range(len(self))]
+        _, caps = write_bytes_many_bound(indices, [self.index[s]["blockSize"] if s in is_named else 1024 for s in range(len(self))])
+        dst_off, dst_cap, at = [], [], 0
+        for s in range(len(self)):                                   # a slot of the bound for a named stream, of its own size for every other
+            cap = caps[s] if s in is_named else self.src_len[s]
+            dst_off.append(at)
+            dst_cap.append(cap)
+            at += cap
+        out = torch.empty(max(at, 1), dtype=torch.uint8, device=dev)
+        for s in range(len(self)):
+            if s not in is_named and self.src_len[s]:
+                out[dst_off[s]:dst_off[s] + self.src_len[s]] = self.src[self.src_off[s]:self.src_off[s] + self.src_len[s]]
+        torch.cuda.current_stream(dev).synchronize()                 # the call runs on the context's own stream
+        dst_len, _ = write_bytes_many_device(self.ctx, self.src.data_ptr(), self.src_off, self.src_len, indices, streams, offsets, sizes,
+                                             data.data_ptr(), out.data_ptr(), dst_off, dst_cap,
+                                             None if self.byte_offsets is None else [t if s in is_named else None for s, t in enumerate(self.byte_offsets)])
+        for s in named:
+            if dst_len[s] < 0:
+                raise KanziError(-dst_len[s], "KnzStore.write_many: stream %d: %s" % (s, self.ctx.error()))
+        new_len = [dst_len[s] if s in is_named else self.src_len[s] for s in range(len(self))]
+        return KnzStore(self.ctx, out, dst_off, new_len, self.byte_offsets)
+
+    def write(self, stream, off, payload):
+        """the one-record form of write_many -> a new KnzStore"""
+        return self.write_many([stream], [off], [payload])
 
 
 # ---- splice: a new .knz stream out of blocks of existing ones, without recoding (kz_knz_splice / kz_knz_splice_device) ----

@@ -51,7 +51,8 @@
   X(KID_KNZ_WALK_MANY, "k_knz_walk_many") X(KID_KNZ_UNPACK_MANY, "k_knz_unpack_many") X(KID_KNZ_SCATTER, "k_knz_scatter") \
   X(KID_KNZ_CHECK_MANY, "k_knz_check_many") X(KID_KNZ_SPLICE, "k_knz_splice") X(KID_KNZ_READ, "k_knz_read") X(KID_KNZ_WRITE, "k_knz_write") \
   X(KID_KNZ_SCAN_COUNT, "k_knz_scan_count") X(KID_KNZ_SCAN_SUM, "k_knz_scan_sum") X(KID_KNZ_SCAN_WRITE, "k_knz_scan_write") X(KID_KNZ_SCAN_LINK, "k_knz_scan_link") \
-  X(KID_KNZ_SCAN_RUN, "k_knz_scan_run") X(KID_KNZ_SCAN_MARK, "k_knz_scan_mark") X(KID_KNZ_SCAN_EMIT, "k_knz_scan_emit") X(KID_KNZ_CHECK_ROWS, "k_knz_check_rows")
+  X(KID_KNZ_SCAN_RUN, "k_knz_scan_run") X(KID_KNZ_SCAN_MARK, "k_knz_scan_mark") X(KID_KNZ_SCAN_EMIT, "k_knz_scan_emit") X(KID_KNZ_CHECK_ROWS, "k_knz_check_rows") \
+  X(KID_KNZ_SPLICE_MANY, "k_knz_splice_many")
 #define KZ_KERNEL_ENUM(id, name) id,
 #define KZ_KERNEL_NAME(id, name) name,
 enum KzKernelId { KZ_KERNELS(KZ_KERNEL_ENUM) KID_COUNT };
@@ -342,6 +343,12 @@ int kz_knz_unpack_many(kz_ctx*, const uint8_t* d_src, const KnzRow* d_t, int nr,
 struct KnzPiece { int64_t pay, bits, seg, n, off, hdrEnd; };
 int kz_knz_check_many(kz_ctx*, const uint8_t* d_src, const KnzPiece* d_pc, int np, int32_t* d_bad);
 int kz_knz_splice_launch(kz_ctx*, const uint8_t* d_src, const KnzPiece* d_pc, int np, uint8_t* d_dst, int64_t startBit, int64_t endBit);
+// the splice's copy into many destinations in one launch (kz_write_bytes_many_device): span i owns the bits [startBit, endBit) of the
+// slot d_dst + dst: the stream header hdr[0 .. hdrBytes) when it is the stream's first (startBit == 0 then), the fields of its pieces
+// d_pc[piece0 .. piece0 + npieces) (pay counted from the slot's first bit), zeros up to endBit and to the end of the last byte.  unit0 =
+// the span's first 16-byte aligned unit among the launch's (a prefix sum that grows strictly with the span, d_sp[0].unit0 == 0).
+struct KnzSpan { int64_t dst, startBit, endBit, unit0; int32_t piece0, npieces, hdrBytes; uint8_t hdr[28]; };
+int kz_knz_splice_many(kz_ctx*, const uint8_t* d_src, const KnzSpan* d_sp, int ns, const KnzPiece* d_pc, uint8_t* d_dst, int64_t units);
 // the index entries of many streams, each against its own (kz_read_bytes_many_device): entry (off, bits) of the stream src[seg .. seg + n),
 // whose header ends at bit hdrEnd; d_hdr[i] = the block-header word as kz_knz_check gives it, d_bad[i] = 0 / 1
 struct KnzCheckRow { int64_t seg, n, off, bits, hdrEnd; };

@@ -7,7 +7,8 @@
 // and the copy of the byte-addressed reads: many (range x block) segments of decoded rows to their places in one launch (k_knz_read),
 // with its mirror image for the byte-addressed writes: segments of new bytes into decoded rows (k_knz_write).
 // For the byte-addressed read of many streams (kz_read_bytes_many_device) the check of index entries has a form over rows of many
-// streams that also brings the block-header words (k_knz_check_rows).
+// streams that also brings the block-header words (k_knz_check_rows); for the byte-addressed write of many streams
+// (kz_write_bytes_many_device) the splice's copy has a form that writes a bit range in each of many slots (k_knz_splice_many).
 // Last, the scan (kz_knz_scan_device): the reader's acceptance test at every bit position of a stream and the link step over the
 // accepted positions (k_knz_scan_*), which finds a stream's blocks without the walk and behind damage.
 // The callers (kz_stream_device.hip: kz_compress_device / kz_decompress_device / kz_decompress_range_device / kz_decode_indexed_device /
@@ -448,6 +449,60 @@ __global__ void __launch_bounds__(256) k_knz_pack_many(const u8* __restrict__ ro
   }
 }
 
+// ---- splice: blocks of existing streams and recoded rows -> bit ranges in many slots (kz_write_bytes_many_device) --------------------
+// k_knz_splice's copy with many destinations in one launch.  Span s (kz_internal.h: KnzSpan) owns the bits [startBit, endBit) of the
+// slot dst + sp[s].dst: the stream header when it is the stream's first span (sp[s].hdr, a whole number of bytes; startBit == 0), the
+// fields of its pieces pcAll[piece0 .. piece0 + npieces) back to back (pay counted from the slot's first bit; a kept block lies in its
+// own stream inside src, a recoded one in an encoder row named by its distance from src), zeros up to endBit and to the end of the
+// last byte.  A span may have no piece: the header alone, or the end marker alone.  No staging rows for kept blocks: a payload bit is
+// loaded once and stored once.
+// The launch's work is the 16-byte aligned units of all its spans, one span after the other (sp[s].unit0, a prefix sum that grows
+// strictly with s, sp[0].unit0 == 0).  A lane takes a unit and finds its span with the read's wave-narrowed search; the piece inside
+// the span likewise when the whole wave is inside one span (k_knz_splice's scheme: its arguments are wave-uniform then), else by a
+// search of its own.  A unit wholly inside one payload is one wide store of aligned loads that stay inside the piece's own source
+// bounds; everything else is composed bytewise.
+// Two spans of a launch never share a byte (every stream has one span per launch at the most, and slots do not overlap), but
+// neighbouring slots may share an aligned unit of memory: each span has a unit of its own for it and writes its own bytes only.  A
+// span that starts in mid-byte keeps that byte's high bits: they are the same stream's previous span, written by an earlier launch on
+// the same HIP stream with the spare bits zero; only the lane of the span's first unit reads and writes that byte.
+__global__ void __launch_bounds__(256) k_knz_splice_many(const u8* __restrict__ src, const KnzSpan* __restrict__ sp, int ns, const KnzPiece* __restrict__ pcAll,
+                                                         u8* dst, int64_t units) {
+  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t u0 = knz_first_lane(u);                                             // the wave's units: at most 64 in a row from its first lane's
+    const int slo = knz_read_find(sp, 0, ns - 1, u0);
+    int shi = slo;                                                                    // (every span has a unit: 63 units on are at most 63 spans on)
+    if (slo + 1 < ns && sp[slo + 1].unit0 <= u0 + 63) shi = knz_read_find(sp, slo + 1, slo + 63 < ns - 1 ? slo + 63 : ns - 1, u0 + 63);
+    const int s = knz_read_find(sp, slo, shi, u);
+    const int64_t startBit = sp[s].startBit, endBit = sp[s].endBit;
+    const int hdrBytes = sp[s].hdrBytes;
+    const KnzPiece* pc = pcAll + sp[s].piece0;
+    const int np = sp[s].npieces;
+    u8* d = dst + sp[s].dst;
+    const int64_t firstByte = startBit >> 3, lastByte = (endBit + 7) >> 3;           // [firstByte, lastByte) of the slot is written
+    const uintptr_t A0 = (uintptr_t)(d + firstByte) & ~(uintptr_t)15;
+    const int64_t ub = (int64_t)(A0 - (uintptr_t)d) + ((u - sp[s].unit0) << 4);       // the unit's first byte as an index into the slot (may be < firstByte)
+    const int64_t lo = ub < firstByte ? firstByte : ub, hi = ub + 16 > lastByte ? lastByte : ub + 16;
+    if (lo >= hi) continue;
+    const int64_t pos0 = (lo == firstByte) ? startBit : (lo << 3);
+    int j;
+    if (slo == shi) {                                                                 // the wave's 64 units lie side by side in one span
+      const int64_t ub0 = knz_first_lane(ub);
+      const int jlo = knz_find_field(pc, np, ub0 < firstByte ? startBit : (ub0 << 3));
+      const int jhi = knz_find_field(pc, np, (ub0 + 63 * 16) << 3);
+      j = knz_find_between(pc, jlo, jhi, pos0);
+    } else j = knz_find_field(pc, np, pos0);
+    if (hi - lo == 16 && knz_wide_unit(src, pc, np, j, pos0, hi << 3, d + lo)) continue;
+    int64_t pos = pos0;
+    for (int64_t b = lo; b < hi; b++) {
+      const int64_t bend = (b + 1) << 3;
+      if (b < hdrBytes) { d[b] = sp[s].hdr[b]; pos = bend; continue; }
+      const u32 acc = (pos & 7) ? d[b] & (0xFFu << (8 - (int)(pos & 7))) : 0u;        // only the span's first byte
+      d[b] = knz_compose_byte(src, pc, np, j, pos, bend, acc);
+      pos = bend;
+    }
+  }
+}
+
 // ---- heads: the first bytes of every stream, for the host's header parse -----------------------------------------------------------
 // heads[32 s + i] = byte i of stream s for i < min(26, n) (the longest stream header), zero behind that
 __global__ void __launch_bounds__(256) k_knz_heads(const u8* __restrict__ src, const KnzSrc* __restrict__ t, int ns, u8* __restrict__ heads) {
@@ -777,6 +832,12 @@ int kz_knz_scatter(kz_ctx* ctx, const uint8_t* d_rows, const KnzCopy* d_t, int n
 int kz_knz_pack_many(kz_ctx* ctx, const uint8_t* d_rows, const KnzSeg* d_seg, int ns, const KnzBlk* d_blk, uint8_t* d_dst, int64_t units) {
   if (ns <= 0 || units <= 0) return 0;
   KZ_LAUNCH(ctx, KID_KNZ_PACK_MANY, k_knz_pack_many, knz_pack_grid(units), dim3(256), d_rows, d_seg, ns, d_blk, d_dst, units);
+  KZ_HIP(hipGetLastError());
+  return 0;
+}
+int kz_knz_splice_many(kz_ctx* ctx, const uint8_t* d_src, const KnzSpan* d_sp, int ns, const KnzPiece* d_pc, uint8_t* d_dst, int64_t units) {
+  if (ns <= 0 || units <= 0) return 0;
+  KZ_LAUNCH(ctx, KID_KNZ_SPLICE_MANY, k_knz_splice_many, knz_pack_grid(units), dim3(256), d_src, d_sp, ns, d_pc, d_dst, units);
   KZ_HIP(hipGetLastError());
   return 0;
 }

@@ -775,16 +775,20 @@ static inline int knz_write_behind(int32_t i, char* err, size_t errCap) {
 // Later wins by a sort and a sweep, O(nRanges log nRanges): the ranges' starts and ends in ascending order cut the data into at most
 // 2 nRanges elementary intervals; over each the owner is the highest range among those open there (a heap of the open ranges, closed
 // ones dropped when they come to the top).  Neighbours of one owner are joined, then each piece is cut with the blocks.
-static inline int32_t knz_write_plan(const int64_t* B, int32_t nIndex, int32_t blockSize, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges,
-                                     int CH, int64_t launch, KnzWritePlan& P) {
+// knz_write_plan_at is the form for a call whose new bytes are packed over the ranges of many streams (kz_write_bytes_many_device): range
+// i brings data[rangeData[i] .. + rangeLen[i]); null = the running sum, the single-stream calls' rule.
+static inline int32_t knz_write_plan_at(const int64_t* B, int32_t nIndex, int32_t blockSize, const int64_t* rangeOff, const int64_t* rangeLen, const int64_t* rangeData,
+                                        int32_t nRanges, int CH, int64_t launch, KnzWritePlan& P) {
   P.end = B ? B[nIndex] : (int64_t)nIndex * blockSize;
   P.blocks.clear(); P.covered.clear(); P.segs.clear(); P.first.assign(1, 0); P.units.clear(); P.cuts.assign(1, 0);
   std::vector<int64_t> D((size_t)nRanges + 1, 0);
+  int64_t run = 0;                                                 // the running sum of the lengths
   std::vector<int32_t> open;                                       // the ranges with bytes, by start (ties: by argument order)
   std::vector<int64_t> pts;
   for (int32_t i = 0; i < nRanges; i++) {
     if (rangeOff[i] > P.end || rangeLen[i] > P.end - rangeOff[i]) return i;
-    D[(size_t)i + 1] = D[(size_t)i] + rangeLen[i];
+    D[(size_t)i] = rangeData ? rangeData[i] : run;
+    run += rangeLen[i];
     if (rangeLen[i] == 0) continue;
     open.push_back(i);
     pts.push_back(rangeOff[i]); pts.push_back(rangeOff[i] + rangeLen[i]);          // (<= P.end: checked above)
@@ -836,6 +840,10 @@ static inline int32_t knz_write_plan(const int64_t* B, int32_t nIndex, int32_t b
       P.cuts.push_back(s);
     }
   return -1;
+}
+static inline int32_t knz_write_plan(const int64_t* B, int32_t nIndex, int32_t blockSize, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges,
+                                     int CH, int64_t launch, KnzWritePlan& P) {
+  return knz_write_plan_at(B, nIndex, blockSize, rangeOff, rangeLen, nullptr, nRanges, CH, launch, P);
 }
 // The results of the wholly covered blocks among blocks[b0 .. b0 + cnt), which are not decoded: before the chunk's decode status 1
 // (left out of it), behind it (decoded) status 0 and the table's length, as if they had been.
@@ -892,3 +900,97 @@ template <class F> static inline int64_t knz_write_walk(const int64_t* blockBits
   return pos;
 }
 static inline void knz_write_walk_only(int64_t, int64_t, int64_t, int64_t) {}
+
+// ---- byte-addressed writes of many streams in one call (kz_write_bytes_many_device) ----
+// Streams, indices, tables and ranges are the many-stream read's; slots are kz_compress_many_device's; the new bytes are packed over
+// all ranges in call order.  The arguments of the call, checked before anything else happens.
+static inline int knz_write_many_args(const void* src, const int64_t* srcOff, const int64_t* srcLen, int32_t nStreams, const int64_t* indexFirst,
+                                      const int64_t* blockBitOff, const int64_t* blockBits, const int64_t* tableFirst, const int64_t* blockByteOff,
+                                      const int32_t* rangeStream, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges, const void* data, int64_t dataLen,
+                                      const void* dst, const int64_t* dstOff, const int64_t* dstCap, const int64_t* dstLen, const int64_t* newBitOff, const int64_t* newBits) {
+  if (nRanges < 0 || dataLen < 0 || (!newBitOff != !newBits)) return -KZ_ERR_INVALID_PARAM;
+  { const int rc = knz_many_src_args(src, srcOff, srcLen, nStreams); if (rc) return rc; }
+  if (nStreams > 0) {
+    if (!indexFirst || indexFirst[0] < 0 || !dst || !dstOff || !dstCap || !dstLen) return -KZ_ERR_INVALID_PARAM;
+    for (int32_t s = 0; s < nStreams; s++)
+      if (indexFirst[s + 1] < indexFirst[s] || indexFirst[s + 1] - indexFirst[s] > 0x7FFFFFFF || dstOff[s] < 0 || dstCap[s] < 0) return -KZ_ERR_INVALID_PARAM;
+    if (indexFirst[nStreams] > 0 && (!blockBitOff || !blockBits)) return -KZ_ERR_INVALID_PARAM;
+    if (tableFirst)
+      for (int32_t s = 0; s < nStreams; s++) if (tableFirst[s] < -1 || (tableFirst[s] >= 0 && !blockByteOff)) return -KZ_ERR_INVALID_PARAM;
+  }
+  if ((nRanges > 0 && (!rangeStream || !rangeOff || !rangeLen)) || (dataLen > 0 && !data)) return -KZ_ERR_INVALID_PARAM;
+  int64_t D = 0;
+  for (int32_t i = 0; i < nRanges; i++) {
+    if (rangeStream[i] < 0 || rangeStream[i] >= nStreams || rangeOff[i] < 0 || rangeLen[i] < 0 || rangeLen[i] > dataLen - D) return -KZ_ERR_INVALID_PARAM;
+    D += rangeLen[i];
+  }
+  return D == dataLen ? 0 : -KZ_ERR_INVALID_PARAM;
+}
+// kz_write_bytes_many_bound: knz_write_bound of every stream's entries and block size, and their sum
+static inline int64_t knz_write_many_bound(const int64_t* indexFirst, const int64_t* blockBits, const int32_t* blockSize, int32_t nStreams, int64_t* slotCap) {
+  if (nStreams < 0 || (nStreams > 0 && (!indexFirst || !blockSize || indexFirst[0] < 0))) return -KZ_ERR_INVALID_PARAM;
+  int64_t sum = 0;
+  for (int32_t s = 0; s < nStreams; s++) {
+    const int64_t cnt = indexFirst[s + 1] - indexFirst[s];
+    if (cnt < 0 || cnt > 0x7FFFFFFF || (cnt > 0 && !blockBits)) return -KZ_ERR_INVALID_PARAM;
+    const int64_t cap = knz_write_bound(cnt ? blockBits + indexFirst[s] : nullptr, (int32_t)cnt, blockSize[s]);
+    if (cap < 0) return cap;
+    if (slotCap) slotCap[s] = cap;
+    sum += cap;
+    if (sum > (1LL << 62)) return -KZ_ERR_INVALID_PARAM;
+  }
+  return sum;
+}
+// What the merged plan needs to know of a stream: whether it is written at all (a stream that no range names, or one with a fault of
+// its own, is not), its header group as in KnzManyStreamIn, its own plan (knz_write_plan_at with one chunk: a segment's slot is its
+// block's place among the stream's touched blocks) and the number in the call of each of its ranges.
+struct KnzManyWriteIn { bool use; int32_t group; const KnzWritePlan* plan; const int32_t* rangeId; };
+// The merged plan of the call: the touched blocks of all streams that are written, covered ones included, in one list of rows ordered
+// by header group, then stream, then block; the rows cut into chunks, each inside one group and of at most that group's chunk size
+// (knz_read_many_plan's rule); the surviving segments of all streams chunk by chunk in row order, as KnzWritePlan holds them: slot = the
+// row's place in its chunk, unit0 = the prefix sum of the row units inside the chunk, range = the range's number in the call, cuts =
+// the patch launches.  A written stream with no touched block has no row.
+struct KnzManyWritePlan {
+  std::vector<int32_t> rowStream, rowBlock;   // the merged list
+  std::vector<uint8_t> rowCovered;            // the row's block is wholly overwritten and a table gave its length
+  std::vector<int64_t> chunkRow;              // chunk c = rows [chunkRow[c], chunkRow[c + 1])
+  std::vector<int32_t> chunkGroup;            // its header group
+  std::vector<KnzWriteSeg> segs;              // chunk by chunk; inside a chunk by row, then by offset in the block
+  std::vector<int64_t> first, units, cuts;    // as in KnzWritePlan
+};
+static inline void knz_write_many_plan(const KnzManyWriteIn* st, int32_t nStreams, const int* chunkBlocks, int64_t launch, KnzManyWritePlan& P) {
+  P.rowStream.clear(); P.rowBlock.clear(); P.rowCovered.clear(); P.chunkRow.clear(); P.chunkGroup.clear();
+  P.segs.clear(); P.first.assign(1, 0); P.units.clear(); P.cuts.assign(1, 0);
+  std::vector<int32_t> order;
+  for (int32_t s = 0; s < nStreams; s++) if (st[s].use && !st[s].plan->blocks.empty()) order.push_back(s);
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return st[a].group < st[b].group; });   // (inside a group: by stream)
+  for (const int32_t s : order) {
+    const KnzWritePlan& W = *st[s].plan;
+    const int32_t g = st[s].group;
+    size_t si = 0;                                                 // the stream's next segment: they ascend with its blocks
+    for (size_t t = 0; t < W.blocks.size(); t++) {
+      const int64_t r = (int64_t)P.rowStream.size();
+      const bool open = !P.chunkGroup.empty() && P.chunkGroup.back() == g && r - P.chunkRow.back() < chunkBlocks[g];
+      if (!open) {                                                 // (a chunk never holds rows of two groups)
+        if (!P.chunkGroup.empty()) P.first.push_back((int64_t)P.segs.size());
+        P.chunkRow.push_back(r); P.chunkGroup.push_back(g); P.units.push_back(0);
+      }
+      P.rowStream.push_back(s); P.rowBlock.push_back(W.blocks[t]); P.rowCovered.push_back(W.covered[t]);
+      for (; si < W.segs.size() && W.segs[si].slot == (int32_t)t; si++) {
+        KnzWriteSeg q = W.segs[si];
+        q.slot = (int32_t)(r - P.chunkRow.back());
+        q.unit0 = P.units.back();
+        q.range = st[s].rangeId[q.range];
+        P.units.back() += knz_read_units(q.off & 15, q.len);
+        P.segs.push_back(q);
+      }
+    }
+  }
+  if (!P.chunkGroup.empty()) P.first.push_back((int64_t)P.segs.size());
+  P.chunkRow.push_back((int64_t)P.rowStream.size());
+  for (size_t c = 0; c + 1 < P.first.size(); c++)
+    for (int64_t s = P.first[c]; s < P.first[c + 1];) {
+      s += std::min<int64_t>(launch, P.first[c + 1] - s);
+      P.cuts.push_back(s);
+    }
+}

@@ -1,7 +1,8 @@
 // kz_stream_device.hip -- the .knz container with source and destination in HBM: the same streams as kz_stream.hip's calls write and
 // read, whole, by block range, by index, and many at a time, edits them without recoding (the splice), and reads and rewrites byte
 // ranges of their data (kz_read_bytes_device, kz_write_bytes_device), and indexes and reads many of them in one call
-// (kz_knz_index_many_device, kz_read_bytes_many_device).  The kernels are in kz_knz_gpu.hip; what stays on the host is what
+// (kz_knz_index_many_device, kz_read_bytes_many_device), and rewrites ranges of many of them in one call
+// (kz_write_bytes_many_device).  The kernels are in kz_knz_gpu.hip; what stays on the host is what
 // kz_compress / kz_decompress do there as well and costs nothing: the stream header (kz_knz_host.h, on a copy of at most 26 bytes),
 // the bit-offset arithmetic over results[] (host arrays anyway), and the block checks on the 8 header bytes per block that the walk
 // kernel brings back.  The rules shared with the host-buffer calls are in kz_knz_host.h and kz_knz_stream.h.
@@ -1411,3 +1412,431 @@ extern "C" int64_t kz_write_bytes_device(kz_ctx* ctx, const uint8_t* d_src, int6
   return (pos + 7) >> 3;
 }
 
+
+
+// =================================================================================================
+// kz_write_bytes_device for ranges of N streams in one call (kz_write_bytes_many_device).  The open is the many-stream read's (k_knz_heads
+// over the streams that some range names, one copy, parsed here); per stream the single call's table check and its plan (knz_write_plan_at:
+// a stream's ranges are not side by side in the packed data); the merged plan is knz_write_many_plan (kz_knz_host.h: the touched blocks of
+// all streams in one list of rows by header group, stream and block, cut into chunks inside a group).  Every entry the call uses, the
+// kept blocks' and the decoded ones', is checked against its own stream (k_knz_check_rows) before anything is unpacked.  A chunk is the
+// indexed calls' decode step over rows of many streams (k_knz_unpack_many), the settle per stream, the patch (k_knz_write), one batched
+// encode under the group's header, and the emit: ONE k_knz_splice_many launch per bounded number of pieces that writes, for every
+// stream with rows in the chunk, every kept block since that stream's last emitted one together with its recoded blocks behind that
+// stream's last bit -- with the stream header in front when it is the stream's first emission, and with the kept tail and the end marker
+// when the stream's last touched block is in the chunk.  A named stream with no touched block is a whole copy that rides in the first
+// emit launch with room for it.  A fault that ends the single-stream call ends only its stream here: its rows are carried through the
+// chunk's decode and then ignored, in later chunks they are left out.
+namespace {
+// The emit launches of the call: spans and pieces collect in the pinned tables (spans at 64, pieces behind cap spans) until either
+// count reaches cap, or the caller flushes because the encoder rows that pieces name are about to be written again.
+struct KnzEmit {
+  kz_ctx* ctx; const uint8_t* d_src; uint8_t* d_dst; int cap;
+  int nsp = 0, npc = 0; int64_t units = 0; bool open = false;
+  KnzSpan* sp() const { return (KnzSpan*)(ctx->knzPin.p + 64); }
+  size_t pcAt() const { return 64 + kz_align((size_t)cap * sizeof(KnzSpan), 64); }
+  KnzPiece* pc() const { return (KnzPiece*)(ctx->knzPin.p + pcAt()); }
+  static size_t bytes(int cap) { return kz_align((size_t)cap * sizeof(KnzSpan), 64) + (size_t)cap * sizeof(KnzPiece); }
+  int room() const { return cap - npc; }
+  int flush() {
+    if (nsp == 0) return 0;
+    KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + 64, sp(), (size_t)nsp * sizeof(KnzSpan), hipMemcpyHostToDevice, ctx->stream));
+    if (npc) KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + pcAt(), pc(), (size_t)npc * sizeof(KnzPiece), hipMemcpyHostToDevice, ctx->stream));
+    { const int rc = kz_knz_splice_many(ctx, d_src, (const KnzSpan*)(ctx->knzAux.p + 64), nsp, (const KnzPiece*)(ctx->knzAux.p + pcAt()), d_dst, units); if (rc) return rc; }
+    KZ_HIP(kz_stream_sync(ctx, ctx->stream));                      // the pinned tables are the next launch's
+    kz_ktimer_flush(ctx);
+    nsp = npc = 0; units = 0;
+    return 0;
+  }
+  void begin(int64_t dst, int64_t startBit, const uint8_t* hdr, int hdrBytes) {
+    KnzSpan& g = sp()[nsp];
+    memset(&g, 0, sizeof(g));
+    g.dst = dst; g.startBit = startBit; g.unit0 = units; g.piece0 = npc; g.hdrBytes = hdrBytes;
+    if (hdrBytes) memcpy(g.hdr, hdr, (size_t)hdrBytes);
+    open = true;
+  }
+  // the open span ends at endBit; a span of no bits is dropped
+  int end(int64_t endBit) {
+    KnzSpan& g = sp()[nsp];
+    open = false;
+    if (endBit <= g.startBit) { npc = g.piece0; return 0; }
+    g.endBit = endBit;
+    const uintptr_t a = (uintptr_t)d_dst + (uintptr_t)g.dst;
+    units += (int64_t)((a + (uintptr_t)((endBit + 7) >> 3) - ((a + (uintptr_t)(g.startBit >> 3)) & ~(uintptr_t)15) + 15) >> 4);
+    nsp++;
+    return nsp == cap ? flush() : 0;
+  }
+  // a piece of the open span whose prefix starts at bit `at`: when the launch is full the span ends there and goes on in the next one
+  int piece(int64_t at, const KnzPiece& p) {
+    if (npc == cap) {
+      const int64_t dst = sp()[nsp].dst;
+      { int rc = end(at); if (!rc) rc = flush(); if (rc) return rc; }
+      begin(dst, at, nullptr, 0);
+    }
+    pc()[npc++] = p;
+    sp()[nsp].npieces++;
+    return 0;
+  }
+};
+}  // namespace
+
+extern "C" int64_t kz_write_bytes_many_bound(const int64_t* indexFirst, const int64_t* blockBits, const int32_t* blockSize, int32_t nStreams, int64_t* slotCap) {
+  return knz_write_many_bound(indexFirst, blockBits, blockSize, nStreams, slotCap);
+}
+
+extern "C" int32_t kz_write_bytes_many_device(kz_ctx* ctx, const uint8_t* d_src, const int64_t* srcOff, const int64_t* srcLen, int32_t nStreams,
+                                              const int64_t* indexFirst, const int64_t* blockBitOff, const int64_t* blockBits,
+                                              const int64_t* tableFirst, const int64_t* blockByteOff,
+                                              const int32_t* rangeStream, const int64_t* rangeOff, const int64_t* rangeLen, int32_t nRanges,
+                                              const uint8_t* d_data, int64_t dataLen,
+                                              uint8_t* d_dst, const int64_t* dstOff, const int64_t* dstCap, int64_t* dstLen,
+                                              int64_t* newBitOff, int64_t* newBits) {
+  if (!ctx) return -KZ_ERR_INVALID_PARAM;
+  {
+    const int rc = knz_write_many_args(d_src, srcOff, srcLen, nStreams, indexFirst, blockBitOff, blockBits, tableFirst, blockByteOff, rangeStream, rangeOff, rangeLen,
+                                       nRanges, d_data, dataLen, d_dst, dstOff, dstCap, dstLen, newBitOff, newBits);
+    if (rc) return rc;
+  }
+  const char* call = "kz_write_bytes_many_device";
+  const int ns = nStreams;
+  for (int s = 0; s < ns; s++) dstLen[s] = 0;
+  if (nRanges == 0) return 0;
+  KZ_HIP(hipSetDevice(ctx->device));
+  // ---- the streams that some range names, ascending, and each one's ranges in call order with their places in the packed data ----
+  std::vector<int32_t> ids;
+  std::vector<int64_t> rFirst((size_t)ns + 1, 0), rOff((size_t)nRanges), rLen((size_t)nRanges), rData((size_t)nRanges);
+  std::vector<int32_t> rId((size_t)nRanges);
+  {
+    for (int32_t i = 0; i < nRanges; i++) rFirst[(size_t)rangeStream[i] + 1]++;
+    for (int s = 0; s < ns; s++) { if (rFirst[(size_t)s + 1]) ids.push_back(s); rFirst[(size_t)s + 1] += rFirst[(size_t)s]; }
+    std::vector<int64_t> fill(rFirst.begin(), rFirst.end() - 1);
+    int64_t D = 0;
+    for (int32_t i = 0; i < nRanges; i++) {
+      const int64_t at = fill[(size_t)rangeStream[i]]++;
+      rOff[(size_t)at] = rangeOff[i]; rLen[(size_t)at] = rangeLen[i]; rData[(size_t)at] = D; rId[(size_t)at] = i;
+      D += rangeLen[i];
+    }
+  }
+  const int nn = (int)ids.size();
+  // ---- their heads in one copy; per stream the single call's open, table check and plan ----
+  KnzStreamFaults F(ns);
+  std::vector<uint8_t> use((size_t)ns, 0);
+  std::vector<KnzPlan> plan((size_t)ns);
+  std::vector<KnzWritePlan> wp((size_t)ns);
+  std::vector<const int64_t*> tab((size_t)ns, nullptr);
+  std::vector<int32_t> nIdx((size_t)ns, 0);
+  {
+    const size_t tBytes = kz_align((size_t)nn * sizeof(KnzSrc), 64);
+    { const int rc = knz_tables(ctx, tBytes + (size_t)nn * 32); if (rc) return rc; }
+    { const int rc = knz_many_heads(ctx, d_src, srcOff, srcLen, ids.data(), nn, tBytes); if (rc) return rc; }
+    for (int k = 0; k < nn; k++) {
+      const int s = ids[(size_t)k];
+      HostBitsIn bs{ctx->knzPin.p + tBytes + (size_t)k * 32, (uint64_t)std::min<int64_t>(srcLen[s], 26) * 8, 0, false};
+      KnzHeader h;
+      char why[96] = "";
+      const int hrc = read_stream_header(bs, h, why, sizeof(why));
+      if (hrc) { F.fail(s, hrc, call, why[0] ? why : "not a stream header"); continue; }
+      plan[(size_t)s] = knz_plan(ctx, h, srcLen[s], (int64_t)bs.pos);
+      nIdx[(size_t)s] = (int32_t)(indexFirst[s + 1] - indexFirst[s]);
+      tab[(size_t)s] = (tableFirst && tableFirst[s] >= 0) ? blockByteOff + tableFirst[s] : nullptr;
+      if (knz_read_table(tab[(size_t)s], nIdx[(size_t)s], h.blockSize)) { F.fail(s, -KZ_ERR_INVALID_PARAM, call, "blockByteOff is not a table of block starts"); continue; }
+      const int64_t a = rFirst[(size_t)s];
+      const int32_t bad = knz_write_plan_at(tab[(size_t)s], nIdx[(size_t)s], h.blockSize, &rOff[(size_t)a], &rLen[(size_t)a], &rData[(size_t)a],
+                                            (int32_t)(rFirst[(size_t)s + 1] - a), 0x7FFFFFFF, INT64_MAX, wp[(size_t)s]);
+      if (bad >= 0) { snprintf(why, sizeof(why), "range %d ends behind the data", (int)rId[(size_t)(a + bad)]); F.fail(s, -KZ_ERR_INVALID_PARAM, call, why); continue; }
+      use[(size_t)s] = 1;
+    }
+  }
+  auto finish = [&]() -> int32_t {
+    for (int s = 0; s < ns; s++) if (F.code[(size_t)s]) dstLen[s] = F.code[(size_t)s];
+    F.tell(ctx);
+    return 0;
+  };
+  // ---- the merged plan, and every entry it uses against its own stream before anything is unpacked: the kept blocks' and the decoded
+  //      ones'; a wholly covered block's is not looked at.  A stream with an entry that does not match leaves the plan, which is then
+  //      made again without it (and checked again: the rows have other places) ----
+  std::vector<KnzManyWriteIn> st((size_t)ns);
+  KnzManyWritePlan R;
+  std::vector<KnzPlan> groups;                                     // a group's plan: its first stream's (the header's four fields, the staging row)
+  std::vector<int> chunkBlocks;
+  std::vector<uint64_t> hdrs;
+  for (;;) {
+    groups.clear(); chunkBlocks.clear();
+    int64_t entries = 0;
+    for (int s = 0; s < ns; s++) {
+      st[(size_t)s] = KnzManyWriteIn{use[(size_t)s] != 0, -1, &wp[(size_t)s], rId.data() + rFirst[(size_t)s]};
+      if (!use[(size_t)s]) continue;
+      const KnzHeader& h = plan[(size_t)s].h;
+      size_t g = 0;
+      for (; g < groups.size(); g++) if (groups[g].h.transformType == h.transformType && groups[g].h.entropyType == h.entropyType && groups[g].h.blockSize == h.blockSize && groups[g].h.chkKind == h.chkKind) break;
+      if (g == groups.size()) { groups.push_back(plan[(size_t)s]); chunkBlocks.push_back(knz_chunk_blocks(ctx, h.blockSize)); }
+      st[(size_t)s].group = (int32_t)g;
+      entries += nIdx[(size_t)s];
+    }
+    knz_write_many_plan(st.data(), ns, chunkBlocks.data(), KNZ_WRITE_LAUNCH, R);
+    const int64_t nr = (int64_t)R.rowStream.size();
+    hdrs.assign((size_t)nr, 0);
+    if (entries == 0) break;
+    std::vector<int64_t> rowOf((size_t)ns, -1);                    // a stream's first row
+    for (int64_t r = nr - 1; r >= 0; r--) rowOf[(size_t)R.rowStream[(size_t)r]] = r;
+    const int CK = (int)std::min<int64_t>(KNZ_CHECK_LAUNCH, entries);
+    const size_t rowBytes = kz_align((size_t)CK * sizeof(KnzCheckRow), 64);
+    { const int rc = knz_tables(ctx, rowBytes + (size_t)CK * 16); if (rc) return rc; }
+    struct Entry { int32_t s, k; int64_t row; };
+    std::vector<Entry> ent((size_t)CK);
+    bool dropped = false;
+    int kn = 0;                                                    // the stream (among ids) and the block of the next entry
+    int64_t kk = 0, tr = -1;                                       // tr: that stream's next touched row, -1 before its first entry
+    for (;;) {
+      int cnt = 0;
+      KnzCheckRow* t = (KnzCheckRow*)ctx->knzPin.p;
+      while (cnt < CK && kn < nn) {
+        const int s = ids[(size_t)kn];
+        if (!use[(size_t)s] || kk >= nIdx[(size_t)s]) { kn++; kk = 0; tr = -1; continue; }
+        if (tr < 0) tr = rowOf[(size_t)s] >= 0 ? rowOf[(size_t)s] : nr;
+        const bool touched = tr < nr && R.rowStream[(size_t)tr] == s && R.rowBlock[(size_t)tr] == kk;
+        const int64_t row = touched ? tr++ : -1;
+        if (!(touched && R.rowCovered[(size_t)row])) {
+          const int64_t e = indexFirst[s] + kk;
+          t[cnt] = KnzCheckRow{srcOff[s], srcLen[s], blockBitOff[e], blockBits[e], plan[(size_t)s].hdrEnd};
+          ent[(size_t)cnt++] = Entry{s, (int32_t)kk, row};
+        }
+        kk++;
+      }
+      if (cnt == 0) break;
+      uint64_t* d_hdr = (uint64_t*)(ctx->knzAux.p + rowBytes);
+      KZ_HIP(hipMemcpyAsync(ctx->knzAux.p, t, (size_t)cnt * sizeof(KnzCheckRow), hipMemcpyHostToDevice, ctx->stream));
+      { const int rc = kz_knz_check_rows(ctx, d_src, (const KnzCheckRow*)ctx->knzAux.p, cnt, d_hdr, (int64_t*)(d_hdr + CK)); if (rc) return rc; }
+      KZ_HIP(hipMemcpyAsync(ctx->knzPin.p + rowBytes, ctx->knzAux.p + rowBytes, (size_t)CK * 8 + (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+      KZ_HIP(kz_stream_sync(ctx, ctx->stream));                    // the pinned table is the next launch's
+      kz_ktimer_flush(ctx);
+      const uint64_t* hw = (const uint64_t*)(ctx->knzPin.p + rowBytes);
+      const int64_t* bad = (const int64_t*)(hw + CK);
+      for (int i = 0; i < cnt; i++) {
+        const Entry& e = ent[(size_t)i];
+        if (e.row >= 0) hdrs[(size_t)e.row] = hw[i];
+        if (!bad[i] || !use[(size_t)e.s]) continue;                // (of a stream's bad entries the first in block order is named)
+        char why[96];
+        snprintf(why, sizeof(why), "index entry %d does not match the stream", (int)e.k);
+        F.fail(e.s, -KZ_ERR_INVALID_PARAM, call, why);
+        use[(size_t)e.s] = 0;
+        dropped = true;
+      }
+    }
+    if (!dropped) break;
+  }
+  const int64_t nChunks = (int64_t)R.chunkGroup.size();
+  if (groups.empty()) return finish();
+  // ---- staging and tables for the largest chunk; PL = the pieces and the spans of an emit launch: the splice's chunk ----
+  int cmax = 1, PL = 1;
+  int64_t segMax = 0;
+  size_t inMax = 0, outMax = 0, encMax = 0;
+  for (size_t g = 0; g < groups.size(); g++) PL = std::max(PL, chunkBlocks[g]);
+  for (int64_t c = 0; c < nChunks; c++) {
+    const int cnt = (int)(R.chunkRow[(size_t)c + 1] - R.chunkRow[(size_t)c]);
+    const KnzPlan& G = groups[(size_t)R.chunkGroup[(size_t)c]];
+    cmax = std::max(cmax, cnt);
+    inMax = std::max(inMax, (size_t)cnt * (size_t)G.iS);
+    outMax = std::max(outMax, (size_t)cnt * (size_t)G.h.blockSize);
+    encMax = std::max(encMax, (size_t)cnt * (size_t)kz_max_block_stream_bytes(G.h.blockSize));
+  }
+  for (size_t l = 0; l + 1 < R.cuts.size(); l++) segMax = std::max(segMax, R.cuts[l + 1] - R.cuts[l]);
+  {
+    int rc = kz_stage_reserve(ctx, ctx->devIn[0], std::max<size_t>(inMax, 64), false);
+    if (!rc) rc = kz_stage_reserve(ctx, ctx->devOut[0], std::max<size_t>(outMax, 64), false);
+    if (!rc) rc = kz_stage_reserve(ctx, ctx->devOut[1], std::max<size_t>(encMax, 64), false);
+    if (!rc) rc = knz_tables(ctx, std::max(std::max((size_t)cmax * sizeof(KnzRow), (size_t)segMax * std::max(sizeof(KnzWriteSeg), sizeof(KnzCopy))), KnzEmit::bytes(PL)));
+    if (rc) return rc;
+  }
+  uint8_t* rows = ctx->devOut[0].p;
+  uint8_t* enc = ctx->devOut[1].p;
+  if ((uintptr_t)rows & 15) { snprintf(ctx->err, sizeof(ctx->err), "%s: staging rows off a 16-byte boundary", call); return -KZ_ERR_DEVICE; }   // (unit0 counts on it)
+  // ---- what every written stream has in the new stream so far ----
+  std::vector<int64_t> pos((size_t)ns, 0), nextBlk((size_t)ns, 0), tDone((size_t)ns, 0);
+  std::vector<uint8_t> started((size_t)ns, 0);
+  KnzEmit E{ctx, d_src, d_dst, PL};
+  // Blocks [nextBlk[s], k1) of stream s behind its last bit, then tailBits zero bits: the blocks of the chunk's rows [i, j) (r0: the
+  // chunk's first row; eW: their bits) come from the encoder's rows oS apart, all others from where they lie in the stream.  The room
+  // is decided from the bit arithmetic before anything of it enters a launch.
+  auto emit = [&](int s, int64_t k1, int64_t r0, int i, int j, const int64_t* eW, int64_t oS, int tailBits) -> int {
+    const int64_t e0 = indexFirst[s];
+    uint8_t nh[32];
+    int64_t p = pos[(size_t)s];
+    int hdrBytes = 0;
+    if (!started[(size_t)s]) {                                     // the new stream's header: the old one's parameters and size
+      const KnzHeader& h = plan[(size_t)s].h;
+      HostBits hb{nh, 32, 0, false};
+      write_stream_header(hb, h.transformType, (uint32_t)h.entropyType, h.blockSize, h.inputSize, h.chkKind);
+      p = (int64_t)hb.pos;
+      hdrBytes = (int)(hb.pos >> 3);
+    }
+    int64_t q = p;
+    { int t = i; for (int64_t k = nextBlk[(size_t)s]; k < k1; k++) { const bool rec = t < j && R.rowBlock[(size_t)(r0 + t)] == k; const int64_t W = rec ? eW[t++] : blockBits[e0 + k]; q += 5 + knz_prefix_width((uint64_t)W) + W; } }
+    if (((q + tailBits + 7) >> 3) > dstCap[s]) { F.fail(s, -KZ_ERR_WRITE_FILE, call, "destination too small"); return 0; }
+    E.begin(dstOff[s], started[(size_t)s] ? p : 0, nh, hdrBytes);
+    int t = i;
+    for (int64_t k = nextBlk[(size_t)s]; k < k1; k++) {
+      const bool rec = t < j && R.rowBlock[(size_t)(r0 + t)] == k;
+      const int64_t W = rec ? eW[t] : blockBits[e0 + k];
+      const int64_t pay = p + 5 + knz_prefix_width((uint64_t)W);
+      const int rc = E.piece(p, rec ? KnzPiece{pay, W, (int64_t)((intptr_t)(enc + (int64_t)t * oS) - (intptr_t)d_src), (W + 7) >> 3, 0, 0}
+                                    : KnzPiece{pay, W, srcOff[s], srcLen[s], blockBitOff[e0 + k], plan[(size_t)s].hdrEnd});
+      if (rc) return rc;
+      if (newBitOff) { newBitOff[e0 + k] = pay; newBits[e0 + k] = W; }
+      if (rec) t++;
+      p = pay + W;
+    }
+    p += tailBits;
+    started[(size_t)s] = 1; pos[(size_t)s] = p; nextBlk[(size_t)s] = k1;
+    return E.end(p);
+  };
+  // the named streams with no touched block, ascending: whole copies
+  std::vector<int32_t> copies;
+  for (int k = 0; k < nn; k++) if (use[(size_t)ids[(size_t)k]] && wp[(size_t)ids[(size_t)k]].blocks.empty()) copies.push_back(ids[(size_t)k]);
+  size_t nextCopy = 0;
+  // ---- chunks: decode under the group's header, settle per stream, patch, encode, emit ----
+  ChecksumScope chk(ctx, ctx->checksum);                           // each chunk runs under its own group's kind and block size
+  BlockSizeScope scope(ctx, ctx->blockSize);
+  std::vector<kz_block_result> res((size_t)cmax), eres((size_t)cmax);
+  std::vector<int64_t> W((size_t)cmax), off((size_t)cmax), eW((size_t)cmax);
+  std::vector<int32_t> lens((size_t)cmax);
+  std::vector<uint8_t> leftOut((size_t)cmax);
+  size_t li = 0;                                                  // the next patch launch of the plan
+  for (int64_t c = 0; c < nChunks; c++) {
+    const int64_t r0 = R.chunkRow[(size_t)c];
+    const int cnt = (int)(R.chunkRow[(size_t)c + 1] - r0);
+    const KnzPlan& G = groups[(size_t)R.chunkGroup[(size_t)c]];
+    const KnzHeader& h = G.h;
+    const int32_t blockSize = h.blockSize;
+    const int64_t oS = kz_max_block_stream_bytes(blockSize);
+    ctx->checksum = h.chkKind;
+    ctx->blockSize = blockSize; ctx->blockSizeSet = true;
+    for (int i = 0; i < cnt; i++) {
+      const int s = R.rowStream[(size_t)(r0 + i)];
+      const int64_t e = indexFirst[s] + R.rowBlock[(size_t)(r0 + i)];
+      leftOut[(size_t)i] = (R.rowCovered[(size_t)(r0 + i)] || F.code[(size_t)s]) ? 1 : 0;   // a failed stream's rows are left out from here on
+      off[(size_t)i] = leftOut[(size_t)i] ? 0 : blockBitOff[e]; W[(size_t)i] = leftOut[(size_t)i] ? 0 : blockBits[e];
+      memset(&res[(size_t)i], 0, sizeof(res[0]));
+      res[(size_t)i].status = 1;
+    }
+    KnzRow* t = (KnzRow*)(ctx->knzPin.p + 64);
+    // (behind it the pinned table becomes the segments')
+    {
+      const int rc = knz_chunk_decode_rows(ctx, G, [&](int i) { return srcLen[R.rowStream[(size_t)(r0 + i)]]; }, off.data(), W.data(), &hdrs[(size_t)r0], leftOut.data(), cnt,
+        [&](int i, int64_t o, int64_t bits) { const int s = R.rowStream[(size_t)(r0 + i)]; t[i] = KnzRow{srcOff[s], srcLen[s], o, bits, (int64_t)i * G.iS}; },
+        [&](int64_t maxBytes) -> int {
+          KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + 64, t, (size_t)cnt * sizeof(KnzRow), hipMemcpyHostToDevice, ctx->stream));
+          return kz_knz_unpack_many(ctx, d_src, (const KnzRow*)(ctx->knzAux.p + 64), cnt, maxBytes, ctx->devIn[0].p);
+        }, rows, blockSize, res.data());
+      if (rc) return rc;
+    }
+    // ---- the settle: a wholly covered block counts as decoded to the table's length; per stream the length check of every block in
+    //      block order and, without a table, the segments against the real end of a short last block ----
+    for (int i = 0; i < cnt; i++) {
+      const int s = R.rowStream[(size_t)(r0 + i)];
+      const int32_t k = R.rowBlock[(size_t)(r0 + i)];
+      lens[(size_t)i] = 0;
+      if (F.code[(size_t)s]) continue;
+      if (R.rowCovered[(size_t)(r0 + i)]) { res[(size_t)i].status = 0; res[(size_t)i].length = (int32_t)(tab[(size_t)s][k + 1] - tab[(size_t)s][k]); }
+      const char* why = "its decode failed";
+      if (!res[(size_t)i].status) {
+        res[(size_t)i].status = knz_block_len_check(tab[(size_t)s], nIdx[(size_t)s], blockSize, k, res[(size_t)i].length);
+        why = res[(size_t)i].status == -KZ_ERR_PROCESS_BLOCK ? "decodes to more than the block size" : "decodes to another length than its place in the data";
+      }
+      if (res[(size_t)i].status) {
+        char text[128];
+        snprintf(text, sizeof(text), "block %d: %s", (int)k, why);
+        F.fail(s, res[(size_t)i].status, call, text);
+        continue;
+      }
+      lens[(size_t)i] = res[(size_t)i].length;
+    }
+    for (int64_t q = R.first[(size_t)c]; q < R.first[(size_t)c + 1]; q++) {
+      const KnzWriteSeg& g = R.segs[(size_t)q];
+      const int s = R.rowStream[(size_t)(r0 + g.slot)];
+      if (F.code[(size_t)s] || tab[(size_t)s] || (int64_t)g.off + g.len <= lens[(size_t)g.slot]) continue;
+      char text[96];
+      snprintf(text, sizeof(text), "range %d ends behind the data", (int)g.range);
+      F.fail(s, -KZ_ERR_INVALID_PARAM, call, text);
+    }
+    // ---- the patch: the chunk's segments into the rows (a failed stream's land in rows that nobody reads) ----
+    for (; li + 1 < R.cuts.size() && R.cuts[li] < R.first[(size_t)c + 1]; li++) {   // (a launch's segments are of one chunk)
+      const int64_t s0 = R.cuts[li], s1 = R.cuts[li + 1];
+      const int nseg = (int)(s1 - s0);
+      if (ctx->sw.writeGather) {                                   // the yardstick: the same segments through the ragged copy, a workgroup column each
+        KnzCopy* ct = (KnzCopy*)(ctx->knzPin.p + 64);
+        int64_t maxLen = 0;
+        for (int i = 0; i < nseg; i++) {
+          const KnzWriteSeg& g = R.segs[(size_t)(s0 + i)];
+          ct[i] = KnzCopy{g.src, (int64_t)g.slot * blockSize + g.off, g.len};
+          maxLen = std::max<int64_t>(maxLen, g.len);
+        }
+        KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + 64, ct, (size_t)nseg * sizeof(KnzCopy), hipMemcpyHostToDevice, ctx->stream));
+        { const int rc = kz_knz_gather(ctx, d_data, (const KnzCopy*)(ctx->knzAux.p + 64), nseg, maxLen, rows); if (rc) return rc; }
+      } else {
+        memcpy(ctx->knzPin.p + 64, &R.segs[(size_t)s0], (size_t)nseg * sizeof(KnzWriteSeg));
+        KZ_HIP(hipMemcpyAsync(ctx->knzAux.p + 64, ctx->knzPin.p + 64, (size_t)nseg * sizeof(KnzWriteSeg), hipMemcpyHostToDevice, ctx->stream));
+        const int64_t u0 = R.segs[(size_t)s0].unit0, uEnd = s1 < R.first[(size_t)c + 1] ? R.segs[(size_t)s1].unit0 : R.units[(size_t)c];
+        const int rc = kz_knz_write(ctx, d_data, dataLen, (const KnzWriteSeg*)(ctx->knzAux.p + 64), nseg, rows, blockSize, u0, uEnd - u0);
+        if (rc) return rc;
+      }
+      KZ_HIP(kz_stream_sync(ctx, ctx->stream));                    // the pinned table is the next launch's; the encoder takes its input to be complete
+      kz_ktimer_flush(ctx);
+    }
+    // ---- one batched encode of the chunk's rows with the chain of the group's header; the rows of failed streams are left out of
+    //      it, so what stands side by side goes in one call ----
+    for (int i = 0; i < cnt;) {
+      if (F.code[(size_t)R.rowStream[(size_t)(r0 + i)]]) { i++; continue; }
+      int j = i + 1;
+      while (j < cnt && !F.code[(size_t)R.rowStream[(size_t)(r0 + j)]]) j++;
+      const int rc = kz_encode_blocks_pre(ctx, h.transformType, (uint32_t)h.entropyType, blockSize, rows + (int64_t)i * blockSize, blockSize, lens.data() + i, j - i,
+                                          enc + (int64_t)i * oS, oS, eres.data() + i, KZ_MEM_DEVICE, nullptr);
+      if (rc) return rc;
+      i = j;
+    }
+    for (int i = 0; i < cnt; i++) {
+      const int s = R.rowStream[(size_t)(r0 + i)];
+      if (F.code[(size_t)s]) continue;
+      if (eres[(size_t)i].status || eres[(size_t)i].bits <= 0) {
+        char text[96];
+        snprintf(text, sizeof(text), "block %d: its encode failed", (int)R.rowBlock[(size_t)(r0 + i)]);
+        F.fail(s, eres[(size_t)i].status ? eres[(size_t)i].status : -KZ_ERR_PROCESS_BLOCK, call, text);
+        continue;
+      }
+      eW[(size_t)i] = eres[(size_t)i].bits;
+    }
+    // ---- the emit: per stream with rows here every kept block since its last emitted one and its recoded ones; with the stream's last
+    //      touched block also its kept tail and the end marker (:491-492).  Whole copies ride along while the launch has room ----
+    for (int i = 0; i < cnt;) {                                    // the rows of a stream lie side by side
+      const int s = R.rowStream[(size_t)(r0 + i)];
+      int j = i + 1;
+      while (j < cnt && R.rowStream[(size_t)(r0 + j)] == s) j++;
+      if (!F.code[(size_t)s]) {
+        const bool last = tDone[(size_t)s] + (j - i) == (int64_t)wp[(size_t)s].blocks.size();
+        const int64_t k1 = last ? nIdx[(size_t)s] : (int64_t)R.rowBlock[(size_t)(r0 + j - 1)] + 1;
+        const int rc = emit(s, k1, r0, i, j, eW.data(), oS, last ? 8 : 0);
+        if (rc) return rc;
+        tDone[(size_t)s] += j - i;
+      }
+      i = j;
+    }
+    for (; nextCopy < copies.size() && E.nsp > 0 && E.nsp < E.cap && nIdx[(size_t)copies[nextCopy]] <= E.room(); nextCopy++) {
+      const int s = copies[nextCopy];
+      const int rc = emit(s, nIdx[(size_t)s], 0, 0, 0, nullptr, 0, 8);
+      if (rc) return rc;
+    }
+    { const int rc = E.flush(); if (rc) return rc; }               // the encoder's rows are the next chunk's
+  }
+  // ---- the whole copies that found no room ----
+  for (; nextCopy < copies.size(); nextCopy++) {
+    const int s = copies[nextCopy];
+    const int rc = emit(s, nIdx[(size_t)s], 0, 0, 0, nullptr, 0, 8);
+    if (rc) return rc;
+  }
+  { const int rc = E.flush(); if (rc) return rc; }
+  for (int k = 0; k < nn; k++) {
+    const int s = ids[(size_t)k];
+    if (!F.code[(size_t)s]) dstLen[s] = (pos[(size_t)s] + 7) >> 3;
+  }
+  return finish();
+}

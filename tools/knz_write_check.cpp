@@ -1,5 +1,6 @@
 // knz_write_check.cpp -- the host-only plan of the byte-addressed writes (kanzi_amd/csrc/kz_knz_host.h: knz_write_args, knz_write_plan,
-// knz_write_settle, knz_write_bound, knz_write_walk) under the sanitizers, on the CPU:
+// knz_write_settle, knz_write_bound, knz_write_walk, and the many-stream form's knz_write_many_args, knz_write_plan_at, knz_write_many_plan,
+// knz_write_many_bound) under the sanitizers, on the CPU:
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I kanzi_amd/csrc tools/knz_write_check.cpp -o /tmp/knz_write_check && /tmp/knz_write_check
 // Every array is a heap allocation of the exact size, so a read or write one element outside it is reported.  The plan is compared
 // with a per-byte simulation: the ranges applied in argument order to an array of owner ids say which range owns every byte, and the
@@ -326,7 +327,112 @@ static void check_walk() {
   }
 }
 
+// The many-stream form (knz_write_many_args, knz_write_plan_at, knz_write_many_plan, knz_write_many_bound): streams of random block
+// counts in random header groups, ranges of all of them interleaved in one call with their new bytes packed over the whole call.  Each
+// stream's plan with explicit places must be its own plan on data packed for it alone, moved to the call's places; the merged rows must
+// ascend by (group, stream, block) and the chunks stay inside a group and its size; the merged segments, applied to rows of the
+// blocks' lengths, must give every stream's ranges applied one after the other.
+static void check_many() {
+  const int32_t bs = 1024;
+  for (int round = 0; round < 300; round++) {
+    const int ns = 1 + (int)(rnd() % 7), nGroups = 1 + (int)(rnd() % 3), nr = (int)(rnd() % 40);
+    std::vector<int32_t> nIdx((size_t)ns), grp((size_t)ns), rs;
+    std::vector<int> chunkBlocks((size_t)nGroups);
+    for (int g = 0; g < nGroups; g++) chunkBlocks[(size_t)g] = 1 + (int)(rnd() % 4);
+    for (int s = 0; s < ns; s++) { nIdx[(size_t)s] = 1 + (int32_t)(rnd() % 6); grp[(size_t)s] = (int32_t)(rnd() % (uint32_t)nGroups); }
+    std::vector<int64_t> ro, rl, D(1, 0);
+    for (int i = 0; i < nr; i++) {
+      const int32_t s = (int32_t)(rnd() % (uint32_t)ns);
+      const int64_t n = (int64_t)nIdx[(size_t)s] * bs, len = rnd() % 5 == 0 ? 0 : 1 + rnd() % (rnd() % 3 ? 40 : 2500);
+      const int64_t l = std::min<int64_t>(len, n), o = (int64_t)(rnd() % (uint64_t)(n - l + 1));
+      rs.push_back(s); ro.push_back(o); rl.push_back(l); D.push_back(D.back() + l);
+    }
+    // the arguments: a complete call passes, a wrong dataLen and a stream out of range do not
+    std::vector<int64_t> srcOff((size_t)ns, 0), srcLen((size_t)ns, 100), first((size_t)ns + 1, 0), cap((size_t)ns, 1 << 20), dl((size_t)ns, 0);
+    for (int s = 0; s < ns; s++) first[(size_t)s + 1] = first[(size_t)s] + nIdx[(size_t)s];
+    std::vector<int64_t> eo((size_t)first.back(), 200), ew((size_t)first.back(), 80);
+    const uint8_t one = 0;
+    auto args = [&](int64_t dataLen, const int32_t* streams) {
+      return knz_write_many_args(&one, srcOff.data(), srcLen.data(), ns, first.data(), eo.data(), ew.data(), nullptr, nullptr, streams, ro.data(), rl.data(), nr, &one, dataLen,
+                                 &one, srcOff.data(), cap.data(), dl.data(), nullptr, nullptr);
+    };
+    CHECK(args(D.back(), rs.data()) == 0, "many args refuse a good call");
+    CHECK(args(D.back() + 1, rs.data()) == -KZ_ERR_INVALID_PARAM, "many args take a wrong dataLen");
+    if (nr) { std::vector<int32_t> bad = rs; bad[0] = ns; CHECK(args(D.back(), bad.data()) == -KZ_ERR_INVALID_PARAM, "many args take a stream out of range"); }
+    std::vector<int32_t> bsz((size_t)ns, bs);
+    std::vector<int64_t> slotCap((size_t)ns, 0);
+    int64_t sum = 0;
+    const int64_t total = knz_write_many_bound(first.data(), ew.data(), bsz.data(), ns, slotCap.data());
+    for (int s = 0; s < ns; s++) { CHECK(slotCap[(size_t)s] == knz_write_bound(ew.data() + first[(size_t)s], nIdx[(size_t)s], bs), "many bound: slot %d", s); sum += slotCap[(size_t)s]; }
+    CHECK(total == sum, "many bound: the sum");
+    // per stream: the plan with explicit places against the plan on data packed for the stream alone
+    std::vector<KnzWritePlan> wp((size_t)ns);
+    std::vector<std::vector<int32_t>> ids((size_t)ns);
+    std::vector<KnzManyWriteIn> st((size_t)ns);
+    for (int s = 0; s < ns; s++) {
+      std::vector<int64_t> o, l, d;
+      for (int i = 0; i < nr; i++) if (rs[(size_t)i] == s) { o.push_back(ro[(size_t)i]); l.push_back(rl[(size_t)i]); d.push_back(D[(size_t)i]); ids[(size_t)s].push_back(i); }
+      const int32_t n = (int32_t)o.size();
+      auto eo_ = exact(o); auto el_ = exact(l); auto ed_ = exact(d);
+      KnzWritePlan alone;
+      CHECK(knz_write_plan_at(nullptr, nIdx[(size_t)s], bs, eo_.get(), el_.get(), ed_.get(), n, 0x7FFFFFFF, INT64_MAX, wp[(size_t)s]) == -1, "plan_at refuses stream %d", s);
+      CHECK(knz_write_plan(nullptr, nIdx[(size_t)s], bs, eo_.get(), el_.get(), n, 0x7FFFFFFF, INT64_MAX, alone) == -1, "plan refuses stream %d", s);
+      CHECK(alone.blocks == wp[(size_t)s].blocks && alone.covered == wp[(size_t)s].covered && alone.segs.size() == wp[(size_t)s].segs.size(), "stream %d: other blocks", s);
+      std::vector<int64_t> Dl(1, 0);
+      for (int32_t i = 0; i < n; i++) Dl.push_back(Dl.back() + l[(size_t)i]);
+      for (size_t i = 0; i < alone.segs.size(); i++) {
+        const KnzWriteSeg &a = alone.segs[i], &b = wp[(size_t)s].segs[i];
+        CHECK(a.range == b.range && a.slot == b.slot && a.off == b.off && a.len == b.len && b.src - d[(size_t)b.range] == a.src - Dl[(size_t)a.range], "stream %d segment %d", s, (int)i);
+      }
+      st[(size_t)s] = KnzManyWriteIn{n > 0 && rnd() % 8 != 0, grp[(size_t)s], &wp[(size_t)s], ids[(size_t)s].data()};   // (now and then a stream has left the plan)
+    }
+    const int64_t launch = 1 + rnd() % 5;
+    KnzManyWritePlan R;
+    knz_write_many_plan(st.data(), ns, chunkBlocks.data(), launch, R);
+    const size_t rows = R.rowStream.size(), nc = R.chunkGroup.size();
+    size_t want = 0;
+    for (int s = 0; s < ns; s++) if (st[(size_t)s].use) want += wp[(size_t)s].blocks.size();
+    CHECK(rows == want && R.rowBlock.size() == rows && R.rowCovered.size() == rows && R.chunkRow.size() == nc + 1 && R.first.size() == nc + 1 && R.units.size() == nc, "merged sizes");
+    for (size_t r = 1; r < rows; r++) {
+      const int32_t a = R.rowStream[r - 1], b = R.rowStream[r];
+      CHECK(grp[(size_t)a] < grp[(size_t)b] || (grp[(size_t)a] == grp[(size_t)b] && (a < b || (a == b && R.rowBlock[r - 1] < R.rowBlock[r]))), "rows do not ascend at %d", (int)r);
+    }
+    for (size_t c = 0; c < nc; c++) {
+      const int64_t a = R.chunkRow[c], b = R.chunkRow[c + 1];
+      CHECK(b > a && b - a <= chunkBlocks[(size_t)R.chunkGroup[c]], "chunk %d has %lld rows", (int)c, (long long)(b - a));
+      for (int64_t r = a; r < b; r++) CHECK(grp[(size_t)R.rowStream[(size_t)r]] == R.chunkGroup[c], "chunk %d mixes groups", (int)c);
+      int64_t u = 0;
+      for (int64_t i = R.first[c]; i < R.first[c + 1]; i++) {
+        const KnzWriteSeg& g = R.segs[(size_t)i];
+        CHECK(g.slot >= 0 && g.slot < b - a && g.unit0 == u && g.len > 0 && (int64_t)g.off + g.len <= bs, "chunk %d segment %lld", (int)c, (long long)i);
+        CHECK(rs[(size_t)g.range] == R.rowStream[(size_t)(a + g.slot)] && g.src >= D[(size_t)g.range] && g.src + g.len <= D[(size_t)g.range + 1], "segment %lld names another range", (long long)i);
+        u += knz_read_units(g.off & 15, g.len);
+      }
+      CHECK(u == R.units[c], "chunk %d units", (int)c);
+    }
+    CHECK(R.cuts.front() == 0 && R.cuts.back() == (int64_t)R.segs.size(), "cuts do not cover the segments");
+    for (size_t q = 0; q + 1 < R.cuts.size(); q++) CHECK(R.cuts[q + 1] > R.cuts[q] && R.cuts[q + 1] - R.cuts[q] <= launch, "launch %d", (int)q);
+    // the patch through the merged segments = every stream's ranges one after the other
+    for (int s = 0; s < ns; s++) {
+      if (!st[(size_t)s].use) continue;
+      const int64_t n = (int64_t)nIdx[(size_t)s] * bs;
+      std::vector<uint8_t> seq((size_t)n), got((size_t)n);
+      for (int64_t i = 0; i < n; i++) seq[(size_t)i] = got[(size_t)i] = orig_byte(i + s);
+      for (int i = 0; i < nr; i++) if (rs[(size_t)i] == s) for (int64_t j = 0; j < rl[(size_t)i]; j++) seq[(size_t)(ro[(size_t)i] + j)] = new_byte(i, j);
+      for (size_t c = 0; c < nc; c++)
+        for (int64_t i = R.first[c]; i < R.first[c + 1]; i++) {
+          const KnzWriteSeg& g = R.segs[(size_t)i];
+          const int64_t r = R.chunkRow[c] + g.slot;
+          if (R.rowStream[(size_t)r] != s) continue;
+          for (int32_t j = 0; j < g.len; j++) got[(size_t)((int64_t)R.rowBlock[(size_t)r] * bs + g.off + j)] = new_byte(g.range, g.src - D[(size_t)g.range] + j);
+        }
+      CHECK(seq == got, "stream %d: the merged segments give other bytes", s);
+    }
+  }
+}
+
 int main() {
+  check_many();
   check_refusals();
   check_cases();
   check_random();
