@@ -63,6 +63,7 @@ void kz_switches_read(kz_switches& s) {
   s.writeGather = flag("KZ_WRITE_GATHER");
   s.bwtTrie = num("KZ_BWT_TRIE", -1); s.bwtTrieWin = num("KZ_BWT_TRIEWIN", -1); s.bwtBuckets = num("KZ_BWT_BUCKETS", -1);
   s.bwtDmax = num("KZ_BWT_DMAX", -1); s.bwtRetire = num("KZ_BWT_RETIRE", -1); s.bwtLazyRank = num("KZ_BWT_LAZYRANK", -1);
+  s.bwtLivePart = num("KZ_BWT_LIVEPART", -1);
   s.bwtTrace = flag("KZ_BWT_TRACE");
   s.bwtTestTrieOverflow = digit("KZ_BWT_TEST_TRIE_OVERFLOW", 0, 9, -1);
   s.cmTestRowBytes = num("KZ_CM_TEST_ROW_BYTES", 0);

@@ -226,6 +226,7 @@ struct BwtRun {
   int bitsR, bitsG, nBuckets, Dmax;
   bool useBuckets, useTrie;
   bool noRetire, trieWinOff, lazyRank, trace; int forceOvfRound;      // the context's switches (kz_switches: read when the context was created)
+  int livePart; bool fromRanks;                                        // KZ_BWT_LIVEPART; this round's bucket partition reads the ranks (k_live_hist counted)
   u64 *kC, *kF; u32 *vC, *vF;                                          // the compact pairs: current / free
   void swap() { std::swap(kC, kF); std::swap(vC, vF); }
   int nAct;                                                            // grid rows of the later rounds: blocks with live suffixes (A.act)

@@ -111,10 +111,11 @@ __global__ __launch_bounds__(256) void k_radix_scan(BwtArrays A) {
 // LDS is sorted and applied by one workgroup (k_bucket_sort): one read of the pair instead of six LSD passes.
 // Buckets above BK_CAP elements (long runs: one old group of many thousand suffixes) are placed BEHIND the small ones,
 // in bucket order, and that window [d_w, d_m) goes through the LSD passes and k_seg_* as before.
-__global__ __launch_bounds__(MSD_BINS) void k_msd_scan(BwtArrays A) {
+// byText: the counts come from k_live_hist, one row of bins per sort tile of the TEXT (a block without live suffixes has none).
+__global__ __launch_bounds__(MSD_BINS) void k_msd_scan(BwtArrays A, int byText) {
   const int b = bw_row_block(A, blockIdx.x);
   const int m = A.d_m[b];
-  const int tiles = (m + RSORT_TILE - 1) / RSORT_TILE;
+  const int tiles = ((byText ? (m > 0 ? A.d_n[b] : 0) : m) + RSORT_TILE - 1) / RSORT_TILE;
   __shared__ u32 lds[32];
   u32* h = A.tileHist + (int64_t)b * A.HS;
   u32 run = 0;
@@ -249,6 +250,66 @@ __global__ __launch_bounds__(RSC_WG) void k_radix_scatter0(u64* __restrict__ key
 }
 // The bucket partition need not be stable (k_bucket_sort orders by the whole key, and suffixes with equal keys stay
 // one group whatever their order), so the tile-local rank of an element is simply an LDS atomic on its bucket's counter.
+#define MSD_NONE 0xFFFFFFFFu
+// one row of 64 elements takes its positions in the tile's bucket counters: d = the lane's bucket, returns the position inside
+// (tile, bucket), MSD_NONE for a lane without an element.  A row of one bucket costs one atomic.
+__device__ __forceinline__ u32 msd_tile_place(u32* cnt, u32 d, bool valid, int lane, uint64_t lt) {
+  const uint64_t vm = kz_ballot(valid);
+  if (vm == 0) return MSD_NONE;
+  const int l0 = (int)__builtin_ctzll(vm);
+  const u32 d0 = (u32)__builtin_amdgcn_readlane((int)d, l0);
+  u32 pos = MSD_NONE;
+  if (kz_ballot(valid && d == d0) == vm) {
+    u32 basePos = 0;
+    if (lane == l0) basePos = atomicAdd(&cnt[d0], (u32)__popcll(vm));
+    basePos = (u32)__builtin_amdgcn_readlane((int)basePos, l0);
+    if (valid) pos = basePos + (u32)__popcll(vm & lt);
+  } else if (valid) pos = atomicAdd(&cnt[d], 1u);
+  return pos;
+}
+// ... and the tile leaves (k_msd_scatter, k_live_scatter): exclusive scan of the tile's bucket counts, gdelta = the bucket's global
+// slot for this tile (digitBase + the scanned tileHist) - its tile-local slot, then keys and values through the LDS stage so that
+// consecutive threads store consecutive elements of a bucket's run.  dr[r] = position inside (tile, bucket) or MSD_NONE.
+__device__ __forceinline__ void msd_tile_flush(const u64 (&k)[RSC_ITEMS], const u32 (&v)[RSC_ITEMS], u32 (&dr)[RSC_ITEMS], int shift,
+                                               u64* __restrict__ keyOut, u32* __restrict__ valOut, const BwtArrays& A, int b, int tile,
+                                               u32* cnt, u32* gdelta, u32* scan, u64* stage) {
+  __syncthreads();
+  u32 tcount;
+  {
+    const u32 tot = cnt[threadIdx.x];
+    const u32 ts = kz_wg_excl_sum(tot, scan, &tcount);
+    gdelta[threadIdx.x] = A.digitBase[b * MSD_BINS + threadIdx.x] + A.tileHist[(int64_t)b * A.HS + (int64_t)tile * MSD_BINS + threadIdx.x] - ts;
+    cnt[threadIdx.x] = ts;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < RSC_ITEMS; r++) {
+    if (dr[r] != MSD_NONE) { const u32 slot = cnt[(u32)(k[r] >> shift) & (MSD_BINS - 1)] + dr[r]; dr[r] = slot; stage[slot] = k[r]; }
+  }
+  __syncthreads();
+  u32 gp[RSC_ITEMS];
+#pragma unroll
+  for (int r = 0; r < RSC_ITEMS; r++) {
+    const u32 slot = (u32)r * RSC_WG + threadIdx.x;
+    if (slot < tcount) {
+      const u64 kk = stage[slot];
+      gp[r] = gdelta[(u32)(kk >> shift) & (MSD_BINS - 1)] + slot;
+      keyOut[gp[r]] = kk;
+    }
+  }
+  __syncthreads();
+  u32* stageV = (u32*)stage;
+#pragma unroll
+  for (int r = 0; r < RSC_ITEMS; r++) {
+    if (dr[r] != MSD_NONE) stageV[dr[r]] = v[r];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < RSC_ITEMS; r++) {
+    const u32 slot = (u32)r * RSC_WG + threadIdx.x;
+    if (slot < tcount) valOut[gp[r]] = stageV[slot];
+  }
+}
 __global__ __launch_bounds__(RSC_WG) void k_msd_scatter(const u64* __restrict__ keyIn, const u32* __restrict__ valIn,
                                                          u64* __restrict__ keyOut, u32* __restrict__ valOut,
                                                          BwtArrays A, int shift) {
@@ -265,7 +326,6 @@ __global__ __launch_bounds__(RSC_WG) void k_msd_scatter(const u64* __restrict__ 
   const int64_t off = (int64_t)b * A.NS;
   const int lane = kz_lane();
   const int tbase = tile * RSORT_TILE;
-  const int tcount = min(RSORT_TILE, m - tbase);
   const uint64_t lt = kz_lanemask_lt();
   u64 k[RSC_ITEMS]; u32 v[RSC_ITEMS]; u32 dr[RSC_ITEMS];
 #pragma unroll
@@ -278,57 +338,9 @@ __global__ __launch_bounds__(RSC_WG) void k_msd_scatter(const u64* __restrict__ 
 #pragma unroll
   for (int r = 0; r < RSC_ITEMS; r++) {
     const int idx = tbase + r * RSC_WG + threadIdx.x;
-    const bool valid = idx < m;
-    const u32 d = (u32)(k[r] >> shift) & (MSD_BINS - 1);
-    const uint64_t vm = kz_ballot(valid);
-    const u32 d0 = (u32)__builtin_amdgcn_readfirstlane((int)d);
-    u32 pos = 0;
-    if (vm != 0 && kz_ballot(valid && d == d0) == vm) {             // one bucket for the whole row: one atomic
-      u32 basePos = 0;
-      if (lane == (int)__builtin_ctzll(vm)) basePos = atomicAdd(&cnt[d0], (u32)__popcll(vm));
-      basePos = (u32)__shfl((int)basePos, (int)__builtin_ctzll(vm), 64);
-      pos = basePos + (u32)__popcll(vm & lt);
-    } else if (valid) pos = atomicAdd(&cnt[d], 1u);
-    dr[r] = pos;
+    dr[r] = msd_tile_place(cnt, (u32)(k[r] >> shift) & (MSD_BINS - 1), idx < m, lane, lt);
   }
-  __syncthreads();
-  {
-    const u32 tot = cnt[threadIdx.x];
-    u32 total;
-    const u32 ts = kz_wg_excl_sum(tot, scan, &total);
-    gdelta[threadIdx.x] = A.digitBase[b * MSD_BINS + threadIdx.x] + A.tileHist[(int64_t)b * A.HS + (int64_t)tile * MSD_BINS + threadIdx.x] - ts;
-    cnt[threadIdx.x] = ts;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < RSC_ITEMS; r++) {
-    const int idx = tbase + r * RSC_WG + threadIdx.x;
-    if (idx < m) { const u32 slot = cnt[(u32)(k[r] >> shift) & (MSD_BINS - 1)] + dr[r]; dr[r] = slot; stage[slot] = k[r]; }
-  }
-  __syncthreads();
-  u32 gp[RSC_ITEMS];
-#pragma unroll
-  for (int r = 0; r < RSC_ITEMS; r++) {
-    const int slot = r * RSC_WG + threadIdx.x;
-    if (slot < tcount) {
-      const u64 kk = stage[slot];
-      gp[r] = gdelta[(u32)(kk >> shift) & (MSD_BINS - 1)] + (u32)slot;
-      keyOut[off + gp[r]] = kk;
-    }
-  }
-  __syncthreads();
-  u32* stageV = (u32*)stage;
-#pragma unroll
-  for (int r = 0; r < RSC_ITEMS; r++) {
-    const int idx = tbase + r * RSC_WG + threadIdx.x;
-    if (idx < m) stageV[dr[r]] = v[r];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < RSC_ITEMS; r++) {
-    const int slot = r * RSC_WG + threadIdx.x;
-    if (slot < tcount) valOut[off + gp[r]] = stageV[slot];
-  }
+  msd_tile_flush(k, v, dr, shift, keyOut + off, valOut + off, A, b, tile, cnt, gdelta, scan, stage);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -826,6 +838,119 @@ __global__ __launch_bounds__(KZ_WG) void k_live_emit(u64* __restrict__ keyN, u32
   }
 }
 
+// The bucket partition of the next round straight from the ranks: where the next round takes the bucket path, the text-order list
+// above has no reader but k_msd_hist / k_msd_scatter, and 32 of the 64 bytes the three kernels move per live suffix only hand it
+// over.  k_live_hist (end of a round) counts the live suffixes of a sort tile of RSORT_TILE TEXT positions per bucket of their group
+// -- the row of bins k_msd_scan takes -- and k_live_scatter (start of the next round, behind the scan) reads the tile's ranks again,
+// builds k_live_emit's element and places it with k_msd_scatter's machinery.  Thread t of 1024 owns the positions tbase + r * 1024 +
+// t: rows r = 4q .. 4q + 3 are the RS_TILE sub-tile q of tileLive, whose dead ones are neither read nor counted.
+static_assert(RSORT_TILE == 4 * RS_TILE && RSC_ITEMS == 16, "k_live_hist / k_live_scatter: four rows of a thread per sub-tile");
+// which of the tile's four sub-tiles to read (bit q), by the round before; a sub-tile behind the end of the text has no tileLive entry
+__device__ __forceinline__ u32 live_subtiles(const BwtArrays& A, int b, int tile, int n, int first) {
+  u32 m = 0;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int sub = tile * 4 + q;
+    if ((int64_t)sub * RS_TILE < n && (first || A.tileLive[(int64_t)b * A.T + sub] != 0)) m |= 1u << q;
+  }
+  return m;
+}
+__global__ __launch_bounds__(RSC_WG) void k_live_hist(BwtArrays A, int first, const int32_t* __restrict__ lazyMeta) {
+  const int b = bw_row_block(A, blockIdx.y);
+  const int n = A.d_n[b];
+  const int tile = blockIdx.x;
+  if ((int64_t)tile * RSORT_TILE >= n) return;
+  u32* th = A.tileHist + (int64_t)b * A.HS + (int64_t)tile * MSD_BINS;
+  u32* tl = A.tileLive + (int64_t)b * A.T + tile * 4;
+  const bool inText = threadIdx.x < 4 && (int64_t)(tile * 4 + (int)threadIdx.x) * RS_TILE < n;
+  if (lazyMeta && lazyMeta[(int64_t)b * TR_META] == 256 && lazyMeta[(int64_t)b * TR_META + 18] == 0 && lazyMeta[(int64_t)b * TR_META + 20] == 0) {
+    // round 0 left no live suffix in this block and stored no ranks (k_tr_sort, lazy ranks): nothing to read, nothing to count
+    th[threadIdx.x] = 0;
+    if (inText) tl[threadIdx.x] = 0;
+    return;
+  }
+  const u32 subs = live_subtiles(A, b, tile, n, first);
+  __shared__ u32 hist[MSD_BINS];
+  __shared__ u32 subLive[4];
+  hist[threadIdx.x] = 0;
+  if (threadIdx.x < 4) subLive[threadIdx.x] = 0;
+  __syncthreads();
+  if (subs) {
+    const u32* rank = A.rank + (int64_t)b * A.NS;
+    const int lane = kz_lane();
+    const int tbase = tile * RSORT_TILE;
+    const uint64_t lt = kz_lanemask_lt();
+    u32 rk[RSC_ITEMS];
+#pragma unroll
+    for (int r = 0; r < RSC_ITEMS; r++) {
+      const int s = tbase + r * RSC_WG + (int)threadIdx.x;
+      rk[r] = ((subs >> (r >> 2)) & 1u) && s < n ? rank[s] : 0u;
+    }
+    u32 c[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < RSC_ITEMS; r++) {
+      const bool live = (rk[r] & BW_LIVE) != 0;
+      c[r >> 2] += (u32)__popcll(kz_ballot(live));
+      (void)msd_tile_place(hist, ((rk[r] & ~BW_LIVE) >> BK_BITS) & (MSD_BINS - 1), live, lane, lt);
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) if (c[q]) atomicAdd(&subLive[q], c[q]);
+    }
+  }
+  __syncthreads();
+  th[threadIdx.x] = hist[threadIdx.x];
+  if (inText) tl[threadIdx.x] = subLive[threadIdx.x];
+  if (threadIdx.x == 0) {
+    const u32 tot = subLive[0] + subLive[1] + subLive[2] + subLive[3];
+    if (tot) atomicAdd(&A.d_m2[b], (int32_t)tot);
+  }
+}
+__global__ __launch_bounds__(RSC_WG) void k_live_scatter(u64* __restrict__ keyOut, u32* __restrict__ valOut, BwtArrays A, int h, int bitsR) {
+  const int b = bw_row_block(A, blockIdx.y);
+  const int n = A.d_n[b];
+  const int tile = blockIdx.x;
+  if ((int64_t)tile * RSORT_TILE >= n || A.d_m[b] <= 0) return;
+  const u32 subs = live_subtiles(A, b, tile, n, 0);
+  if (!subs) return;                                                  // nothing left here: neither read nor written
+  __shared__ u32 cnt[MSD_BINS];
+  __shared__ u32 gdelta[MSD_BINS];
+  __shared__ u32 scan[32];
+  __shared__ u64 stage[RSORT_TILE];  // 128 KiB: keys, then values
+  cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t off = (int64_t)b * A.NS;
+  const u32* rank = A.rank + off;
+  const int lane = kz_lane();
+  const int tbase = tile * RSORT_TILE;
+  const uint64_t lt = kz_lanemask_lt();
+  const u32 hcap = (u32)min(h, n);
+  u64 k[RSC_ITEMS]; u32 v[RSC_ITEMS]; u32 dr[RSC_ITEMS];
+#pragma unroll
+  for (int r = 0; r < RSC_ITEMS; r++) {
+    const int s = tbase + r * RSC_WG + (int)threadIdx.x;
+    v[r] = (u32)s;
+    dr[r] = ((subs >> (r >> 2)) & 1u) && s < n ? rank[s] : 0u;        // the rank for now
+  }
+#pragma unroll
+  for (int r = 0; r < RSC_ITEMS; r++) {
+    k[r] = 0;
+    if (dr[r] & BW_LIVE) {
+      const int s = tbase + r * RSC_WG + (int)threadIdx.x;
+      const int64_t j = (int64_t)s + h;
+      // positions past the end (s + h >= n): n - s in [1, min(h, n)], smaller for the shorter suffix and below every real rank
+      const u64 r2 = (j < n) ? (u64)(rank[j] & ~BW_LIVE) + (u64)hcap + 1ULL : (u64)(n - s);
+      k[r] = ((u64)(dr[r] & ~BW_LIVE) << bitsR) | r2;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < RSC_ITEMS; r++) {
+    const bool live = (dr[r] & BW_LIVE) != 0;
+    dr[r] = msd_tile_place(cnt, ((dr[r] & ~BW_LIVE) >> BK_BITS) & (MSD_BINS - 1), live, lane, lt);
+  }
+  msd_tile_flush(k, v, dr, bitsR + BK_BITS, keyOut + off, valOut + off, A, b, tile, cnt, gdelta, scan, stage);
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // emit: header + BWT bytes (BWTBlockCodec.java:90-126, DivSufSort.java:217-224)
@@ -941,6 +1066,7 @@ static int bwt_plan(BwtRun& R, kz_ctx* ctx, kz_batch& bt, bool allowTrie) {
   R.noRetire = ctx->sw.bwtRetire == 0;                              // A/B switch: every block rides through every round, as before
   R.trieWinOff = ctx->sw.bwtTrieWin == 0;
   R.lazyRank = ctx->sw.bwtLazyRank != 0;
+  R.livePart = ctx->sw.bwtLivePart < 0 ? 1 : ctx->sw.bwtLivePart;   // A/B switch: 0 = every later round from the text-order list, as before
   R.trace = ctx->sw.bwtTrace != 0;
   R.forceOvfRound = ctx->sw.bwtTestTrieOverflow;                    // tests: pretend the tables overflowed in round <digit>
   R.kC = R.A.key[0]; R.kF = R.A.key[1]; R.vC = R.A.val[0]; R.vF = R.A.val[1];
@@ -950,16 +1076,27 @@ static int bwt_plan(BwtRun& R, kz_ctx* ctx, kz_batch& bt, bool allowTrie) {
   return 0;
 }
 
+// the bucket partition of the live suffixes into (kF, vF): from the ranks (k_live_hist counted at the end of the round before), or
+// from the text-order list in (kC, vC)
+static int bwt_partition(BwtRun& R) {
+  kz_ctx* ctx = R.ctx; BwtArrays& A = R.A;
+  const int nAct = R.nAct;
+  const int rt = gridFor(R.fromRanks ? R.maxN : R.mMax, RSORT_TILE);
+  const int sh = R.bitsR + BK_BITS;
+  if (!R.fromRanks) KZ_LAUNCH(ctx, KID_MSD_HIST, k_msd_hist, dim3(rt, nAct), dim3(KZ_WG), R.kC, A, sh);
+  KZ_LAUNCH(ctx, KID_MSD_SCAN, k_msd_scan, dim3(nAct), dim3(MSD_BINS), A, R.fromRanks ? 1 : 0);
+  KZ_HIP(hipMemcpyAsync(ctx->hpin, A.d_big, (size_t)R.B * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (R.fromRanks) KZ_LAUNCH(ctx, KID_MSD_SCATTER, k_live_scatter, dim3(rt, nAct), dim3(RSC_WG), R.kF, R.vF, A, R.h, R.bitsR);
+  else KZ_LAUNCH(ctx, KID_MSD_SCATTER, k_msd_scatter, dim3(rt, nAct), dim3(RSC_WG), R.kC, R.vC, R.kF, R.vF, A, sh);
+  return 0;
+}
+
 // a later round of blocks up to 4 MiB: bucket partition + one LDS kernel per bucket; what is left for the window comes back in wMax
 static int bwt_round_buckets(BwtRun& R, int round) {
   kz_ctx* ctx = R.ctx; BwtArrays& A = R.A;
   const int nAct = R.nAct, nBuckets = R.nBuckets;
-  const int rt = gridFor(R.mMax, RSORT_TILE);
-  const int sh = R.bitsR + BK_BITS;
-  KZ_LAUNCH(ctx, KID_MSD_HIST, k_msd_hist, dim3(rt, nAct), dim3(KZ_WG), R.kC, A, sh);
-  KZ_LAUNCH(ctx, KID_MSD_SCAN, k_msd_scan, dim3(nAct), dim3(MSD_BINS), A);
-  KZ_HIP(hipMemcpyAsync(ctx->hpin, A.d_big, (size_t)R.B * 4, hipMemcpyDeviceToHost, ctx->stream));
-  KZ_LAUNCH(ctx, KID_MSD_SCATTER, k_msd_scatter, dim3(rt, nAct), dim3(RSC_WG), R.kC, R.vC, R.kF, R.vF, A, sh);
+  const int rc = bwt_partition(R);
+  if (rc) return rc;
   R.swap();
   KZ_LAUNCH(ctx, KID_BUCKET_COUNT_S, k_bucket_count_s, dim3(nBuckets, nAct), dim3(256), R.kC, R.vC, A, R.bitsR, R.bitsG, (u32)BK_GMAX);
   KZ_LAUNCH(ctx, KID_BUCKET_COUNT, k_bucket_count, dim3(nBuckets, nAct), dim3(1024), R.kC, R.vC, A, R.bitsR, R.bitsG, (u32)BK_GMAX);
@@ -1001,16 +1138,38 @@ static int bwt_round_lsd(BwtRun& R, int round) {
   return 0;
 }
 
-// text order: compact the live suffixes with their keys for the next round, and read the next compact sizes back
+// text order: the live suffixes with their keys as a compact list in (kC, vC), for the rounds that sort the whole list
+static int bwt_live_list(BwtRun& R, bool first) {
+  kz_ctx* ctx = R.ctx; BwtArrays& A = R.A;
+  KZ_HIP(hipMemsetAsync(A.d_m2, 0, (size_t)R.B * 4, ctx->stream));
+  KZ_LAUNCH(ctx, KID_LIVE_EMIT, k_live_emit, dim3(gridFor(R.maxN, RS_TILE), R.nAct), dim3(KZ_WG), R.kF, R.vF, A, R.h, R.bitsR, first ? 1 : 0,
+            (first && R.useTrie && R.lazyRank) ? R.TR.meta : (const int32_t*)nullptr);
+  R.swap();
+  return 0;
+}
+// ... or only their number per bucket and sort tile of the text: a bucket round takes them from the ranks (k_live_scatter)
+static int bwt_live_count(BwtRun& R, bool first) {
+  kz_ctx* ctx = R.ctx; BwtArrays& A = R.A;
+  KZ_HIP(hipMemsetAsync(A.d_m2, 0, (size_t)R.B * 4, ctx->stream));
+  KZ_LAUNCH(ctx, KID_MSD_HIST, k_live_hist, dim3(gridFor(R.maxN, RSORT_TILE), R.nAct), dim3(RSC_WG), A, first ? 1 : 0,
+            (first && R.useTrie && R.lazyRank) ? R.TR.meta : (const int32_t*)nullptr);
+  return 0;
+}
+// does the next round partition straight from the ranks?  (livePart = N >= 2: only while the longest list is above maxN / N)
+static bool bwt_next_from_ranks(const BwtRun& R) {
+  if (!R.livePart || !R.useBuckets || R.mMax < BW_BUCKET_MIN) return false;
+  return R.livePart < 2 || (int64_t)R.mMax * R.livePart >= (int64_t)R.maxN;
+}
+
+// count or compact the live suffixes for the next round, and read the next compact sizes back
 static int bwt_compact_and_read_back(BwtRun& R, int round, bool* trieOverflow) {
   kz_ctx* ctx = R.ctx; BwtArrays& A = R.A;
   const int B = R.B;
   hipStream_t st = ctx->stream;
   R.h = (round == 0) ? (R.useTrie ? 6 : BW_K0) : R.h * 2;
-  KZ_HIP(hipMemsetAsync(A.d_m2, 0, (size_t)B * 4, st));
-  KZ_LAUNCH(ctx, KID_LIVE_EMIT, k_live_emit, dim3(gridFor(R.maxN, RS_TILE), R.nAct), dim3(KZ_WG), R.kF, R.vF, A, R.h, R.bitsR, round == 0 ? 1 : 0,
-            (round == 0 && R.useTrie && R.lazyRank) ? R.TR.meta : (const int32_t*)nullptr);
-  R.swap();
+  const bool count = R.livePart && R.useBuckets;                  // the list is written once the sizes say that the next round needs it
+  int rc = count ? bwt_live_count(R, round == 0) : bwt_live_list(R, round == 0);
+  if (rc) return rc;
   KZ_HIP(hipMemcpyAsync(ctx->hpin, A.d_m2, (size_t)B * 4, hipMemcpyDeviceToHost, st));
   // the trie tables' overflow flag rides along, every round that ran a trie (round 0 and the key rounds of the window): an
   // overflow dropped buckets, the ranks of this pass are void (the bounds of tr_max_nodes / tr_max_buckets say it cannot happen)
@@ -1025,7 +1184,9 @@ static int bwt_compact_and_read_back(BwtRun& R, int round, bool* trieOverflow) {
     fprintf(stderr, "[bwt] round %d h=%d: live %lld of %lld (%.1f%%), max per block %d\n", round, R.h, tot, totN, 100.0 * tot / (totN ? totN : 1), R.mMax);
   }
   std::swap(A.d_m, A.d_m2);
-  return 0;
+  R.fromRanks = bwt_next_from_ranks(R);
+  if (count && !R.fromRanks && R.mMax > 0) rc = bwt_live_list(R, false);      // (tileLive is k_live_hist's: no tile is `first`)
+  return rc;
 }
 
 // retire the blocks that are done: the next round's grids get one row per block that still has live suffixes

@@ -86,6 +86,8 @@ struct kz_switches {
   int writeGather = 0;           // KZ_WRITE_GATHER: kz_write_bytes_device patches its rows with k_knz_gather (tools/knz_write_probe.py's yardstick)
   int bwtTrie = -1, bwtTrieWin = -1, bwtBuckets = -1, bwtDmax = -1, bwtRetire = -1;   // KZ_BWT_TRIE / _TRIEWIN / _BUCKETS / _DMAX / _RETIRE (-1 unset)
   int bwtLazyRank = -1;         // KZ_BWT_LAZYRANK=0: round 0 stores every rank (A/B; see k_tr_sort)
+  int bwtLivePart = -1;          // KZ_BWT_LIVEPART=0: the bucket rounds partition the text-order list (k_live_emit, k_msd_hist, k_msd_scatter: A/B);
+                                 // unset / 1: straight from the ranks (k_live_hist, k_live_scatter); N >= 2: only while the longest list is above maxN / N
   int bwtTrace = 0;              // KZ_BWT_TRACE
   int bwtTestTrieOverflow = -1;  // KZ_BWT_TEST_TRIE_OVERFLOW=<round> (tests)
   int fpaqForce = 0;             // KZ_FPAQ_FORCE: 0 unset, 1 wave, 2 lane
